@@ -32,6 +32,9 @@ the HBM-side traffic.
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line (metric/value/... + "roofline" + "cpu_baseline").
+--dump-outputs DIR: right after the timed window, rank 0 writes what a caller reads of the volume (voxels, meshes, patches,
+atlas texels; seeded samples, float32 / float64 .npy, under 64 MB) -- the same arguments give the same inputs, so two builds
+can be compared output for output.
 N > 1: one process per GPU, static chunk-range partition of ONE stream (slabs of the key x + y + z) -- every
 rank sees every frame, selects / integrates / meshes / textures only the chunks of its slab ("strong"
 scaling); the ranks exchange the chunks of their ghost bands over RCCL.
@@ -96,6 +99,8 @@ def parse():
                     help="N>1: the boundary exchange serially in the stream (round 4's order) instead of next to the interior mesh pass")
     ap.add_argument("--force-exchange", action="store_true",
                     help="run the N>1 code path (partition + boundary exchange) even with one rank (smoke test)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the caller reads of the volume as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
 
 
@@ -918,6 +923,57 @@ class Job:
         return out
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: the whole dump stays under this
+ATLAS_DIM = 13824      # atlas width (and height) in texels, Structure/Atlas.h:29-30
+
+
+def dump_outputs(vol, out_dir, textured, seed=20261015):
+    """--dump-outputs DIR: the state the timed steps left in the volume, as a caller of the path reads it -- voxels of the
+    chunks, the meshes, their patches and the atlas texels -- one float32 / float64 .npy per array.  Larger outputs are a
+    sample: the same seeded draw over ids sorted ascending, so that two builds fed the same stream dump the same records."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    out = {}
+
+    def sorted_ids(ids):
+        return ids[np.lexsort((ids[:, 2], ids[:, 1], ids[:, 0]))] if len(ids) else ids
+
+    def sample(ids, n):
+        return ids if len(ids) <= n else ids[np.sort(rng.choice(len(ids), n, replace=False))]
+
+    chunks = sorted_ids(vol.list_chunks())
+    st = vol.stats()
+    out["counts"] = np.array([st.n_chunks, len(vol.list_meshes())], np.float64)
+    cid = sample(chunks, 1024)                      # 1024 chunks: 12 MB of voxels
+    sdf, w, col = vol.get_chunks(cid)
+    out.update(chunk_ids=cid.astype(np.float64), voxel_sdf=sdf, voxel_weight=w, voxel_color=col.astype(np.float32))
+    if textured:
+        meshes = sorted_ids(vol.list_meshes())
+        order = rng.permutation(len(meshes))
+        nv, ni, _, _ = vol.mesh_counts(meshes)
+        per_mesh = 4 * 11 * nv.astype(np.int64) + 8 * ni.astype(np.int64) + 64  # verts, normals, colours, texcoords; indices
+        keep = order[np.cumsum(per_mesh[order]) <= (32 << 20)]
+        mid = meshes[np.sort(keep)]
+        voff, ioff, V, N, Cc, I, _, _ = vol.get_meshes(mid)
+        P = vol.get_patches(mid)
+        out.update(mesh_ids=mid.astype(np.float64), mesh_vertex_offsets=voff.astype(np.float64),
+                   mesh_index_offsets=ioff.astype(np.float64), mesh_vertices=V, mesh_normals=N, mesh_colors=Cc,
+                   mesh_indices=I.astype(np.float64),
+                   patch_texloc=P["texloc"].astype(np.float64), patch_bbox=P["bbox"].astype(np.float64),
+                   patch_frameid=P["frameid"].astype(np.float64), patch_texcoords=P["texcoord"])
+        rows = min(ATLAS_DIM, int(P["texloc"].max()) // ATLAS_DIM + 18) if len(mid) else 0  # up to the highest patch slot
+        pick = np.sort(rng.choice(rows, min(rows, 48), replace=False)) if rows else np.zeros(0, np.int64)
+        texels = np.zeros((len(pick), ATLAS_DIM, 3), np.float32)          # 48 rows: 8 MB
+        for k, r in enumerate(pick):
+            texels[k] = vol.atlas_rows(int(r), int(r) + 1, ATLAS_DIM)[0]
+        out.update(atlas_row_ids=pick.astype(np.float64), atlas_rows=texels)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES, total
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _side_figure(fn):
     """a side figure never fails the bench line"""
     try:
@@ -940,6 +996,8 @@ def main():
     job.preroll()
     exchange_order = job.pick_exchange_order()
     job.timed_window()         # warm-up, then THE K timed steps -> job.dt, job.t_enq
+    if args.dump_outputs and rank == 0:
+        dump_outputs(vol, args.dump_outputs, job.textured)
     per_rank = job.rank_stats() if multi else None
     if args.child:  # profiler child pass: the workload above is all there is
         vol.close()
