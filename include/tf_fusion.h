@@ -395,6 +395,50 @@ TF_API int tf_clear_dirty(tf_volume* v);
 TF_API int tf_get_stats(tf_volume* v, tf_stats* out);
 TF_API int tf_get_texture_stats(tf_volume* v, tf_texture_stats* out);
 
+/* ---- reading the volume back (tf_ray.hip) -----------------------------------------------
+ * These calls only read the volume: no voxel, hash entry, dirty mark, mesh-filter summary, neighbour-table word or
+ * statistic changes.  A chunk that is not alive counts as absent (as in tf_has_chunk).  A handle with an active
+ * communicator (tf_comm_init) answers from its own chunks and the ghosts it holds; there is no multi-rank raycast.
+ *
+ * Batched point queries: n world points xyz (f32[3n]); want_mask selects the outputs, flags[i] gets one bit per
+ * output that is valid at point i (an invalid output is written as 0):
+ *   bit 0  sdf[n]      ChunkManager::GetSDF (Structure/ChunkManager.cpp:1168-1185): the voxel that contains the point,
+ *                      valid if its chunk exists and weight > 1e-12
+ *   bit 1  weight[n]   ChunkManager::GetWeight (:1151-1166): the same voxel, valid whenever its chunk exists
+ *   bit 2  grad3[3n]   ChunkManager::GetSDFAndGradient (:1043-1141, live branch): point snapped to its voxel centre,
+ *                      (x+ - x-, y+ - y-, z+ - z-) of the six face neighbours (across a chunk face: the adjacent chunk,
+ *                      voxelNeighborIndex :108-140), unnormalised; invalid if a chunk is missing or a value is >= 1
+ *                      (GetNeighborSDF, ChunkManager.h:755-788)
+ *   bit 3  sdf_tri[n]  trilinear SDF over the 8 voxel centres around the point (order of operations: tf_ray.hip),
+ *                      valid if all 8 exist with weight > 0
+ *   bit 4  rgb3[3n]    trilinear colour of the per-voxel means R / count ... (ColorVoxel.h:44-55), rounded half up to
+ *                      u8, valid if all 8 corners have count > 0
+ * tf_query_points takes host arrays, is ordered after every call already issued on the handle and returns when the
+ * results are there; _device takes device pointers and is asynchronous on the handle's stream. */
+TF_API int tf_query_points(tf_volume* v, const float* xyz, int64_t n, uint32_t want_mask, float* sdf, float* weight,
+                           float* grad3, float* sdf_tri, uint8_t* rgb3, uint32_t* flags);
+TF_API int tf_query_points_device(tf_volume* v, const float* d_xyz, int64_t n, uint32_t want_mask, float* d_sdf,
+                                  float* d_weight, float* d_grad3, float* d_sdf_tri, uint8_t* d_rgb3, uint32_t* d_flags);
+/* Model view from a pose (what frame-to-model tracking reads; the reference renders its meshes with GL instead,
+ * Chisel::DrawMeshes + MobileFusion.h:404-446).  pose: camera-to-world 3x4 as in tf_integrate.  The ray of pixel (x, y)
+ * runs through camera point ((x - cx - 0.5) / fx, (y - cy - 0.5) / fy, 1) with the int-truncated intrinsics of
+ * tf_set_camera (the integrator's projection, so a surface renders back at the depth it was integrated from) or of
+ * tf_raycast_camera.  March: whole chunks skipped where the chunk is absent, one voxel while the trilinear SDF is
+ * invalid, max(voxel, 0.75 * sdf) where it is valid; a hit is the first + -> - crossing, t refined linearly between the
+ * two samples; a - -> + crossing, t > far_plane or max_steps samples end the ray as a miss.  Outputs (NULL = not
+ * written): depth f32[H][W] camera-frame z, 0 = miss; normal f32 planar [3][H][W] world-frame unit normal from the
+ * trilinear SDF's central differences (one-sided against the hit on an axis where one tap is invalid; 0 where both are, or on a miss); rgba u8[H][W][4] the bit-4 colour,
+ * a = 255 on a hit, 0 on a miss; vertex f32 planar [3][H][W] world hit point.  Needs 0 <= near < far, max_steps > 0.
+ * tf_raycast: host outputs, synchronous; _device: device outputs, asynchronous on the handle's stream. */
+TF_API int tf_raycast(tf_volume* v, const float pose[12], float near_plane, float far_plane, int32_t max_steps,
+                      float* depth, float* normal, uint8_t* rgba, float* vertex);
+TF_API int tf_raycast_device(tf_volume* v, const float pose[12], float near_plane, float far_plane, int32_t max_steps,
+                             float* d_depth, float* d_normal, uint8_t* d_rgba, float* d_vertex);
+/* camera of the raycaster only (intrinsics truncated to int like tf_set_camera's; any width up to 32768); width = height
+ * = 0 goes back to the camera of tf_set_camera.  fx, fy >= 1; fx, fy, cx, cy finite and of magnitude below 2^31.  Every
+ * output of tf_raycast(_device) holds the W x H of the camera active at the call. */
+TF_API int tf_raycast_camera(tf_volume* v, float fx, float fy, float cx, float cy, int width, int height);
+
 /* ---- meshing (the stage between the volume and the atlas) -----
  * Chisel::UpdateMeshes (Structure/Chisel.h:479-481) -> ChunkManager::RecomputeMeshes
  *   (Structure/ChunkManager.cpp:232-264): every chunk of meshesToUpdate that exists is re-meshed by

@@ -47,7 +47,11 @@ SYMBOLS = (
     "tf_update_meshes", "tf_check_summaries", "tf_check_neighbours", "tf_list_meshes", "tf_mesh_counts", "tf_meshes_download", "tf_compress_meshes",
     "tf_pre_normal_map", "tf_pre_refine_depth_normal", "tf_pre_color_valid", "tf_pre_color_quality",
     "tf_pre_refine_newframe", "tf_pre_refine_keyframe", "tf_pre_frame_depth", "tf_integrate_depth_group", "tf_integrate_depth_group_host",
+    "tf_query_points", "tf_query_points_device", "tf_raycast", "tf_raycast_device", "tf_raycast_camera",
 )
+
+# tf_query_points want_mask bits
+Q_SDF, Q_WEIGHT, Q_GRAD, Q_SDF_TRI, Q_RGB_TRI = 1, 2, 4, 8, 16
 
 
 def host_frame_deferral():
@@ -223,6 +227,11 @@ def lib():
     L.tf_mesh_counts.argtypes = [vp, i32p, C.c_int64, i32p, i32p, u8p, u8p]
     L.tf_meshes_download.argtypes = [vp, i32p, C.c_int64, i64p, i64p, fp, fp, fp, u32p]
     L.tf_compress_meshes.argtypes = [vp, i32p, C.c_int64, i64p]
+    L.tf_query_points.argtypes = [vp, fp, C.c_int64, C.c_uint32, fp, fp, fp, fp, u8p, u32p]
+    L.tf_query_points_device.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.tf_raycast.argtypes = [vp, fp, C.c_float, C.c_float, C.c_int32, fp, fp, u8p, fp]
+    L.tf_raycast_device.argtypes = [vp, fp, C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp]
+    L.tf_raycast_camera.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -512,6 +521,63 @@ class Volume:
         st = Stats()
         self._ck(self.L.tf_get_stats(self.h, C.byref(st)))
         return st
+
+    # -- reading the volume back (tf_query_points / tf_raycast; read-only)
+    def query(self, points, want=Q_SDF | Q_WEIGHT | Q_GRAD | Q_SDF_TRI | Q_RGB_TRI):
+        """Batched GetSDF / GetWeight / GetSDFAndGradient / trilinear SDF / trilinear colour at world points [n, 3].
+        Returns a dict of numpy arrays: 'flags' (u32 [n], bit i = output i valid) and every requested output
+        ('sdf', 'weight' [n] f32, 'grad' [n, 3] f32, 'sdf_tri' [n] f32, 'rgb' [n, 3] u8)."""
+        pts = _f32(points).reshape(-1, 3)
+        n = len(pts)
+        out = {"flags": np.zeros(n, np.uint32)}
+        if want & Q_SDF:
+            out["sdf"] = np.zeros(n, np.float32)
+        if want & Q_WEIGHT:
+            out["weight"] = np.zeros(n, np.float32)
+        if want & Q_GRAD:
+            out["grad"] = np.zeros((n, 3), np.float32)
+        if want & Q_SDF_TRI:
+            out["sdf_tri"] = np.zeros(n, np.float32)
+        if want & Q_RGB_TRI:
+            out["rgb"] = np.zeros((n, 3), np.uint8)
+        g = lambda k, ty: _p(out[k], ty) if k in out else None
+        self._ck(self.L.tf_query_points(self.h, _p(pts, C.c_float), n, int(want), g("sdf", C.c_float),
+                                        g("weight", C.c_float), g("grad", C.c_float), g("sdf_tri", C.c_float),
+                                        g("rgb", C.c_uint8), _p(out["flags"], C.c_uint32)))
+        return out
+
+    def query_device(self, d_xyz, n, want, d_sdf=0, d_weight=0, d_grad=0, d_sdf_tri=0, d_rgb=0, d_flags=0):
+        self._ck(self.L.tf_query_points_device(self.h, d_xyz, n, int(want), d_sdf or None, d_weight or None,
+                                               d_grad or None, d_sdf_tri or None, d_rgb or None, d_flags or None))
+
+    def raycast_camera(self, cam=None):
+        """Camera of the raycaster only (synth.Camera-like); None = the handle's camera.  raycast() sizes its outputs
+        from the camera set here."""
+        if cam is None:
+            self._ck(self.L.tf_raycast_camera(self.h, 0.0, 0.0, 0.0, 0.0, 0, 0))
+        else:
+            self._ck(self.L.tf_raycast_camera(self.h, cam.fx, cam.fy, cam.cx, cam.cy, cam.width, cam.height))
+        self.ray_cam = cam
+
+    def raycast(self, pose, near, far, max_steps=1024):
+        """Model view from a camera-to-world pose with the raycast camera (raycast_camera, default: the handle's camera):
+        dict of 'depth' [H, W] f32, 'normal' [3, H, W] f32, 'rgba' [H, W, 4] u8, 'vertex' [3, H, W] f32."""
+        cam = getattr(self, "ray_cam", None) or getattr(self, "cam", None)
+        if cam is None:
+            raise TFError(TF_ERR_INVALID, "no camera (set_camera / raycast_camera)")
+        H, W = cam.height, cam.width
+        pose = _f32(pose).reshape(12)
+        out = {"depth": np.zeros((H, W), np.float32), "normal": np.zeros((3, H, W), np.float32),
+               "rgba": np.zeros((H, W, 4), np.uint8), "vertex": np.zeros((3, H, W), np.float32)}
+        self._ck(self.L.tf_raycast(self.h, _p(pose, C.c_float), float(near), float(far), int(max_steps),
+                                   _p(out["depth"], C.c_float), _p(out["normal"], C.c_float),
+                                   _p(out["rgba"], C.c_uint8), _p(out["vertex"], C.c_float)))
+        return out
+
+    def raycast_device(self, pose, near, far, max_steps=1024, d_depth=0, d_normal=0, d_rgba=0, d_vertex=0):
+        pose = _f32(pose).reshape(12)
+        self._ck(self.L.tf_raycast_device(self.h, _p(pose, C.c_float), float(near), float(far), int(max_steps),
+                                          d_depth or None, d_normal or None, d_rgba or None, d_vertex or None))
 
     # -- meshing (Chisel::UpdateMeshes / CompressMeshes, ChunkManager::allMeshes)
     def update_meshes(self):

@@ -1,0 +1,522 @@
+// tf_ray.hip -- reading the fused volume back: batched point queries and a device raycaster.
+//
+//   k_query    one lane per world point: ChunkManager::GetSDF / GetWeight (Structure/ChunkManager.cpp:1151-1185),
+//              GetSDFAndGradient (:1043-1141, the live #else branch), and a trilinear SDF / colour sampler
+//   k_raycast  one lane per pixel, an 8 x 8 pixel tile per wave64: depth / normal / colour / vertex maps of the model
+//              from a pose (chunk DDA over absent chunks, voxel steps where the sampler is invalid, sdf-sized steps where
+//              it is valid, linear refinement at the first + -> - crossing)
+//
+// Both kernels only READ the volume (tsdf, color, hent, nbr): no voxel, hash entry, dirty mark, summary, neighbour word
+// or statistic is written.  A chunk that is not alive counts as absent, as in tf_has_chunk.
+//
+// Trilinear sampler (bits 3 / 4 of k_query, every sample of k_raycast) -- the reference's own form is under #if 0, so its
+// arithmetic is defined here, once:
+//   g = p * (1 / res) - 0.5 per axis (voxel-centre coordinates), i = floor(g), f = g - i (all f32);
+//   corner k = dx + 2 dy + 4 dz is voxel (i.x + dx, i.y + dy, i.z + dz);
+//   lerp(a, b, t) = a + t * (b - a) (three roundings);
+//   e0 = lerp(c0, c1, fx), e1 = lerp(c2, c3, fx), e2 = lerp(c4, c5, fx), e3 = lerp(c6, c7, fx);
+//   g0 = lerp(e0, e1, fy), g1 = lerp(e2, e3, fy);  result = lerp(g0, g1, fz).
+//   SDF: valid iff all 8 corners exist with weight > 0.  Colour: per corner the mean R / count, G / count, B / count (f32
+//   divisions, ColorVoxel.h:44-55), the same lerps, then u8 = min(255, floor(x + 0.5)); valid iff all 8 counts > 0.
+// The library is built with -ffp-contract=off, so tests/raycast_ref.py restates all of this bit for bit in numpy.
+#include <math.h>
+#include <limits.h>
+#include <string.h>
+
+#include "tf_devfn.h"
+#include "tf_volume.h"
+
+#pragma clang fp contract(off)
+
+namespace tf {
+
+constexpr float kRayStepK = 0.75f;       // k of the step rule max(voxel, k * sdf)
+constexpr float kRayGap = 4.0f;          // voxels an invalid stretch may span between the two samples of a crossing
+constexpr float kVoxLimit = 8388607.0f;  // |voxel coordinate| bound: chunk ids stay inside pack_id's 21-bit range
+constexpr float kChunkLimit = 1048576.0f;
+constexpr int kRayMaxSide = 32768;       // tf_raycast_camera: largest width / height (the tile grid stays in 32 bits)
+
+// per-lane cache of the last chunk lookup
+struct ChunkCache {
+  int x, y, z;
+  uint32_t slot;
+};
+
+__device__ __forceinline__ uint32_t lookup_cached(const VolumeDev& v, ChunkCache& cc, int x, int y, int z) {
+  if (x != cc.x || y != cc.y || z != cc.z) {
+    cc.x = x; cc.y = y; cc.z = z;
+    cc.slot = hash_slot_alive(v, pack_id(x, y, z));
+  }
+  return cc.slot;
+}
+
+// floor of a float as an int, false when it is not finite or outside (-lim, lim)
+__device__ __forceinline__ bool floor_in(float a, float lim, int* out) {
+  const float f = floorf(a);
+  if (!(f > -lim && f < lim)) return false;
+  *out = (int)f;
+  return true;
+}
+
+__device__ __forceinline__ float lerpf(float a, float b, float t) { return a + t * (b - a); }
+
+__device__ __forceinline__ float tri8(const float c[8], float fx, float fy, float fz) {
+  const float e0 = lerpf(c[0], c[1], fx), e1 = lerpf(c[2], c[3], fx), e2 = lerpf(c[4], c[5], fx), e3 = lerpf(c[6], c[7], fx);
+  const float g0 = lerpf(e0, e1, fy), g1 = lerpf(e2, e3, fy);
+  return lerpf(g0, g1, fz);
+}
+
+// Trilinear SDF (and, with rgb != nullptr, colour) at world point p.  Returns the SDF validity; *okc the colour's.
+// The corners' chunks: the base corner's through the cache / hash, the others through the base chunk's row of the neighbour
+// table (a non-zero word is the neighbour's pool slot for the life of the volume) and the hash where a word
+// is 0.  A parked chunk that the table still names holds fresh voxels (weight 0, count 0): invalid, as if absent.
+template <bool kRgb>
+__device__ __forceinline__ bool tri_sample(const VolumeDev& v, ChunkCache& cc, float px, float py, float pz, float ir,
+                                           float* sdf, float* rgb = nullptr, bool* okc = nullptr) {
+  if (kRgb) *okc = false;
+  const float gx = px * ir - 0.5f, gy = py * ir - 0.5f, gz = pz * ir - 0.5f;
+  int ix, iy, iz;
+  if (!floor_in(gx, kVoxLimit, &ix) || !floor_in(gy, kVoxLimit, &iy) || !floor_in(gz, kVoxLimit, &iz)) return false;
+  const float fx = gx - floorf(gx), fy = gy - floorf(gy), fz = gz - floorf(gz);
+  const int bx = ix >> 3, by = iy >> 3, bz = iz >> 3;  // arithmetic shift = floor division
+  const int lx = ix & 7, ly = iy & 7, lz = iz & 7;
+  const uint32_t base = lookup_cached(v, cc, bx, by, bz);
+  if (base == kInvalidSlot) return false;
+  const int ox = lx == 7, oy = ly == 7, oz = lz == 7;
+  uint32_t slots[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int dx = (k & 1) & ox, dy = ((k >> 1) & 1) & oy, dz = ((k >> 2) & 1) & oz;
+    if ((dx | dy | dz) == 0) { slots[k] = base; continue; }
+    const uint32_t w = v.nbr[(size_t)base * kNbrWords + (dx + 1) + 3 * (dy + 1) + 9 * (dz + 1)];
+    slots[k] = w ? w - 1u : hash_slot_alive(v, pack_id(bx + dx, by + dy, bz + dz));
+  }
+  float c[8];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    c[k] = 0.f;
+    if (slots[k] == kInvalidSlot) { ok = false; continue; }
+    const int vx = (lx + (k & 1)) & 7, vy = (ly + ((k >> 1) & 1)) & 7, vz = (lz + ((k >> 2) & 1)) & 7;
+    const float2 sw = v.tsdf[(size_t)slots[k] * kChunkVoxels + (vz * 8 + vy) * 8 + vx];
+    if (!(sw.y > 0.f)) ok = false;
+    c[k] = sw.x;
+  }
+  if (ok) *sdf = tri8(c, fx, fy, fz);
+  if (!kRgb) return ok;
+  ushort4 q[8];  // the corners' colour words (two VGPRs each); the means are formed channel by channel
+  bool okk = true;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    q[k] = make_ushort4(0, 0, 0, 0);
+    if (slots[k] == kInvalidSlot) { okk = false; continue; }
+    const int vx = (lx + (k & 1)) & 7, vy = (ly + ((k >> 1) & 1)) & 7, vz = (lz + ((k >> 2) & 1)) & 7;
+    q[k] = v.color[(size_t)slots[k] * kChunkVoxels + (vz * 8 + vy) * 8 + vx];
+    if (q[k].w == 0) okk = false;
+  }
+  if (okk) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = (float)q[k].x / (float)q[k].w;
+    rgb[0] = fminf(255.f, floorf(tri8(c, fx, fy, fz) + 0.5f));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = (float)q[k].y / (float)q[k].w;
+    rgb[1] = fminf(255.f, floorf(tri8(c, fx, fy, fz) + 0.5f));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = (float)q[k].z / (float)q[k].w;
+    rgb[2] = fminf(255.f, floorf(tri8(c, fx, fy, fz) + 0.5f));
+  }
+  *okc = okk;
+  return ok;
+}
+
+struct QueryArgs {
+  const float* xyz;
+  uint32_t n;
+  uint32_t want;
+  float res;
+  float* sdf;
+  float* weight;
+  float* grad;
+  float* sdf_tri;
+  uint8_t* rgb;
+  uint32_t* flags;
+};
+
+// ChunkManager::GetSDF / GetWeight: the chunk GetIDAt names, the voxel Chunk::GetVoxelCoords names (relative to the chunk's
+// origin), accepted iff its linear id is in [0, 512) -- as the reference checks it
+__device__ __forceinline__ bool point_voxel(const VolumeDev& v, ChunkCache& cc, float px, float py, float pz, float res,
+                                            uint32_t* slot, int* id) {
+  const float rc = 1.0f / (8.0f * res), ir = 1.0f / res;
+  int cx, cy, cz;
+  if (!floor_in(px * rc, kChunkLimit, &cx) || !floor_in(py * rc, kChunkLimit, &cy) || !floor_in(pz * rc, kChunkLimit, &cz))
+    return false;
+  *slot = lookup_cached(v, cc, cx, cy, cz);
+  if (*slot == kInvalidSlot) return false;
+  int vx, vy, vz;
+  if (!floor_in((px - (float)(8 * cx) * res) * ir, kChunkLimit, &vx) ||
+      !floor_in((py - (float)(8 * cy) * res) * ir, kChunkLimit, &vy) ||
+      !floor_in((pz - (float)(8 * cz) * res) * ir, kChunkLimit, &vz))
+    return false;
+  const long long i = ((long long)vz * 8 + vy) * 8 + vx;
+  if (i < 0 || i >= kChunkVoxels) return false;
+  *id = (int)i;
+  return true;
+}
+
+// one face neighbour: the voxel at (wrapped) local index (nx, ny, nz), in the adjacent chunk (cid + e) when the centre
+// voxel lies on that face (cross), else in the centre chunk
+__device__ __forceinline__ bool face_sdf(const VolumeDev& v, uint32_t centre, bool cross, int cx, int cy, int cz, int nx,
+                                         int ny, int nz, float* d) {
+  uint32_t slot = centre;
+  if (cross) {
+    slot = hash_slot_alive(v, pack_id(cx, cy, cz));
+    if (slot == kInvalidSlot) return false;
+  }
+  *d = v.tsdf[(size_t)slot * kChunkVoxels + (nz * 8 + ny) * 8 + nx].x;
+  return *d < 1.f;
+}
+
+// ChunkManager::GetSDFAndGradient (live branch): snap to the voxel centre, ids by the reference's f32 arithmetic, the six
+// face neighbours (across a chunk face: the adjacent chunk at the wrapped index, voxelNeighborIndex), each must be < 1
+// (GetNeighborSDF, ChunkManager.h:755-788)
+__device__ __forceinline__ bool point_gradient(const VolumeDev& v, ChunkCache& cc, float px, float py, float pz, float res,
+                                               float* gx, float* gy, float* gz) {
+  const float half = res / 2.0f, ir = 1.0f / res, rc = 1.0f / (res * 8.0f);
+  const float qx = floorf(px / res) * res + half, qy = floorf(py / res) * res + half, qz = floorf(pz / res) * res + half;
+  int vgx, vgy, vgz, cx, cy, cz;
+  if (!floor_in(qx * ir, kVoxLimit, &vgx) || !floor_in(qy * ir, kVoxLimit, &vgy) || !floor_in(qz * ir, kVoxLimit, &vgz) ||
+      !floor_in(qx * rc, kChunkLimit, &cx) || !floor_in(qy * rc, kChunkLimit, &cy) || !floor_in(qz * rc, kChunkLimit, &cz))
+    return false;
+  const int x = vgx - cx * 8, y = vgy - cy * 8, z = vgz - cz * 8;
+  if ((unsigned)x > 7u || (unsigned)y > 7u || (unsigned)z > 7u) return false;  // (f32 rounding far from the origin)
+  const uint32_t centre = lookup_cached(v, cc, cx, cy, cz);
+  if (centre == kInvalidSlot) return false;
+  float xm, xp, ym, yp, zm, zp;
+  if (!face_sdf(v, centre, x == 0, cx - 1, cy, cz, (x + 7) & 7, y, z, &xm)) return false;
+  if (!face_sdf(v, centre, x == 7, cx + 1, cy, cz, (x + 1) & 7, y, z, &xp)) return false;
+  if (!face_sdf(v, centre, y == 0, cx, cy - 1, cz, x, (y + 7) & 7, z, &ym)) return false;
+  if (!face_sdf(v, centre, y == 7, cx, cy + 1, cz, x, (y + 1) & 7, z, &yp)) return false;
+  if (!face_sdf(v, centre, z == 0, cx, cy, cz - 1, x, y, (z + 7) & 7, &zm)) return false;
+  if (!face_sdf(v, centre, z == 7, cx, cy, cz + 1, x, y, (z + 1) & 7, &zp)) return false;
+  *gx = xp - xm;
+  *gy = yp - ym;
+  *gz = zp - zm;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_query(VolumeDev v, QueryArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const float px = a.xyz[3 * (size_t)i], py = a.xyz[3 * (size_t)i + 1], pz = a.xyz[3 * (size_t)i + 2];
+  ChunkCache cc{INT_MIN, INT_MIN, INT_MIN, kInvalidSlot};
+  uint32_t fl = 0;
+  if (a.want & 3u) {
+    uint32_t slot;
+    int id;
+    if (point_voxel(v, cc, px, py, pz, a.res, &slot, &id)) {
+      const float2 sw = v.tsdf[(size_t)slot * kChunkVoxels + id];
+      if ((a.want & 1u) && (double)sw.y > 1e-12) { a.sdf[i] = sw.x; fl |= 1u; }
+      if (a.want & 2u) { a.weight[i] = sw.y; fl |= 2u; }
+    }
+    if ((a.want & 1u) && !(fl & 1u)) a.sdf[i] = 0.f;
+    if ((a.want & 2u) && !(fl & 2u)) a.weight[i] = 0.f;
+  }
+  if (a.want & 4u) {
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    if (point_gradient(v, cc, px, py, pz, a.res, &gx, &gy, &gz)) fl |= 4u;
+    else gx = gy = gz = 0.f;
+    a.grad[3 * (size_t)i] = gx; a.grad[3 * (size_t)i + 1] = gy; a.grad[3 * (size_t)i + 2] = gz;
+  }
+  if (a.want & 24u) {
+    float s = 0.f, rgb[3] = {0.f, 0.f, 0.f};
+    bool okc = false;
+    const bool ok = (a.want & 16u) ? tri_sample<true>(v, cc, px, py, pz, 1.0f / a.res, &s, rgb, &okc)
+                                   : tri_sample<false>(v, cc, px, py, pz, 1.0f / a.res, &s);
+    if (a.want & 8u) { a.sdf_tri[i] = ok ? s : 0.f; if (ok) fl |= 8u; }
+    if (a.want & 16u) {
+      if (!okc) rgb[0] = rgb[1] = rgb[2] = 0.f;
+      else fl |= 16u;
+      a.rgb[3 * (size_t)i] = (uint8_t)rgb[0]; a.rgb[3 * (size_t)i + 1] = (uint8_t)rgb[1]; a.rgb[3 * (size_t)i + 2] = (uint8_t)rgb[2];
+    }
+  }
+  a.flags[i] = fl;
+}
+
+struct RayArgs {
+  float R[9], t[3];
+  float fx, fy, cxs, cys;  // int-truncated intrinsics, cx + 0.5 / cy + 0.5 (the integrator's projection)
+  int W, H, tiles_x;
+  float near_p, far_p;
+  int max_steps;
+  float res;
+  size_t plane;  // W * H
+  float* depth;
+  float* normal;
+  uint8_t* rgba;
+  float* vertex;
+};
+
+// one wave per 8 x 8 pixel tile (lane = 8 y + x): neighbouring rays march through the same chunks
+__global__ __launch_bounds__(64) void k_raycast(VolumeDev v, RayArgs a) {
+  const int lane = threadIdx.x;
+  const int px = (blockIdx.x % a.tiles_x) * 8 + (lane & 7), py = (blockIdx.x / a.tiles_x) * 8 + (lane >> 3);
+  if (px >= a.W || py >= a.H) return;
+  const float res = a.res, ir = 1.0f / res, cs = 8.0f * res, rc = 1.0f / (8.0f * res), eps = res * 0.015625f, gap = kRayGap * res;
+  // ray through the pixel centre, camera frame z = 1: t is the camera-frame depth
+  const float dcx = ((float)px - a.cxs) / a.fx, dcy = ((float)py - a.cys) / a.fy;
+  const float dx = (a.R[0] * dcx + a.R[1] * dcy) + a.R[2];
+  const float dy = (a.R[3] * dcx + a.R[4] * dcy) + a.R[5];
+  const float dz = (a.R[6] * dcx + a.R[7] * dcy) + a.R[8];
+  const float ox = a.t[0], oy = a.t[1], oz = a.t[2];
+  ChunkCache cc{INT_MIN, INT_MIN, INT_MIN, kInvalidSlot};
+  float t = a.near_p, pt = 0.f, ps = 0.f, thit = -1.f;
+  bool pok = false;
+  for (int step = 0; step < a.max_steps && t <= a.far_p; ++step) {  // the step cap bounds the loop whatever the volume holds
+    const float x = ox + t * dx, y = oy + t * dy, z = oz + t * dz;
+    int cx, cy, cz;
+    if (!floor_in(x * rc, kChunkLimit, &cx) || !floor_in(y * rc, kChunkLimit, &cy) || !floor_in(z * rc, kChunkLimit, &cz)) break;
+    if (lookup_cached(v, cc, cx, cy, cz) == kInvalidSlot) {
+      // absent chunk: every sample inside it is invalid (the voxel holding the point is one of its corners) -- jump to the
+      // ray's exit from the chunk's box
+      const float tx = dx > 0.f ? ((float)(cx + 1) * cs - ox) / dx : (dx < 0.f ? ((float)cx * cs - ox) / dx : INFINITY);
+      const float ty = dy > 0.f ? ((float)(cy + 1) * cs - oy) / dy : (dy < 0.f ? ((float)cy * cs - oy) / dy : INFINITY);
+      const float tz = dz > 0.f ? ((float)(cz + 1) * cs - oz) / dz : (dz < 0.f ? ((float)cz * cs - oz) / dz : INFINITY);
+      t = fmaxf(fminf(fminf(tx, ty), tz), t) + eps;
+      pok = false;
+      continue;
+    }
+    float s;
+    if (!tri_sample<false>(v, cc, x, y, z, ir, &s)) {  // (the last valid sample stays: voxels that only hole pixels saw
+      t = t + res;                                       // leave one-voxel gaps in the band right behind a surface)
+      continue;
+    }
+    pok = pok && t - pt <= gap;  // a crossing pairs two valid samples at most kRayGap voxels apart
+    if (pok && ps > 0.f && s <= 0.f) { thit = pt + (t - pt) * (ps / (ps - s)); break; }
+    if (pok && ps <= 0.f && s > 0.f) break;  // - -> +: leaving a surface from behind
+    pt = t;
+    ps = s;
+    pok = true;
+    t = t + fmaxf(res, kRayStepK * s);
+  }
+  const size_t o = (size_t)py * a.W + px;
+  const bool hit = thit >= 0.f;
+  const float hx = ox + thit * dx, hy = oy + thit * dy, hz = oz + thit * dz;
+  if (a.depth) a.depth[o] = hit ? thit : 0.f;
+  if (a.vertex) {
+    a.vertex[o] = hit ? hx : 0.f; a.vertex[a.plane + o] = hit ? hy : 0.f; a.vertex[2 * a.plane + o] = hit ? hz : 0.f;
+  }
+  if (a.normal) {
+    float n[3] = {0.f, 0.f, 0.f};
+    if (hit) {
+      // central differences of the trilinear SDF, one voxel each way (tap k: axis k >> 1, sign - / + by k & 1).  An axis
+      // with one invalid tap takes the one-sided difference against the hit itself, where the SDF is 0 (the refined
+      // crossing), doubled; an axis with none valid leaves the normal 0.
+      float sp[3] = {0.f, 0.f, 0.f}, sm[3] = {0.f, 0.f, 0.f};
+      uint32_t okm = 0;
+#pragma unroll 1
+      for (int k = 0; k < 6; ++k) {
+        const float h = (k & 1) ? res : -res;
+        float s = 0.f;
+        if (tri_sample<false>(v, cc, hx + ((k >> 1) == 0 ? h : 0.f), hy + ((k >> 1) == 1 ? h : 0.f),
+                              hz + ((k >> 1) == 2 ? h : 0.f), ir, &s)) okm |= 1u << k;
+        if ((k >> 1) == 0) { if (k & 1) sp[0] = s; else sm[0] = s; }
+        else if ((k >> 1) == 1) { if (k & 1) sp[1] = s; else sm[1] = s; }
+        else { if (k & 1) sp[2] = s; else sm[2] = s; }
+      }
+      float g[3];
+      bool ok = true;
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax) {
+        const uint32_t m = (okm >> (2 * ax)) & 3u;  // bit 0: minus tap, bit 1: plus tap
+        g[ax] = m == 3u ? sp[ax] - sm[ax] : (m == 2u ? 2.f * sp[ax] : -2.f * sm[ax]);
+        ok = ok && m != 0u;
+      }
+      if (ok) {
+        const float len = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+        if (len > 0.f) { n[0] = g[0] / len; n[1] = g[1] / len; n[2] = g[2] / len; }
+      }
+    }
+    a.normal[o] = n[0]; a.normal[a.plane + o] = n[1]; a.normal[2 * a.plane + o] = n[2];
+  }
+  if (a.rgba) {
+    float rgb[3] = {0.f, 0.f, 0.f}, s;
+    bool okc = false;
+    if (hit) tri_sample<true>(v, cc, hx, hy, hz, ir, &s, rgb, &okc);
+    uchar4 c;
+    c.x = okc ? (uint8_t)rgb[0] : 0; c.y = okc ? (uint8_t)rgb[1] : 0; c.z = okc ? (uint8_t)rgb[2] : 0;
+    c.w = hit ? 255 : 0;
+    reinterpret_cast<uchar4*>(a.rgba)[o] = c;
+  }
+}
+
+}  // namespace tf
+
+using namespace tf;
+
+namespace {
+
+int query_launch(tf_volume* v, const float* d_xyz, uint32_t n, uint32_t want, float* sdf, float* weight, float* grad3,
+                 float* sdf_tri, uint8_t* rgb3, uint32_t* flags) {
+  QueryArgs a{d_xyz, n, want, v->res, sdf, weight, grad3, sdf_tri, rgb3, flags};
+  hipLaunchKernelGGL(k_query, dim3((n + 255) / 256), dim3(256), 0, v->stream, v->dev, a);
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+
+int query_check(tf_volume* v, const float* xyz, int64_t n, uint32_t want, const float* sdf, const float* weight,
+                const float* grad3, const float* sdf_tri, const uint8_t* rgb3, const uint32_t* flags) {
+  if (!v || (n > 0 && (!xyz || !flags))) { set_error("null argument"); return TF_ERR_INVALID; }
+  if (n < 0 || n > 0x7FFFFFFFll) { set_error("point count out of range"); return TF_ERR_INVALID; }
+  if (want & ~31u) { set_error("want_mask: unknown bits (0 sdf, 1 weight, 2 grad, 3 sdf_tri, 4 rgb_tri)"); return TF_ERR_INVALID; }
+  if (((want & 1u) && !sdf) || ((want & 2u) && !weight) || ((want & 4u) && !grad3) || ((want & 8u) && !sdf_tri) ||
+      ((want & 16u) && !rgb3)) {
+    set_error("a requested output is null");
+    return TF_ERR_INVALID;
+  }
+  return TF_OK;
+}
+
+struct RayCam { float fx, fy, cx, cy; int W, H; };
+
+int ray_check(tf_volume* v, const float* pose, float near_plane, float far_plane, int32_t max_steps, RayCam* cam) {
+  if (!v || !pose) { set_error("null argument"); return TF_ERR_INVALID; }
+  if (!(near_plane >= 0.f) || !(far_plane > near_plane) || !isfinite(far_plane)) {
+    set_error("need 0 <= near < far < inf");
+    return TF_ERR_INVALID;
+  }
+  if (max_steps <= 0) { set_error("max_steps must be positive"); return TF_ERR_INVALID; }
+  for (int i = 0; i < 12; ++i)
+    if (!isfinite(pose[i])) { set_error("pose is not finite"); return TF_ERR_INVALID; }
+  if (v->ray_w > 0) *cam = {v->ray_fx, v->ray_fy, v->ray_cx, v->ray_cy, v->ray_w, v->ray_h};
+  else *cam = {v->cam.fxi, v->cam.fyi, v->cam.cxi, v->cam.cyi, v->cam.W, v->cam.H};
+  if (cam->W <= 0 || cam->H <= 0 || !(cam->fx > 0.f) || !(cam->fy > 0.f)) {
+    set_error("no camera (tf_set_camera / tf_raycast_camera)");
+    return TF_ERR_INVALID;
+  }
+  return TF_OK;
+}
+
+int ray_launch(tf_volume* v, const float* pose, float near_plane, float far_plane, int32_t max_steps, const RayCam& cam,
+               float* depth, float* normal, uint8_t* rgba, float* vertex) {
+  RayArgs a;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) a.R[3 * r + c] = pose[4 * r + c];
+    a.t[r] = pose[4 * r + 3];
+  }
+  a.fx = cam.fx; a.fy = cam.fy; a.cxs = cam.cx + 0.5f; a.cys = cam.cy + 0.5f;
+  a.W = cam.W; a.H = cam.H; a.tiles_x = (cam.W + 7) / 8;
+  a.near_p = near_plane; a.far_p = far_plane; a.max_steps = max_steps; a.res = v->res;
+  a.plane = (size_t)cam.W * cam.H;
+  a.depth = depth; a.normal = normal; a.rgba = rgba; a.vertex = vertex;
+  const unsigned tiles = (unsigned)(a.tiles_x * ((cam.H + 7) / 8));
+  hipLaunchKernelGGL(k_raycast, dim3(tiles), dim3(64), 0, v->stream, v->dev, a);
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tf_query_points_device(tf_volume* v, const float* d_xyz, int64_t n, uint32_t want_mask, float* d_sdf, float* d_weight,
+                           float* d_grad3, float* d_sdf_tri, uint8_t* d_rgb3, uint32_t* d_flags) {
+  int rc = query_check(v, d_xyz, n, want_mask, d_sdf, d_weight, d_grad3, d_sdf_tri, d_rgb3, d_flags);
+  if (rc) return rc;
+  TF_DEV(v);
+  if (n == 0) return TF_OK;
+  return query_launch(v, d_xyz, (uint32_t)n, want_mask, d_sdf, d_weight, d_grad3, d_sdf_tri, d_rgb3, d_flags);
+}
+
+int tf_query_points(tf_volume* v, const float* xyz, int64_t n, uint32_t want_mask, float* sdf, float* weight, float* grad3,
+                    float* sdf_tri, uint8_t* rgb3, uint32_t* flags) {
+  int rc = query_check(v, xyz, n, want_mask, sdf, weight, grad3, sdf_tri, rgb3, flags);
+  if (rc) return rc;
+  TF_DEV(v);
+  if (n == 0) return TF_OK;
+  // device layout: xyz | sdf | weight | grad | sdf_tri | flags | rgb, 16-byte aligned
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
+  const size_t N = (size_t)n;
+  const size_t o_xyz = take(12 * N), o_s = take(4 * N), o_w = take(4 * N), o_g = take(12 * N), o_t = take(4 * N),
+               o_f = take(4 * N), o_c = take(3 * N);
+  if ((rc = ensure_tmp(v, o)) || (rc = ensure_pinned(v, o))) return rc;
+  TF_HIP(hipStreamSynchronize(v->stream));  // the scratch buffers may still be read by an earlier call
+  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
+  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
+  memcpy(hb + o_xyz, xyz, 12 * N);
+  TF_HIP(hipMemcpyAsync(db + o_xyz, hb + o_xyz, 12 * N, hipMemcpyHostToDevice, v->stream));
+  rc = query_launch(v, reinterpret_cast<const float*>(db + o_xyz), (uint32_t)n, want_mask,
+                    reinterpret_cast<float*>(db + o_s), reinterpret_cast<float*>(db + o_w), reinterpret_cast<float*>(db + o_g),
+                    reinterpret_cast<float*>(db + o_t), db + o_c, reinterpret_cast<uint32_t*>(db + o_f));
+  if (rc) return rc;
+  TF_HIP(hipMemcpyAsync(hb + o_s, db + o_s, o - o_s, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipStreamSynchronize(v->stream));
+  if (want_mask & 1u) memcpy(sdf, hb + o_s, 4 * N);
+  if (want_mask & 2u) memcpy(weight, hb + o_w, 4 * N);
+  if (want_mask & 4u) memcpy(grad3, hb + o_g, 12 * N);
+  if (want_mask & 8u) memcpy(sdf_tri, hb + o_t, 4 * N);
+  if (want_mask & 16u) memcpy(rgb3, hb + o_c, 3 * N);
+  memcpy(flags, hb + o_f, 4 * N);
+  return TF_OK;
+}
+
+int tf_raycast_camera(tf_volume* v, float fx, float fy, float cx, float cy, int width, int height) {
+  if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
+  if (width < 0 || height < 0 || (width > 0) != (height > 0) || width > kRayMaxSide || height > kRayMaxSide) {
+    set_error("raycast camera: width and height both in 1..32768, or both 0 (= the handle's camera)");
+    return TF_ERR_INVALID;
+  }
+  const float lim = 2147483648.0f;  // 2^31: the int truncation below is defined only inside (-2^31, 2^31)
+  if (!(fabsf(fx) < lim) || !(fabsf(fy) < lim) || !(fabsf(cx) < lim) || !(fabsf(cy) < lim)) {
+    set_error("raycast camera: fx, fy, cx, cy must be finite and of magnitude below 2^31");
+    return TF_ERR_INVALID;
+  }
+  if (width > 0 && (!(fx >= 1.f) || !(fy >= 1.f))) { set_error("raycast camera: fx, fy must be >= 1"); return TF_ERR_INVALID; }
+  v->ray_fx = (float)(int)fx;  // truncated like PinholeCamera::GetFx (the integrator's convention)
+  v->ray_fy = (float)(int)fy;
+  v->ray_cx = (float)(int)cx;
+  v->ray_cy = (float)(int)cy;
+  v->ray_w = width;
+  v->ray_h = height;
+  return TF_OK;
+}
+
+int tf_raycast_device(tf_volume* v, const float pose[12], float near_plane, float far_plane, int32_t max_steps,
+                      float* d_depth, float* d_normal, uint8_t* d_rgba, float* d_vertex) {
+  RayCam cam;
+  int rc = ray_check(v, pose, near_plane, far_plane, max_steps, &cam);
+  if (rc) return rc;
+  TF_DEV(v);
+  return ray_launch(v, pose, near_plane, far_plane, max_steps, cam, d_depth, d_normal, d_rgba, d_vertex);
+}
+
+int tf_raycast(tf_volume* v, const float pose[12], float near_plane, float far_plane, int32_t max_steps, float* depth,
+               float* normal, uint8_t* rgba, float* vertex) {
+  RayCam cam;
+  int rc = ray_check(v, pose, near_plane, far_plane, max_steps, &cam);
+  if (rc) return rc;
+  TF_DEV(v);
+  const size_t P = (size_t)cam.W * cam.H;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
+  const size_t o_d = take(depth ? 4 * P : 0), o_n = take(normal ? 12 * P : 0), o_c = take(rgba ? 4 * P : 0),
+               o_v = take(vertex ? 12 * P : 0);
+  if (o == 0) return TF_OK;
+  if ((rc = ensure_tmp(v, o)) || (rc = ensure_pinned(v, o))) return rc;
+  TF_HIP(hipStreamSynchronize(v->stream));
+  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
+  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
+  rc = ray_launch(v, pose, near_plane, far_plane, max_steps, cam, depth ? reinterpret_cast<float*>(db + o_d) : nullptr,
+                  normal ? reinterpret_cast<float*>(db + o_n) : nullptr, rgba ? db + o_c : nullptr,
+                  vertex ? reinterpret_cast<float*>(db + o_v) : nullptr);
+  if (rc) return rc;
+  TF_HIP(hipMemcpyAsync(hb, db, o, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipStreamSynchronize(v->stream));
+  if (depth) memcpy(depth, hb + o_d, 4 * P);
+  if (normal) memcpy(normal, hb + o_n, 12 * P);
+  if (rgba) memcpy(rgba, hb + o_c, 4 * P);
+  if (vertex) memcpy(vertex, hb + o_v, 12 * P);
+  return TF_OK;
+}
+
+}  // extern "C"

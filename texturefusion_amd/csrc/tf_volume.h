@@ -146,6 +146,9 @@ struct tf_volume {
   // camera as given (floats) and as consumed (int-truncated)
   float fx = 525.f, fy = 525.f, cx = 319.5f, cy = 239.5f;
   tf::Cam cam;
+  // tf_raycast_camera: intrinsics (int-truncated) and image size of the raycaster; ray_w = 0 = the camera above
+  float ray_fx = 0.f, ray_fy = 0.f, ray_cx = 0.f, ray_cy = 0.f;
+  int ray_w = 0, ray_h = 0;
   tf::Integ ig;
   hipStream_t stream = nullptr;
   bool own_stream = false;

@@ -409,6 +409,55 @@ class ChunkManager {
     for (int64_t i = 0; i < n; ++i) out.emplace_back(ids[3 * i], ids[3 * i + 1], ids[3 * i + 2]);
     return out;
   }
+  // ---- point queries on the device volume (tf_query_points; read-only) ----
+  // ChunkManager::GetSDF (ChunkManager.cpp:1168-1185): false where the chunk is absent or the voxel's weight <= 1e-12
+  bool GetSDF(const Vec3& pos, double* dist) {
+    float s = 0.f;
+    uint32_t fl = 0;
+    tf_check(tf_query_points(vol, pos.v, 1, 1u, &s, nullptr, nullptr, nullptr, nullptr, &fl), "GetSDF");
+    if (!(fl & 1u)) return false;
+    *dist = s;
+    return true;
+  }
+  // ChunkManager::GetWeight (:1151-1166)
+  bool GetWeight(const Vec3& pos, double* weight) {
+    float w = 0.f;
+    uint32_t fl = 0;
+    tf_check(tf_query_points(vol, pos.v, 1, 2u, nullptr, &w, nullptr, nullptr, nullptr, &fl), "GetWeight");
+    if (!(fl & 2u)) return false;
+    *weight = w;
+    return true;
+  }
+  // ChunkManager::GetSDFAndGradient (:1043-1141, live branch): unnormalised central difference of the six face
+  // neighbours of the voxel that contains pos; false where a chunk is missing or a neighbour's sdf >= 1
+  bool GetSDFAndGradient(const Vec3& pos, Vec3& grad) {
+    uint32_t fl = 0;
+    Vec3 g;
+    tf_check(tf_query_points(vol, pos.v, 1, 4u, nullptr, nullptr, g.v, nullptr, nullptr, &fl), "GetSDFAndGradient");
+    if (!(fl & 4u)) return false;
+    grad = g;
+    return true;
+  }
+  // Batched form of the three (one ABI call for every point): sdf / weight / grad may be null (not wanted); valid[i] gets
+  // bit 0 / 1 / 2 when GetSDF / GetWeight / GetSDFAndGradient would have returned true for pos[i].
+  void GetSDFAndGradients(const Vec3List& pos, std::vector<double>* sdf, std::vector<double>* weight, Vec3List* grad,
+                          std::vector<uint32_t>* valid) {
+    const int64_t n = (int64_t)pos.size();
+    std::vector<float> xyz((size_t)n * 3), s(sdf ? (size_t)n : 0), w(weight ? (size_t)n : 0), g(grad ? (size_t)n * 3 : 0);
+    for (int64_t i = 0; i < n; ++i)
+      for (int a = 0; a < 3; ++a) xyz[(size_t)i * 3 + a] = pos[(size_t)i](a);
+    valid->assign((size_t)n, 0u);
+    const uint32_t want = (sdf ? 1u : 0u) | (weight ? 2u : 0u) | (grad ? 4u : 0u);
+    tf_check(tf_query_points(vol, xyz.data(), n, want, sdf ? s.data() : nullptr, weight ? w.data() : nullptr,
+                             grad ? g.data() : nullptr, nullptr, nullptr, valid->data()), "GetSDFAndGradients");
+    if (sdf) sdf->assign(s.begin(), s.end());
+    if (weight) weight->assign(w.begin(), w.end());
+    if (grad) {
+      grad->clear();
+      for (int64_t i = 0; i < n; ++i) grad->emplace_back(g[(size_t)i * 3], g[(size_t)i * 3 + 1], g[(size_t)i * 3 + 2]);
+    }
+  }
+
   // observation bookkeeping of Chisel::IntegrateDepthScanColor (Chisel.h:244-247)
   ChunkPtr Mirror(const ChunkID& id) {
     auto it = mirrors.find(id);
