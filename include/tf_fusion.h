@@ -398,7 +398,8 @@ TF_API int tf_get_texture_stats(tf_volume* v, tf_texture_stats* out);
 /* ---- reading the volume back (tf_ray.hip) -----------------------------------------------
  * These calls only read the volume: no voxel, hash entry, dirty mark, mesh-filter summary, neighbour-table word or
  * statistic changes.  A chunk that is not alive counts as absent (as in tf_has_chunk).  A handle with an active
- * communicator (tf_comm_init) answers from its own chunks and the ghosts it holds; there is no multi-rank raycast.
+ * communicator (tf_comm_init) answers from its own chunks and the ghosts it holds (the raycast, the point queries,
+ * GetDistanceFromSurface and RefineFrameInVoxel alike); there is no multi-rank raycast.
  *
  * Batched point queries: n world points xyz (f32[3n]); want_mask selects the outputs, flags[i] gets one bit per
  * output that is valid at point i (an invalid output is written as 0):
@@ -438,6 +439,25 @@ TF_API int tf_raycast_device(tf_volume* v, const float pose[12], float near_plan
  * = 0 goes back to the camera of tf_set_camera.  fx, fy >= 1; fx, fy, cx, cy finite and of magnitude below 2^31.  Every
  * output of tf_raycast(_device) holds the W x H of the camera active at the call. */
 TF_API int tf_raycast_camera(tf_volume* v, float fx, float fy, float cx, float cy, int width, int height);
+/* Chisel::GetDistanceFromSurface (Structure/Chisel.h:251-342) for n world points xyz (f32[3n]): the SDF averaged over
+ * the 8 voxels around p - res / 2 with trilinear weights times voxel weight (floor / ceil corners as the reference
+ * forms them, absent chunks skipped; order of operations: tf_ray.hip).  dist[i] = sum(sdf sw w) / sum(sw w) and
+ * tsdf_weight[i] = sum(w sw) / sum(sw w), both left as accumulated (0 where no corner exists) when sum(sw w) <= 0.
+ * A corner whose voxel coordinate is not finite or beyond +-(2^23 - 1) is absent.  n = 0 is a no-op. */
+TF_API int tf_distance_from_surface(tf_volume* v, const float* xyz, int64_t n, float* dist, float* tsdf_weight);
+TF_API int tf_distance_from_surface_device(tf_volume* v, const float* d_xyz, int64_t n, float* d_dist,
+                                           float* d_tsdf_weight);
+/* Chisel::RefineFrameInVoxel (Structure/Chisel.h:377-451): depth (W x H of tf_set_camera) refined in place, weight
+ * written; pixels the reference skips keep both values.  pose: camera-to-world 3x4 as in tf_integrate.
+ * A pixel with depth < 0.05 or > 3 is skipped.  Otherwise, along the ray ((j - cx) / fx, (i - cy) / fy, 1) of the
+ * int-truncated intrinsics, depth += GetDistanceFromSurface(vertex(depth)) six times; weight = the sixth call's
+ * tsdf_weight; then depth and weight are set to 0 where |sixth distance| > 5e-3, where depth is outside
+ * [near, far] of the camera, or where |depth - initial depth| > 0.1 (in that order, on the value written so far).
+ * A NaN depth stays NaN with weight 0.  tf_refine_frame_in_voxel: host images, synchronous; _device: device images,
+ * asynchronous on the handle's stream (a device depth image refined in place can go on to tf_frame_bind_device /
+ * tf_integrate_frames_device with no host round trip). */
+TF_API int tf_refine_frame_in_voxel(tf_volume* v, float* depth, float* weight, const float pose[12]);
+TF_API int tf_refine_frame_in_voxel_device(tf_volume* v, float* d_depth, float* d_weight, const float pose[12]);
 
 /* ---- meshing (the stage between the volume and the atlas) -----
  * Chisel::UpdateMeshes (Structure/Chisel.h:479-481) -> ChunkManager::RecomputeMeshes

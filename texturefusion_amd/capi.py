@@ -48,6 +48,8 @@ SYMBOLS = (
     "tf_pre_normal_map", "tf_pre_refine_depth_normal", "tf_pre_color_valid", "tf_pre_color_quality",
     "tf_pre_refine_newframe", "tf_pre_refine_keyframe", "tf_pre_frame_depth", "tf_integrate_depth_group", "tf_integrate_depth_group_host",
     "tf_query_points", "tf_query_points_device", "tf_raycast", "tf_raycast_device", "tf_raycast_camera",
+    "tf_distance_from_surface", "tf_distance_from_surface_device", "tf_refine_frame_in_voxel",
+    "tf_refine_frame_in_voxel_device",
 )
 
 # tf_query_points want_mask bits
@@ -232,6 +234,10 @@ def lib():
     L.tf_raycast.argtypes = [vp, fp, C.c_float, C.c_float, C.c_int32, fp, fp, u8p, fp]
     L.tf_raycast_device.argtypes = [vp, fp, C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp]
     L.tf_raycast_camera.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int]
+    L.tf_distance_from_surface.argtypes = [vp, fp, C.c_int64, fp, fp]
+    L.tf_distance_from_surface_device.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.tf_refine_frame_in_voxel.argtypes = [vp, fp, fp, fp]
+    L.tf_refine_frame_in_voxel_device.argtypes = [vp, vp, vp, fp]
     _lib = L
     return L
 
@@ -578,6 +584,47 @@ class Volume:
         pose = _f32(pose).reshape(12)
         self._ck(self.L.tf_raycast_device(self.h, _p(pose, C.c_float), float(near), float(far), int(max_steps),
                                           d_depth or None, d_normal or None, d_rgba or None, d_vertex or None))
+
+    def distance_from_surface(self, points):
+        """Chisel::GetDistanceFromSurface at world points [n, 3] -> (dist [n] f32, tsdf_weight [n] f32)."""
+        pts = _f32(points).reshape(-1, 3)
+        n = len(pts)
+        dist, tw = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        self._ck(self.L.tf_distance_from_surface(self.h, _p(pts, C.c_float), n, _p(dist, C.c_float), _p(tw, C.c_float)))
+        return dist, tw
+
+    def distance_from_surface_device(self, d_xyz, n, d_dist, d_tsdf_weight):
+        self._ck(self.L.tf_distance_from_surface_device(self.h, d_xyz, int(n), d_dist or None, d_tsdf_weight or None))
+
+    def refine_frame(self, depth, pose, weight=None, in_place=False):
+        """Chisel::RefineFrameInVoxel of a depth image [H, W] of the handle's camera with a camera-to-world pose ->
+        (depth, weight).  weight: the image written where a pixel is refined (skipped pixels keep its value); None = a
+        zero image.  Both are worked on in copies unless in_place (then the caller's arrays, which must be contiguous
+        f32 arrays, are refined and written)."""
+        if getattr(self, "cam", None) is None:
+            raise TFError(TF_ERR_INVALID, "no camera (set_camera)")
+        shape = (self.cam.height, self.cam.width)
+        if in_place:
+            if not (isinstance(depth, np.ndarray) and depth.dtype == np.float32 and depth.flags.c_contiguous):
+                raise TFError(TF_ERR_INVALID, "in_place needs a contiguous float32 depth array")
+            d = depth
+        else:
+            d = np.array(depth, np.float32, order="C", copy=True)
+        if weight is None:
+            w = np.zeros(shape, np.float32)
+        else:
+            w = weight if in_place else np.array(weight, np.float32, order="C", copy=True)
+        if not (isinstance(w, np.ndarray) and w.dtype == np.float32 and w.flags.c_contiguous):
+            raise TFError(TF_ERR_INVALID, "weight must be a contiguous float32 array")
+        if d.size != shape[0] * shape[1] or w.size != d.size:
+            raise TFError(TF_ERR_INVALID, "depth / weight need %dx%d pixels" % (shape[1], shape[0]))
+        pose = _f32(pose).reshape(12)
+        self._ck(self.L.tf_refine_frame_in_voxel(self.h, _p(d, C.c_float), _p(w, C.c_float), _p(pose, C.c_float)))
+        return d.reshape(shape), w.reshape(shape)
+
+    def refine_frame_device(self, d_depth, d_weight, pose):
+        pose = _f32(pose).reshape(12)
+        self._ck(self.L.tf_refine_frame_in_voxel_device(self.h, d_depth or None, d_weight or None, _p(pose, C.c_float)))
 
     # -- meshing (Chisel::UpdateMeshes / CompressMeshes, ChunkManager::allMeshes)
     def update_meshes(self):

@@ -6,8 +6,11 @@
 //              from a pose (chunk DDA over absent chunks, voxel steps where the sampler is invalid, sdf-sized steps where
 //              it is valid, linear refinement at the first + -> - crossing)
 //
-// Both kernels only READ the volume (tsdf, color, hent, nbr): no voxel, hash entry, dirty mark, summary, neighbour word
-// or statistic is written.  A chunk that is not alive counts as absent, as in tf_has_chunk.
+//   k_surface_dist  one lane per world point: Chisel::GetDistanceFromSurface (Structure/Chisel.h:251-342)
+//   k_refine_frame  one lane per pixel, an 8 x 8 pixel tile per wave64: Chisel::RefineFrameInVoxel (:377-451)
+//
+// All four kernels only READ the volume (tsdf, color, hent, nbr): no voxel, hash entry, dirty mark, summary, neighbour
+// word or statistic is written.  A chunk that is not alive counts as absent, as in tf_has_chunk.
 //
 // Trilinear sampler (bits 3 / 4 of k_query, every sample of k_raycast) -- the reference's own form is under #if 0, so its
 // arithmetic is defined here, once:
@@ -19,6 +22,21 @@
 //   SDF: valid iff all 8 corners exist with weight > 0.  Colour: per corner the mean R / count, G / count, B / count (f32
 //   divisions, ColorVoxel.h:44-55), the same lerps, then u8 = min(255, floor(x + 0.5)); valid iff all 8 counts > 0.
 // The library is built with -ffp-contract=off, so tests/raycast_ref.py restates all of this bit for bit in numpy.
+//
+// GetDistanceFromSurface, in this order, all f32 (tests/refine_ref.py restates it):
+//   r = (p - res / 2) * (1 / res) per axis (the reciprocal rounded first); d = r - floor(r);
+//   corner k = 0..7 takes ceil(r) on x where bit 2 is set, on y where bit 1 is, on z where bit 0 is, else floor(r)
+//   (an integral r repeats the corner: ceil == floor); its weight sw = (a_x * a_y) * a_z with a = d (ceil) or 1 - d;
+//   a corner coordinate that is not finite or beyond +-(2^23 - 1) is absent (the reference's float -> int is undefined
+//   there); chunk = V >> 3 (= floor((float)V / 8), exact), voxel = (V & 7) as x + 8 y + 64 z;
+//   over k in order, corners whose chunk is alive only: weight += sw * w; distance += (sdf * sw) * w; tw += w * sw;
+//   if weight > 0: distance /= weight, tw /= weight (else both stay as accumulated).
+// RefineFrameInVoxel per pixel (i, j): skipped, depth and weight untouched, if (double)depth < 0.05 or > 3;
+//   dir = ((j - cx) / fx, (i - cy) / fy, 1) with the int-truncated intrinsics as float; R * dir per row as
+//   a0 b0 + (a1 b1 + a2 b2) -- the reading of Eigen's fixed-size product the integrator kernels use;
+//   six times: vertex = (R dir) * depth + t, d = GetDistanceFromSurface(vertex), depth += d; weight = the sixth tw;
+//   then depth = weight = 0 where |d| > 5e-3 (double), where depth > far or < near (f32), where |depth - depth_init|
+//   > 0.1 (f32 difference, double compare), in that order on the value written so far.
 #include <math.h>
 #include <limits.h>
 #include <string.h>
@@ -349,6 +367,111 @@ __global__ __launch_bounds__(64) void k_raycast(VolumeDev v, RayArgs a) {
   }
 }
 
+
+// ---- Chisel::GetDistanceFromSurface / RefineFrameInVoxel (Structure/Chisel.h:251-342, 377-451) ----------------------
+
+// voxel coordinate of a corner: absent unless finite and |c| <= 2^23 - 1 (the reference converts any float to int)
+__device__ __forceinline__ bool vox_in(float c, int* out) {
+  if (!(fabsf(c) <= kVoxLimit)) return false;
+  *out = (int)c;
+  return true;
+}
+
+// GetDistanceFromSurface at world point p: the weight-averaged trilinear SDF over the 8 voxels around p - res / 2.
+// cc caches the base corner's chunk (corner 0: floor on every axis), cn the last other chunk a corner fell in.  Those go
+// through the hash, not the base chunk's neighbour-table row: a non-zero word may name a parked chunk, and a pool slot
+// carries no alive state of its own (HEntry::alive does) -- HasChunk must be false there, and weight 0 is not the same.
+__device__ __forceinline__ float surface_dist(const VolumeDev& v, ChunkCache& cc, ChunkCache& cn, float px, float py,
+                                             float pz, float half, float step, float* tsdf_weight) {
+  const float rx = (px - half) * step, ry = (py - half) * step, rz = (pz - half) * step;
+  const float flx = floorf(rx), fly = floorf(ry), flz = floorf(rz);
+  const float dX = rx - flx, dY = ry - fly, dZ = rz - flz;
+  int fx, fy, fz, cx, cy, cz;
+  const bool okfx = vox_in(flx, &fx), okfy = vox_in(fly, &fy), okfz = vox_in(flz, &fz);
+  const bool okcx = vox_in(ceilf(rx), &cx), okcy = vox_in(ceilf(ry), &cy), okcz = vox_in(ceilf(rz), &cz);
+  const uint32_t base = (okfx && okfy && okfz) ? lookup_cached(v, cc, fx >> 3, fy >> 3, fz >> 3) : kInvalidSlot;
+  float weight = 0.f, distance = 0.f, tw = 0.f;
+#pragma unroll 1
+  for (int k = 0; k < 8; ++k) {  // the reference's corner order: x from bit 2, y from bit 1, z from bit 0 (ceil where set)
+    const bool sx = (k >> 2) & 1, sy = (k >> 1) & 1, sz = k & 1;
+    if (!(sx ? okcx : okfx) || !(sy ? okcy : okfy) || !(sz ? okcz : okfz)) continue;
+    const int Vx = sx ? cx : fx, Vy = sy ? cy : fy, Vz = sz ? cz : fz;
+    const int bx = Vx >> 3, by = Vy >> 3, bz = Vz >> 3;  // = floor((float)V / 8.0f): V is exact in f32, /8 is exact
+    const uint32_t slot = (bx == (fx >> 3) && by == (fy >> 3) && bz == (fz >> 3) && okfx && okfy && okfz)
+                              ? base : lookup_cached(v, cn, bx, by, bz);
+    if (slot == kInvalidSlot) continue;
+    const float ax = sx ? dX : 1.f - dX, ay = sy ? dY : 1.f - dY, az = sz ? dZ : 1.f - dZ;
+    const float sw = (ax * ay) * az;
+    const float2 d = v.tsdf[(size_t)slot * kChunkVoxels + ((Vz & 7) * 8 + (Vy & 7)) * 8 + (Vx & 7)];
+    weight = weight + sw * d.y;
+    distance = distance + (d.x * sw) * d.y;
+    tw = tw + d.y * sw;
+  }
+  if (weight > 0.f) {
+    distance = distance / weight;
+    tw = tw / weight;
+  }
+  *tsdf_weight = tw;
+  return distance;
+}
+
+struct SurfArgs {
+  const float* xyz;
+  uint32_t n;
+  float half, step;
+  float* dist;
+  float* tw;
+};
+
+__global__ __launch_bounds__(256) void k_surface_dist(VolumeDev v, SurfArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  ChunkCache cc{INT_MIN, INT_MIN, INT_MIN, kInvalidSlot}, cn{INT_MIN, INT_MIN, INT_MIN, kInvalidSlot};
+  float tw;
+  a.dist[i] = surface_dist(v, cc, cn, a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2], a.half,
+                           a.step, &tw);
+  a.tw[i] = tw;
+}
+
+struct RefineArgs {
+  float R[9], t[3];
+  float fx, fy, cx, cy;  // int-truncated intrinsics (PinholeCamera::GetFx ... return int), used as float
+  int W, H, tiles_x;
+  float near_p, far_p;
+  float half, step;
+  float* depth;
+  float* weight;
+};
+
+// one wave per 8 x 8 pixel tile (lane = 8 y + x), as k_raycast: neighbouring pixels read the same chunks
+__global__ __launch_bounds__(64) void k_refine_frame(VolumeDev v, RefineArgs a) {
+  const int lane = threadIdx.x;
+  const int j = (blockIdx.x % a.tiles_x) * 8 + (lane & 7), i = (blockIdx.x / a.tiles_x) * 8 + (lane >> 3);
+  if (j >= a.W || i >= a.H) return;
+  const size_t o = (size_t)i * a.W + j;
+  float depth = a.depth[o];
+  if ((double)depth < 0.05 || (double)depth > 3.0) return;  // skipped: depth and weight untouched
+  const float dx = ((float)j - a.cx) / a.fx, dy = ((float)i - a.cy) / a.fy;
+  // R * (dx, dy, 1): a0 b0 + (a1 b1 + a2 b2) per row, a2 * 1 exact
+  const float rx = a.R[0] * dx + (a.R[1] * dy + a.R[2]);
+  const float ry = a.R[3] * dx + (a.R[4] * dy + a.R[5]);
+  const float rz = a.R[6] * dx + (a.R[7] * dy + a.R[8]);
+  const float depth_init = depth;
+  ChunkCache cc{INT_MIN, INT_MIN, INT_MIN, kInvalidSlot}, cn{INT_MIN, INT_MIN, INT_MIN, kInvalidSlot};
+  float d = 0.f, tw = 0.f;
+#pragma unroll 1
+  for (int r = 0; r < 6; ++r) {
+    d = surface_dist(v, cc, cn, rx * depth + a.t[0], ry * depth + a.t[1], rz * depth + a.t[2], a.half, a.step, &tw);
+    depth = depth + d;
+  }
+  // the three rejections in the reference's order, each on the value written so far (double constants compared in double)
+  if (fabs((double)d) > 5e-3) { depth = 0.f; tw = 0.f; }
+  if (depth > a.far_p || depth < a.near_p) { depth = 0.f; tw = 0.f; }
+  if (fabs((double)(depth - depth_init)) > 0.1) { depth = 0.f; tw = 0.f; }
+  a.depth[o] = depth;
+  a.weight[o] = tw;
+}
+
 }  // namespace tf
 
 using namespace tf;
@@ -410,6 +533,44 @@ int ray_launch(tf_volume* v, const float* pose, float near_plane, float far_plan
   a.depth = depth; a.normal = normal; a.rgba = rgba; a.vertex = vertex;
   const unsigned tiles = (unsigned)(a.tiles_x * ((cam.H + 7) / 8));
   hipLaunchKernelGGL(k_raycast, dim3(tiles), dim3(64), 0, v->stream, v->dev, a);
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+
+int surf_launch(tf_volume* v, const float* d_xyz, uint32_t n, float* d_dist, float* d_tw) {
+  SurfArgs a{d_xyz, n, v->res / 2.0f, 1.0f / v->res, d_dist, d_tw};
+  hipLaunchKernelGGL(k_surface_dist, dim3((n + 255) / 256), dim3(256), 0, v->stream, v->dev, a);
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+
+int surf_check(tf_volume* v, const float* xyz, int64_t n, const float* dist, const float* tw) {
+  if (!v || (n > 0 && (!xyz || !dist || !tw))) { set_error("null argument"); return TF_ERR_INVALID; }
+  if (n < 0 || n > 0x7FFFFFFFll) { set_error("point count out of range"); return TF_ERR_INVALID; }
+  return TF_OK;
+}
+
+int refine_check(tf_volume* v, const float* depth, const float* weight, const float* pose) {
+  if (!v || !depth || !weight || !pose) { set_error("null argument"); return TF_ERR_INVALID; }
+  for (int i = 0; i < 12; ++i)
+    if (!isfinite(pose[i])) { set_error("pose is not finite"); return TF_ERR_INVALID; }
+  if (v->cam.W <= 0 || v->cam.H <= 0) { set_error("no camera (tf_set_camera)"); return TF_ERR_INVALID; }
+  return TF_OK;
+}
+
+int refine_launch(tf_volume* v, const float* pose, float* d_depth, float* d_weight) {
+  RefineArgs a;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) a.R[3 * r + c] = pose[4 * r + c];
+    a.t[r] = pose[4 * r + 3];
+  }
+  a.fx = v->cam.fxi; a.fy = v->cam.fyi; a.cx = v->cam.cxi; a.cy = v->cam.cyi;
+  a.W = v->cam.W; a.H = v->cam.H; a.tiles_x = (v->cam.W + 7) / 8;
+  a.near_p = v->cam.nearP; a.far_p = v->cam.farP;
+  a.half = v->res / 2.0f; a.step = 1.0f / v->res;
+  a.depth = d_depth; a.weight = d_weight;
+  const unsigned tiles = (unsigned)(a.tiles_x * ((v->cam.H + 7) / 8));
+  hipLaunchKernelGGL(k_refine_frame, dim3(tiles), dim3(64), 0, v->stream, v->dev, a);
   TF_HIP(hipGetLastError());
   return TF_OK;
 }
@@ -516,6 +677,66 @@ int tf_raycast(tf_volume* v, const float pose[12], float near_plane, float far_p
   if (normal) memcpy(normal, hb + o_n, 12 * P);
   if (rgba) memcpy(rgba, hb + o_c, 4 * P);
   if (vertex) memcpy(vertex, hb + o_v, 12 * P);
+  return TF_OK;
+}
+
+int tf_distance_from_surface_device(tf_volume* v, const float* d_xyz, int64_t n, float* d_dist, float* d_tsdf_weight) {
+  int rc = surf_check(v, d_xyz, n, d_dist, d_tsdf_weight);
+  if (rc) return rc;
+  TF_DEV(v);
+  if (n == 0) return TF_OK;
+  return surf_launch(v, d_xyz, (uint32_t)n, d_dist, d_tsdf_weight);
+}
+
+int tf_distance_from_surface(tf_volume* v, const float* xyz, int64_t n, float* dist, float* tsdf_weight) {
+  int rc = surf_check(v, xyz, n, dist, tsdf_weight);
+  if (rc) return rc;
+  TF_DEV(v);
+  if (n == 0) return TF_OK;
+  const size_t N = (size_t)n;
+  const size_t o_d = (12 * N + 15) & ~(size_t)15, o_w = o_d + ((4 * N + 15) & ~(size_t)15), total = o_w + 4 * N;
+  if ((rc = ensure_tmp(v, total)) || (rc = ensure_pinned(v, total))) return rc;
+  TF_HIP(hipStreamSynchronize(v->stream));  // the scratch buffers may still be read by an earlier call
+  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
+  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
+  memcpy(hb, xyz, 12 * N);
+  TF_HIP(hipMemcpyAsync(db, hb, 12 * N, hipMemcpyHostToDevice, v->stream));
+  rc = surf_launch(v, reinterpret_cast<const float*>(db), (uint32_t)n, reinterpret_cast<float*>(db + o_d),
+                   reinterpret_cast<float*>(db + o_w));
+  if (rc) return rc;
+  TF_HIP(hipMemcpyAsync(hb + o_d, db + o_d, total - o_d, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipStreamSynchronize(v->stream));
+  memcpy(dist, hb + o_d, 4 * N);
+  memcpy(tsdf_weight, hb + o_w, 4 * N);
+  return TF_OK;
+}
+
+int tf_refine_frame_in_voxel_device(tf_volume* v, float* d_depth, float* d_weight, const float pose[12]) {
+  int rc = refine_check(v, d_depth, d_weight, pose);
+  if (rc) return rc;
+  TF_DEV(v);
+  return refine_launch(v, pose, d_depth, d_weight);
+}
+
+int tf_refine_frame_in_voxel(tf_volume* v, float* depth, float* weight, const float pose[12]) {
+  int rc = refine_check(v, depth, weight, pose);
+  if (rc) return rc;
+  TF_DEV(v);
+  const size_t P = (size_t)v->cam.W * v->cam.H;
+  const size_t o_w = (4 * P + 15) & ~(size_t)15, total = o_w + 4 * P;
+  if ((rc = ensure_tmp(v, total)) || (rc = ensure_pinned(v, total))) return rc;
+  TF_HIP(hipStreamSynchronize(v->stream));
+  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
+  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
+  memcpy(hb, depth, 4 * P);
+  memcpy(hb + o_w, weight, 4 * P);  // (skipped pixels keep the caller's weight)
+  TF_HIP(hipMemcpyAsync(db, hb, total, hipMemcpyHostToDevice, v->stream));
+  rc = refine_launch(v, pose, reinterpret_cast<float*>(db), reinterpret_cast<float*>(db + o_w));
+  if (rc) return rc;
+  TF_HIP(hipMemcpyAsync(hb, db, total, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipStreamSynchronize(v->stream));
+  memcpy(depth, hb, 4 * P);
+  memcpy(weight, hb + o_w, 4 * P);
   return TF_OK;
 }
 

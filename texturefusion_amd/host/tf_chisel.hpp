@@ -807,6 +807,32 @@ class Chisel {
   }
   std::vector<float> candidateCubes;  // Chisel.h:101, refreshed by PrepareIntersectChunks (:129)
 
+  // Structure/Chisel.h:251-342: weight-averaged trilinear SDF over the 8 voxels around global_vertex - res / 2 (floor /
+  // ceil corners, absent chunks skipped; tf_distance_from_surface)
+  float GetDistanceFromSurface(Vec3 global_vertex, float& tsdfWeight) {
+    float d = 0.f;
+    tf_check(tf_distance_from_surface(vol, global_vertex.v, 1, &d, &tsdfWeight), "GetDistanceFromSurface");
+    return d;
+  }
+  // Batched form (one ABI call for every point): (*dist)[i], (*tsdfWeight)[i] as GetDistanceFromSurface(pos[i], ...)
+  void GetDistancesFromSurface(const Vec3List& pos, std::vector<float>* dist, std::vector<float>* tsdfWeight) {
+    const int64_t n = (int64_t)pos.size();
+    std::vector<float> xyz((size_t)n * 3);
+    for (int64_t i = 0; i < n; ++i)
+      for (int a = 0; a < 3; ++a) xyz[(size_t)i * 3 + a] = pos[(size_t)i](a);
+    dist->assign((size_t)n, 0.f);
+    tsdfWeight->assign((size_t)n, 0.f);
+    tf_check(tf_distance_from_surface(vol, xyz.data(), n, dist->data(), tsdfWeight->data()), "GetDistancesFromSurface");
+  }
+  // Structure/Chisel.h:377-451: depthImage (W x H of depthCamera) refined in place against the volume, weight written;
+  // pixels with depth < 0.05 or > 3 keep both values.  The integrator is not read (as in the reference); the camera
+  // becomes the volume's camera (tf_set_camera), as every call of this mirror that takes one.
+  void RefineFrameInVoxel(ProjectionIntegrator& integrator, float* depthImage, float* weight,
+                          const Transform& depthExtrinsic, const PinholeCamera& depthCamera) {
+    Configure(integrator, depthCamera, false);
+    tf_check(tf_refine_frame_in_voxel(vol, depthImage, weight, depthExtrinsic.data()), "RefineFrameInVoxel");
+  }
+
   // Structure/Chisel.h:103-140.  depthImage is borrowed for the call (uploaded to HBM and kept
   // bound for the IntegrateDepthScanColor calls that follow, like the reference keeps the cv::Mat).
   void PrepareIntersectChunks(ProjectionIntegrator& integrator, float* depthImage,
