@@ -510,9 +510,8 @@ void atlas_destroy(tf_volume* v) {
   if (a.h_dirty_len) hipHostFree(a.h_dirty_len);
   a.h_dirty_len = nullptr;
   if (a.d_cand) hipFree(a.d_cand);
-  if (a.d_stage) hipFree(a.d_stage);
-  if (a.h_stage) hipHostFree(a.h_stage);
-  a.buf = nullptr; a.d_stage = nullptr; a.h_stage = nullptr; a.d_kf = nullptr; a.d_actl = nullptr;
+  scratch_free(a.stage);
+  a.buf = nullptr; a.d_kf = nullptr; a.d_actl = nullptr;
   a.d_work_ids = nullptr; a.d_work_slot = nullptr; a.d_patch_list = nullptr; a.d_patch_cnt = nullptr; a.d_cand = nullptr;
 }
 
@@ -532,22 +531,6 @@ int atlas_reset(tf_volume* v) {
   a.fused_par = 0;
   a.fused_armed = true;
   a.pend_patch.on = false;
-  return TF_OK;
-}
-
-static int atlas_stage(tf_volume* v, size_t bytes) {
-  AtlasState& a = v->atlas;
-  if (bytes > a.d_stage_bytes) {
-    TF_HIP(hipStreamSynchronize(v->stream));
-    if (a.d_stage) hipFree(a.d_stage);
-    if (a.h_stage) hipHostFree(a.h_stage);
-    a.d_stage = nullptr; a.h_stage = nullptr;
-    size_t want = 1;
-    while (want < bytes) want <<= 1;
-    TF_HIP(hipMalloc(&a.d_stage, want));
-    TF_HIP(hipHostMalloc(&a.h_stage, want, hipHostMallocDefault));
-    a.d_stage_bytes = a.h_stage_bytes = want;
-  }
   return TF_OK;
 }
 
@@ -658,21 +641,21 @@ static bool row_less(const PatchRow& a, const PatchRow& b) {
 // every mesh with a patch, ascending chunk id (host copy)
 static int list_patches(tf_volume* v, std::vector<PatchRow>* rows) {
   const size_t cap = (size_t)v->dev.max_chunks;
-  int rc = atlas_stage(v, cap * sizeof(PatchRow));
-  if (rc) return rc;
   AtlasState& a = v->atlas;
+  int rc = reserve(v, a.stage, cap * sizeof(PatchRow), cap * sizeof(PatchRow));
+  if (rc) return rc;
   TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
   hipLaunchKernelGGL(k_list_patches, dim3(1024), dim3(256), 0, v->stream, v->dev,
-                     reinterpret_cast<PatchRow*>(a.d_stage), (uint32_t)cap);
+                     reinterpret_cast<PatchRow*>(a.stage.d), (uint32_t)cap);
   TF_HIP(hipGetLastError());
   uint32_t n = 0;
   TF_HIP(hipMemcpyAsync(&n, &v->dev.vctl->n_tmp, 4, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   rows->resize(n);
   if (n) {
-    TF_HIP(hipMemcpyAsync(a.h_stage, a.d_stage, (size_t)n * sizeof(PatchRow), hipMemcpyDeviceToHost, v->stream));
+    TF_HIP(hipMemcpyAsync(a.stage.h, a.stage.d, (size_t)n * sizeof(PatchRow), hipMemcpyDeviceToHost, v->stream));
     TF_HIP(hipStreamSynchronize(v->stream));
-    memcpy(rows->data(), a.h_stage, (size_t)n * sizeof(PatchRow));
+    memcpy(rows->data(), a.stage.h, (size_t)n * sizeof(PatchRow));
     std::sort(rows->begin(), rows->end(), row_less);
   }
   return TF_OK;
@@ -683,14 +666,11 @@ static int list_patches(tf_volume* v, std::vector<PatchRow>* rows) {
 static int upload_work(tf_volume* v, const int32_t* ids, const int* kfslot, int64_t n) {
   AtlasState& a = v->atlas;
   if (n > (int64_t)v->dev.max_chunks) { set_error("chunk list longer than tf_config.max_chunks"); return TF_ERR_CAPACITY; }
-  int rc = atlas_stage(v, (size_t)n * 16 + 16);
+  Stage sg;
+  int rc = stage_begin(v, a.stage, (size_t)n * 16 + 16, (size_t)n * 16 + 16, &sg);
   if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  int32_t* h = reinterpret_cast<int32_t*>(a.h_stage);
-  for (int64_t i = 0; i < n; ++i) {
-    h[4 * i] = ids[3 * i]; h[4 * i + 1] = ids[3 * i + 1]; h[4 * i + 2] = ids[3 * i + 2];
-    h[4 * i + 3] = kfslot ? kfslot[i] : 0;
-  }
+  int32_t* h = sg.hp<int32_t>(0);
+  pack_ids(ids, n, h, kfslot);
   h[4 * n] = (int32_t)n;
   TF_HIP(hipMemcpyAsync(a.d_work_ids, h, (size_t)n * 16, hipMemcpyHostToDevice, v->stream));
   TF_HIP(hipMemcpyAsync(&a.d_actl->set[0].n_work, h + 4 * n, 4, hipMemcpyHostToDevice, v->stream));
@@ -725,10 +705,10 @@ int tf_keyframe_cache(tf_volume* v, int32_t kf_id, const uint8_t* rgb, const flo
     TF_HIP(hipMalloc((void**)&ks.depth, npix * 4));
     ks.owned = true;
   }
-  rc = atlas_stage(v, npix * 7);
+  Stage sg;
+  rc = stage_begin(v, a.stage, npix * 7, npix * 7, &sg);
   if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hs = reinterpret_cast<uint8_t*>(a.h_stage);
+  uint8_t* hs = sg.h;
   memcpy(hs, rgb, npix * 3);
   memcpy(hs + npix * 3, depth, npix * 4);
   TF_HIP(hipMemcpyAsync(ks.rgb, hs, npix * 3, hipMemcpyHostToDevice, v->stream));
@@ -823,32 +803,25 @@ int tf_meshes_upload(tf_volume* v, const int32_t* ids, int64_t n, const int64_t*
   if (n <= 0) return TF_OK;
   const int64_t nv = vert_offsets[n], ni = index_offsets[n];
   if (ni > 0 && !indices) { set_error("null index argument"); return TF_ERR_INVALID; }
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
-  const size_t o_ids = take((size_t)n * 16), o_vo = take((size_t)(n + 1) * 8), o_io = take((size_t)(n + 1) * 8);
-  const size_t o_v = take((size_t)nv * 12), o_n = take((size_t)nv * 12), o_c = take((size_t)nv * 12), o_i = take((size_t)ni * 4);
-  int rc = atlas_stage(v, o);
+  Layout L;
+  const size_t o_ids = L.take((size_t)n * 16), o_vo = L.take((size_t)(n + 1) * 8), o_io = L.take((size_t)(n + 1) * 8);
+  const size_t o_v = L.take((size_t)nv * 12), o_n = L.take((size_t)nv * 12), o_c = L.take((size_t)nv * 12),
+               o_i = L.take((size_t)ni * 4);
+  Stage sg;
+  int rc = stage_begin(v, v->atlas.stage, L.size, L.size, &sg);
   if (rc) return rc;
-  AtlasState& a = v->atlas;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hs = reinterpret_cast<uint8_t*>(a.h_stage);
-  uint8_t* ds = reinterpret_cast<uint8_t*>(a.d_stage);
-  int32_t* hid = reinterpret_cast<int32_t*>(hs + o_ids);
-  for (int64_t i = 0; i < n; ++i) {
-    hid[4 * i] = ids[3 * i]; hid[4 * i + 1] = ids[3 * i + 1]; hid[4 * i + 2] = ids[3 * i + 2]; hid[4 * i + 3] = 0;
-  }
+  uint8_t* hs = sg.h;
+  pack_ids(ids, n, sg.hp<int32_t>(o_ids));
   memcpy(hs + o_vo, vert_offsets, (size_t)(n + 1) * 8);
   memcpy(hs + o_io, index_offsets, (size_t)(n + 1) * 8);
   memcpy(hs + o_v, verts, (size_t)nv * 12);
   memcpy(hs + o_n, normals, (size_t)nv * 12);
   memcpy(hs + o_c, colors, (size_t)nv * 12);
   if (ni) memcpy(hs + o_i, indices, (size_t)ni * 4);
-  TF_HIP(hipMemcpyAsync(ds, hs, o, hipMemcpyHostToDevice, v->stream));
-  hipLaunchKernelGGL(k_mesh_scatter, dim3((unsigned)n), dim3(256), 0, v->stream, v->dev,
-                     reinterpret_cast<const int4*>(ds + o_ids), (uint32_t)n, reinterpret_cast<const long long*>(ds + o_vo),
-                     reinterpret_cast<const long long*>(ds + o_io), reinterpret_cast<const float*>(ds + o_v),
-                     reinterpret_cast<const float*>(ds + o_n), reinterpret_cast<const float*>(ds + o_c),
-                     reinterpret_cast<const uint32_t*>(ds + o_i), ++v->mesh_epoch);
+  TF_HIP(hipMemcpyAsync(sg.d, hs, L.size, hipMemcpyHostToDevice, v->stream));
+  hipLaunchKernelGGL(k_mesh_scatter, dim3((unsigned)n), dim3(256), 0, v->stream, v->dev, sg.dp<const int4>(o_ids), (uint32_t)n,
+                     sg.dp<const long long>(o_vo), sg.dp<const long long>(o_io), sg.dp<const float>(o_v),
+                     sg.dp<const float>(o_n), sg.dp<const float>(o_c), sg.dp<const uint32_t>(o_i), ++v->mesh_epoch);
   TF_HIP(hipGetLastError());
   v->host_list_n = -1;
   return tf_sync(v);
@@ -876,7 +849,7 @@ int tf_generate_patches(tf_volume* v, const int32_t* ids, int64_t n, const int32
   }
   // (room behind the work list for the counters coming back: pinned, so that the copy does not go through the runtime's staging)
   const size_t o_ctl = ((size_t)n * 16 + 16 + 63) & ~(size_t)63;
-  int rc = atlas_stage(v, o_ctl + sizeof(AtlasCtl));
+  int rc = reserve(v, a.stage, o_ctl + sizeof(AtlasCtl), o_ctl + sizeof(AtlasCtl));
   if (rc) return rc;
   rc = upload_work(v, ids, kfs.data(), n);
   if (rc) return rc;
@@ -887,7 +860,7 @@ int tf_generate_patches(tf_volume* v, const int32_t* ids, int64_t n, const int32
   hipLaunchKernelGGL((k_patch<true, false, false>), dim3(1024), dim3(256), 0, v->stream, v->dev, v->cam, 0, KfDev{});
   prof_end(v);
   TF_HIP(hipGetLastError());
-  AtlasCtl* hc = reinterpret_cast<AtlasCtl*>(reinterpret_cast<uint8_t*>(a.h_stage) + o_ctl);
+  AtlasCtl* hc = reinterpret_cast<AtlasCtl*>(reinterpret_cast<uint8_t*>(a.stage.h) + o_ctl);
   TF_HIP(hipMemcpyAsync(hc, a.d_actl, sizeof(AtlasCtl), hipMemcpyDeviceToHost, v->stream));
   rc = sync_status(v, nullptr);
   const AtlasCtl c = *hc;
@@ -945,11 +918,11 @@ int tf_compensate_color(tf_volume* v, int64_t* out_n_clusters) {
   const size_t o_mean = o_red + ncl * 48;                                             // [ncl][6]
   const size_t o_xf = o_mean + ncl * 24;                                              // [ncl][16]
   const size_t total = o_xf + ncl * 64;
-  rc = atlas_stage(v, total);
+  Stage sg;
+  rc = stage_begin(v, a.stage, total, total, &sg);
   if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hs = reinterpret_cast<uint8_t*>(a.h_stage);
-  uint8_t* ds = reinterpret_cast<uint8_t*>(a.d_stage);
+  uint8_t* hs = sg.h;
+  uint8_t* ds = sg.d;
   CcPatch* hp = reinterpret_cast<CcPatch*>(hs + o_pt);
   for (int64_t p = 0; p < np; ++p) {
     hp[p].slot = rows[(size_t)p].slot; hp[p].nv = rows[(size_t)p].nv;
@@ -1023,18 +996,15 @@ static int draw_common(tf_volume* v, float* d_vertices, uint32_t* d_indices, flo
   if (out_ni) *out_ni = (int64_t)iout;
   if ((int64_t)vout > cap_v || (int64_t)iout > cap_i) { set_error("vertex / index buffer too small"); return TF_ERR_CAPACITY; }
   if (dp.empty()) return TF_OK;
-  AtlasState& a = v->atlas;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
-  const size_t o_pt = take(sizeof(DrawPatch) * dp.size());
-  const size_t o_v = d_vertices ? 0 : take((size_t)vout * 48), o_i = d_indices ? 0 : take((size_t)iout * 4);
-  rc = atlas_stage(v, o);
-  if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hs = reinterpret_cast<uint8_t*>(a.h_stage);
-  uint8_t* ds = reinterpret_cast<uint8_t*>(a.d_stage);
-  memcpy(hs + o_pt, dp.data(), sizeof(DrawPatch) * dp.size());
-  TF_HIP(hipMemcpyAsync(ds + o_pt, hs + o_pt, sizeof(DrawPatch) * dp.size(), hipMemcpyHostToDevice, v->stream));
+  Layout L;
+  const size_t o_pt = L.take(sizeof(DrawPatch) * dp.size());
+  const size_t o_v = d_vertices ? 0 : L.take((size_t)vout * 48), o_i = d_indices ? 0 : L.take((size_t)iout * 4);
+  Stage sg;
+  if ((rc = stage_begin(v, v->atlas.stage, L.size, L.size, &sg)) ||
+      (rc = stage_in(v, sg, o_pt, dp.data(), sizeof(DrawPatch) * dp.size())))
+    return rc;
+  uint8_t* hs = sg.h;
+  uint8_t* ds = sg.d;
   float* dv = d_vertices ? d_vertices : reinterpret_cast<float*>(ds + o_v);
   uint32_t* di = d_indices ? d_indices : reinterpret_cast<uint32_t*>(ds + o_i);
   hipLaunchKernelGGL(k_draw, dim3((unsigned)dp.size()), dim3(256), 0, v->stream, v->dev,
@@ -1069,22 +1039,18 @@ int tf_patches_download(tf_volume* v, const int32_t* ids, int64_t n, const int64
   TF_DEV(v);
   if (n <= 0) return TF_OK;
   const int64_t nv = vert_offsets ? vert_offsets[n] : 0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
-  const size_t o_ids = take((size_t)n * 16), o_vo = take((size_t)(n + 1) * 8);
-  const size_t o_in_end = o;
-  const size_t o_ph = take(sizeof(PatchHost) * (size_t)n), o_tc = take((size_t)nv * 8), o_tcol = take((size_t)nv * 12),
-               o_labs = take((size_t)nv * 12);
-  int rc = atlas_stage(v, o);
+  Layout L;
+  const size_t o_ids = L.take((size_t)n * 16), o_vo = L.take((size_t)(n + 1) * 8);
+  const size_t o_in_end = L.size;
+  const size_t o_ph = L.take(sizeof(PatchHost) * (size_t)n), o_tc = L.take((size_t)nv * 8), o_tcol = L.take((size_t)nv * 12),
+               o_labs = L.take((size_t)nv * 12);
+  const size_t o = L.size;
+  Stage sg;
+  int rc = stage_begin(v, v->atlas.stage, o, o, &sg);
   if (rc) return rc;
-  AtlasState& a = v->atlas;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hs = reinterpret_cast<uint8_t*>(a.h_stage);
-  uint8_t* ds = reinterpret_cast<uint8_t*>(a.d_stage);
-  int32_t* hid = reinterpret_cast<int32_t*>(hs + o_ids);
-  for (int64_t i = 0; i < n; ++i) {
-    hid[4 * i] = ids[3 * i]; hid[4 * i + 1] = ids[3 * i + 1]; hid[4 * i + 2] = ids[3 * i + 2]; hid[4 * i + 3] = 0;
-  }
+  uint8_t* hs = sg.h;
+  uint8_t* ds = sg.d;
+  pack_ids(ids, n, sg.hp<int32_t>(o_ids));
   if (vert_offsets) memcpy(hs + o_vo, vert_offsets, (size_t)(n + 1) * 8);
   TF_HIP(hipMemcpyAsync(ds, hs, o_in_end, hipMemcpyHostToDevice, v->stream));
   if (o > o_tc) TF_HIP(hipMemsetAsync(ds + o_tc, 0, o - o_tc, v->stream));
@@ -1099,11 +1065,7 @@ int tf_patches_download(tf_volume* v, const int32_t* ids, int64_t n, const int64
   TF_HIP(hipStreamSynchronize(v->stream));
   const PatchHost* ph = reinterpret_cast<const PatchHost*>(hs + o_ph);
   for (int64_t i = 0; i < n; ++i) {
-    if (!ph[i].found) {
-      set_error("chunk (" + std::to_string(ids[3 * i]) + "," + std::to_string(ids[3 * i + 1]) + "," +
-                std::to_string(ids[3 * i + 2]) + ") has no mesh");
-      return TF_ERR_MISSING_CHUNK;
-    }
+    if (!ph[i].found) return missing_chunk_error(ids, i, "has no mesh");
     if (texloc) texloc[i] = ph[i].texloc;
     if (frameid) frameid[i] = ph[i].frameid;
     if (bbox) memcpy(bbox + 4 * i, ph[i].bbox, 16);

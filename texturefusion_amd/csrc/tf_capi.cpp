@@ -60,32 +60,74 @@ static int dev_alloc(tf_volume* v, T** p, size_t count) {
   return TF_OK;
 }
 
-int ensure_tmp(tf_volume* v, size_t bytes) {
-  if (bytes <= v->d_tmp_bytes) return TF_OK;
-  if (v->d_tmp) {
-    TF_HIP(hipStreamSynchronize(v->stream));
-    TF_HIP(hipFree(v->d_tmp));
-    v->d_tmp = nullptr;
-    v->d_tmp_bytes = 0;
+int reserve(tf_volume* v, Scratch& s, size_t dev_bytes, size_t host_bytes) {
+  const bool grow_d = dev_bytes > s.d_bytes, grow_h = host_bytes > s.h_bytes;
+  if ((grow_d && s.d) || (grow_h && s.h)) TF_HIP(hipStreamSynchronize(v->stream));
+  if (grow_d) {
+    if (s.d) TF_HIP(hipFree(s.d));
+    s.d = nullptr; s.d_bytes = 0;
+    TF_HIP(hipMalloc(&s.d, pow2_at_least(dev_bytes)));
+    s.d_bytes = pow2_at_least(dev_bytes);
   }
-  size_t want = pow2_at_least(bytes);
-  TF_HIP(hipMalloc(&v->d_tmp, want));
-  v->d_tmp_bytes = want;
+  if (grow_h) {
+    if (s.h) TF_HIP(hipHostFree(s.h));
+    s.h = nullptr; s.h_bytes = 0;
+    TF_HIP(hipHostMalloc(&s.h, pow2_at_least(host_bytes), hipHostMallocDefault));
+    s.h_bytes = pow2_at_least(host_bytes);
+  }
   return TF_OK;
 }
 
-int ensure_pinned(tf_volume* v, size_t bytes) {
-  if (bytes <= v->h_pinned_bytes) return TF_OK;
-  if (v->h_pinned) {
-    TF_HIP(hipStreamSynchronize(v->stream));
-    TF_HIP(hipHostFree(v->h_pinned));
-    v->h_pinned = nullptr;
-    v->h_pinned_bytes = 0;
-  }
-  size_t want = pow2_at_least(bytes);
-  TF_HIP(hipHostMalloc(&v->h_pinned, want, hipHostMallocDefault));
-  v->h_pinned_bytes = want;
+void scratch_free(Scratch& s) {
+  if (s.d) hipFree(s.d);
+  if (s.h) hipHostFree(s.h);
+  s = Scratch{};
+}
+
+int stage_begin(tf_volume* v, Scratch& s, size_t dev_bytes, size_t host_bytes, Stage* st) {
+  int rc = reserve(v, s, dev_bytes, host_bytes);
+  if (rc) return rc;
+  TF_HIP(hipStreamSynchronize(v->stream));
+  st->h = reinterpret_cast<uint8_t*>(s.h);
+  st->d = reinterpret_cast<uint8_t*>(s.d);
   return TF_OK;
+}
+
+int stage_in(tf_volume* v, const Stage& st, size_t at, const void* src, size_t bytes) {
+  memcpy(st.h + at, src, bytes);
+  TF_HIP(hipMemcpyAsync(st.d + at, st.h + at, bytes, hipMemcpyHostToDevice, v->stream));
+  return TF_OK;
+}
+
+int stage_ids(tf_volume* v, Scratch& s, size_t bytes, const int32_t* ids, int64_t n, Stage* st) {
+  int rc = stage_begin(v, s, bytes, bytes, st);
+  if (rc) return rc;
+  pack_ids(ids, n, st->hp<int32_t>(0));
+  TF_HIP(hipMemcpyAsync(st->d, st->h, (size_t)n * 16, hipMemcpyHostToDevice, v->stream));
+  return TF_OK;
+}
+
+int download_ids(tf_volume* v, const Scratch& s, int64_t m, int32_t* out) {
+  TF_HIP(hipMemcpyAsync(s.h, s.d, (size_t)m * 16, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipStreamSynchronize(v->stream));
+  unpack_ids(reinterpret_cast<const int32_t*>(s.h), m, out);
+  return TF_OK;
+}
+
+void pack_ids(const int32_t* ids, int64_t n, int32_t* out4, const int* w) {
+  for (int64_t i = 0; i < n; ++i) {
+    out4[4 * i] = ids[3 * i]; out4[4 * i + 1] = ids[3 * i + 1]; out4[4 * i + 2] = ids[3 * i + 2]; out4[4 * i + 3] = w ? w[i] : 0;
+  }
+}
+
+void unpack_ids(const int32_t* in4, int64_t n, int32_t* ids) {
+  for (int64_t i = 0; i < n; ++i) { ids[3 * i] = in4[4 * i]; ids[3 * i + 1] = in4[4 * i + 1]; ids[3 * i + 2] = in4[4 * i + 2]; }
+}
+
+int missing_chunk_error(const int32_t* ids, int64_t i, const char* what) {
+  set_error("chunk (" + std::to_string(ids[3 * i]) + "," + std::to_string(ids[3 * i + 1]) + "," + std::to_string(ids[3 * i + 2]) +
+            ") " + what);
+  return TF_ERR_MISSING_CHUNK;
 }
 
 void prof_begin(tf_volume* v, int kind, hipStream_t s) {
@@ -287,16 +329,11 @@ static int sync_list(tf_volume* v, const int32_t* ids, int64_t n) {
   }
   if (v->host_list_n == n && (n == 0 || memcmp(v->host_list.data(), ids, (size_t)n * 12) == 0))
     return TF_OK;
-  int rc = ensure_pinned(v, (size_t)n * 16 + 16);
+  Stage sg;
+  int rc = stage_begin(v, v->scratch, 0, (size_t)n * 16 + 16, &sg);
   if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));  // pinned staging may still be in flight
-  int32_t* st = reinterpret_cast<int32_t*>(v->h_pinned);
-  for (int64_t i = 0; i < n; ++i) {
-    st[4 * i] = ids[3 * i];
-    st[4 * i + 1] = ids[3 * i + 1];
-    st[4 * i + 2] = ids[3 * i + 2];
-    st[4 * i + 3] = 0;
-  }
+  int32_t* st = sg.hp<int32_t>(0);
+  pack_ids(ids, n, st);
   uint32_t* cnt = reinterpret_cast<uint32_t*>(st + 4 * n);
   cnt[0] = cnt[1] = (uint32_t)n;  // n_list and n_front: a plain list
   if (n) TF_HIP(hipMemcpyAsync(v->dev.sel.list_id, st, (size_t)n * 16, hipMemcpyHostToDevice, v->stream));
@@ -488,9 +525,8 @@ int tf_volume_destroy(tf_volume* v) {
   if (v->d_depth) hipFree(v->d_depth);
   if (v->d_rgba) hipFree(v->d_rgba);
   if (v->d_quality) hipFree(v->d_quality);
-  if (v->d_tmp) hipFree(v->d_tmp);
+  scratch_free(v->scratch);
   if (v->d_group) hipFree(v->d_group);
-  if (v->h_pinned) hipHostFree(v->h_pinned);
   if (v->h_ctl) hipHostFree(v->h_ctl);
   if (v->h_progress) hipHostFree(v->h_progress);
   v->h_progress = nullptr;
@@ -574,6 +610,13 @@ int tf_set_weight(tf_volume* v, float w) {
   return TF_OK;
 }
 
+// tf_frame_upload's staging in the host half of the pool: depth | rgba | quality, 4 bytes per pixel each.  tf_frame_upload_rgb
+// stages its RGB (3 B) and colour flag (1 B) per pixel in the rgba block, next to tf_frame_upload's depth and quality copies.
+struct FrameStaging {
+  size_t depth, rgba, quality, size;
+  explicit FrameStaging(size_t npix) : depth(0), rgba(4 * npix), quality(8 * npix), size(12 * npix) {}
+};
+
 int tf_frame_upload(tf_volume* v, const float* depth, const uint8_t* rgba, const float* quality) {
   if (!v || !depth) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
@@ -589,19 +632,19 @@ int tf_frame_upload(tf_volume* v, const float* depth, const uint8_t* rgba, const
     TF_HIP(hipMalloc((void**)&v->d_quality, npix * 4));
     v->img_pixels = npix;
   }
-  int rc = ensure_pinned(v, npix * 12);
+  const FrameStaging fs(npix);
+  Stage sg;
+  int rc = stage_begin(v, v->scratch, 0, fs.size, &sg);
   if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));  // previous use of the staging buffer
-  uint8_t* st = reinterpret_cast<uint8_t*>(v->h_pinned);
-  memcpy(st, depth, npix * 4);
-  TF_HIP(hipMemcpyAsync(v->d_depth, st, npix * 4, hipMemcpyHostToDevice, v->stream));
+  memcpy(sg.h + fs.depth, depth, npix * 4);
+  TF_HIP(hipMemcpyAsync(v->d_depth, sg.h + fs.depth, npix * 4, hipMemcpyHostToDevice, v->stream));
   if (rgba) {
-    memcpy(st + npix * 4, rgba, npix * 4);
-    TF_HIP(hipMemcpyAsync(v->d_rgba, st + npix * 4, npix * 4, hipMemcpyHostToDevice, v->stream));
+    memcpy(sg.h + fs.rgba, rgba, npix * 4);
+    TF_HIP(hipMemcpyAsync(v->d_rgba, sg.h + fs.rgba, npix * 4, hipMemcpyHostToDevice, v->stream));
   }
   if (quality) {
-    memcpy(st + npix * 8, quality, npix * 4);
-    TF_HIP(hipMemcpyAsync(v->d_quality, st + npix * 8, npix * 4, hipMemcpyHostToDevice, v->stream));
+    memcpy(sg.h + fs.quality, quality, npix * 4);
+    TF_HIP(hipMemcpyAsync(v->d_quality, sg.h + fs.quality, npix * 4, hipMemcpyHostToDevice, v->stream));
   }
   v->frame.depth = v->d_depth;
   v->frame.rgba = rgba ? reinterpret_cast<const uchar4*>(v->d_rgba) : nullptr;
@@ -620,13 +663,15 @@ int tf_frame_upload_rgb(tf_volume* v, const float* depth, const uint8_t* rgb, co
   int rc = tf_frame_upload(v, depth, nullptr, quality);
   if (rc) return rc;
   const size_t npix = (size_t)v->cam.W * v->cam.H;
-  rc = ensure_tmp(v, npix * 4);
+  const FrameStaging fs(npix);
+  rc = reserve(v, v->scratch, npix * 4, 0);
   if (rc) return rc;
-  uint8_t* st = reinterpret_cast<uint8_t*>(v->h_pinned);  // [0, 12 npix): tf_frame_upload used depth (0..4) and quality (8..12)
-  memcpy(st + npix * 4, rgb, npix * 3);
-  memcpy(st + npix * 7, color_valid, npix);
-  uint8_t* dt = reinterpret_cast<uint8_t*>(v->d_tmp);
-  TF_HIP(hipMemcpyAsync(dt, st + npix * 4, npix * 4, hipMemcpyHostToDevice, v->stream));
+  // (tf_frame_upload synchronised before its copies, none of which reads the rgba block)
+  uint8_t* st = reinterpret_cast<uint8_t*>(v->scratch.h) + fs.rgba;
+  memcpy(st, rgb, npix * 3);
+  memcpy(st + npix * 3, color_valid, npix);
+  uint8_t* dt = reinterpret_cast<uint8_t*>(v->scratch.d);
+  TF_HIP(hipMemcpyAsync(dt, st, npix * 4, hipMemcpyHostToDevice, v->stream));
   launch_pack_rgba(dt, dt + npix * 3, reinterpret_cast<uchar4*>(v->d_rgba), (uint32_t)npix, v->stream);
   TF_HIP(hipGetLastError());
   v->frame.rgba = reinterpret_cast<const uchar4*>(v->d_rgba);
@@ -659,12 +704,12 @@ int tf_prepare(tf_volume* v, const float pose[12], int32_t* out_ids, uint8_t* ou
   v->host_list_n = -1;
   // the list goes to host-visible memory behind the kernels that make it: one synchronisation per call
   const size_t cap_list = (size_t)v->dev.max_list;
-  int rc = ensure_pinned(v, cap_list * 17);
+  int rc = reserve(v, v->scratch, 0, cap_list * 17);
   if (rc) return rc;
   rc = launch_prepare(v, P, true);
   if (rc) return rc;
   TF_HIP(hipGetLastError());
-  int32_t* st = reinterpret_cast<int32_t*>(v->h_pinned);
+  int32_t* st = reinterpret_cast<int32_t*>(v->scratch.h);
   uint8_t* stn = reinterpret_cast<uint8_t*>(st + 4 * cap_list);
   launch_export_list(v->dev, reinterpret_cast<int4*>(st), stn, (uint32_t)cap_list, v->stream);
   TF_HIP(hipGetLastError());
@@ -676,11 +721,7 @@ int tf_prepare(tf_volume* v, const float pose[12], int32_t* out_ids, uint8_t* ou
   if (cnt > cap) { set_error("output capacity too small for the visible list"); return TF_ERR_CAPACITY; }
   if (cnt == 0) { v->host_list.clear(); v->host_list_n = 0; v->host_flags_n = -2; return TF_OK; }
   v->host_list.resize((size_t)cnt * 3);
-  for (int64_t i = 0; i < cnt; ++i) {
-    v->host_list[3 * i] = st[4 * i];
-    v->host_list[3 * i + 1] = st[4 * i + 1];
-    v->host_list[3 * i + 2] = st[4 * i + 2];
-  }
+  unpack_ids(st, cnt, v->host_list.data());
   v->host_list_n = cnt;
   v->host_needs.assign((size_t)cnt, 0);  // (the selection leaves needsUpdate clear)
   v->host_new.assign(stn, stn + cnt);
@@ -702,10 +743,10 @@ int tf_integrate(tf_volume* v, const float pose[12], const int32_t* ids, int64_t
   int rc = sync_list(v, ids, n);
   if (rc) return rc;
   const size_t npad = (size_t)((n + 3) & ~(int64_t)3);
-  rc = ensure_pinned(v, 2 * npad + (size_t)n * 4 + 16);
+  Stage sg;
+  rc = stage_begin(v, v->scratch, 0, 2 * npad + (size_t)n * 4 + 16, &sg);
   if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* st = reinterpret_cast<uint8_t*>(v->h_pinned);           // flags going in
+  uint8_t* st = sg.h;                                               // flags going in
   uint8_t* st_out = st + npad;                                      // flags coming back (written by the device)
   float* stq = reinterpret_cast<float*>(st + 2 * npad);
   uint32_t* stat = reinterpret_cast<uint32_t*>(st + 2 * npad + (size_t)n * 4);
@@ -751,22 +792,20 @@ int tf_integrate_depth_group(tf_volume* v, int32_t n_frames, const float* const*
   int rc = sync_list(v, ids, n);
   if (rc) return rc;
   const size_t npad = (size_t)((n + 3) & ~(int64_t)3);
-  rc = ensure_pinned(v, npad);
-  if (rc) return rc;
   // scratch: per frame the list records (2 x float4 per entry, stride 4) and the centroid table
   const size_t pre_bytes = (size_t)n_frames * 4 * v->dev.max_list * sizeof(float4);
   const size_t cen_bytes = (size_t)n_frames * 3 * kChunkVoxels * sizeof(float);
-  rc = ensure_tmp(v, pre_bytes + cen_bytes);
+  Stage sg;
+  rc = stage_begin(v, v->scratch, pre_bytes + cen_bytes, npad, &sg);
   if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* st = reinterpret_cast<uint8_t*>(v->h_pinned);
+  uint8_t* st = sg.h;
   if (!flags_current(v, v->host_needs, inout_needs_update, n)) {
     memcpy(st, inout_needs_update, (size_t)n);
     TF_HIP(hipMemcpyAsync(v->dev.sel.list_needs, st, (size_t)n, hipMemcpyHostToDevice, v->stream));
   }
   v->host_flags_n = -2;
-  float4* pre = reinterpret_cast<float4*>(v->d_tmp);
-  float* cen = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(v->d_tmp) + pre_bytes);
+  float4* pre = sg.dp<float4>(0);
+  float* cen = sg.dp<float>(pre_bytes);
   prof_begin(v, TF_PROF_INTEGRATE);
   launch_integrate_group(v->dev, n_frames, d_depth, poses12, pre, cen, v->cam, v->ig, v->res, integrate_flag, v->stream);
   prof_end(v);
@@ -810,10 +849,10 @@ int tf_finalize(tf_volume* v, const int32_t* ids, const uint8_t* needs_update, c
   if (n > 0) {
     int rc = sync_list(v, ids, n);
     if (rc) return rc;
-    rc = ensure_pinned(v, (size_t)n * 2);
+    Stage sg;
+    rc = stage_begin(v, v->scratch, 0, (size_t)n * 2, &sg);
     if (rc) return rc;
-    TF_HIP(hipStreamSynchronize(v->stream));
-    uint8_t* st = reinterpret_cast<uint8_t*>(v->h_pinned);
+    uint8_t* st = sg.h;
     if (!flags_current(v, v->host_needs, needs_update, n)) {
       memcpy(st, needs_update, (size_t)n);
       TF_HIP(hipMemcpyAsync(v->dev.sel.list_needs, st, (size_t)n, hipMemcpyHostToDevice, v->stream));
@@ -1699,19 +1738,19 @@ int tf_get_texture_stats(tf_volume* v, tf_texture_stats* out) {
   if (!v || !out) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   memset(out, 0, sizeof(*out));
-  int rc = ensure_tmp(v, 64);
+  int rc = reserve(v, v->scratch, 64, 0);
   if (rc) return rc;
-  TF_HIP(hipMemsetAsync(v->d_tmp, 0, 48, v->stream));
+  TF_HIP(hipMemsetAsync(v->scratch.d, 0, 48, v->stream));
   {
     const int par = v->atlas.fused_par ^ 1;
     VolumeDev d = v->dev;
     d.work_ids = v->atlas.d_work_ids + (size_t)par * d.max_chunks;
     d.work_slot = v->atlas.d_work_slot + (size_t)par * d.max_chunks;
-    launch_texture_stats(d, par, reinterpret_cast<unsigned long long*>(v->d_tmp), v->stream);
+    launch_texture_stats(d, par, reinterpret_cast<unsigned long long*>(v->scratch.d), v->stream);
   }
   TF_HIP(hipGetLastError());
   unsigned long long r[6];
-  TF_HIP(hipMemcpyAsync(r, v->d_tmp, 48, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(r, v->scratch.d, 48, hipMemcpyDeviceToHost, v->stream));
   AtlasCtl c;
   TF_HIP(hipMemcpyAsync(&c, v->dev.actl, sizeof(c), hipMemcpyDeviceToHost, v->stream));
   uint32_t mc[kMeshCntWords];  // the counters of the last mesher launch: rows per shard | {exact tests, rows with a surface cell} per shard
@@ -1740,38 +1779,24 @@ int tf_chunks_download(tf_volume* v, const int32_t* ids, int64_t n, float* sdf, 
   if (!v || (n > 0 && !ids)) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   if (n <= 0) return TF_OK;
-  const size_t per = 16 + 2048 + 2048 + 4096 + 4;  // id, sdf, weight, colour, found
-  int rc = ensure_tmp(v, (size_t)n * per);
+  const size_t N = (size_t)n;
+  Layout L;  // ids | sdf | weight | colour | found
+  L.take(N * 16);
+  const size_t o_sdf = L.take(N * 2048), o_w = L.take(N * 2048), o_c = L.take(N * 4096), o_f = L.take(N * 4);
+  Stage sg;
+  int rc = stage_ids(v, v->scratch, L.size, ids, n, &sg);
   if (rc) return rc;
-  rc = ensure_pinned(v, (size_t)n * per);
-  if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  int32_t* hid = reinterpret_cast<int32_t*>(hb);
-  for (int64_t i = 0; i < n; ++i) {
-    hid[4 * i] = ids[3 * i]; hid[4 * i + 1] = ids[3 * i + 1]; hid[4 * i + 2] = ids[3 * i + 2]; hid[4 * i + 3] = 0;
-  }
-  const size_t o_sdf = (size_t)n * 16, o_w = o_sdf + (size_t)n * 2048, o_c = o_w + (size_t)n * 2048,
-               o_f = o_c + (size_t)n * 4096;
-  TF_HIP(hipMemcpyAsync(db, hb, (size_t)n * 16, hipMemcpyHostToDevice, v->stream));
-  launch_gather_chunks(v->dev, reinterpret_cast<const int4*>(db), (uint32_t)n,
-                       reinterpret_cast<float*>(db + o_sdf), reinterpret_cast<float*>(db + o_w),
-                       reinterpret_cast<uint16_t*>(db + o_c), reinterpret_cast<uint32_t*>(db + o_f),
-                       v->stream);
+  launch_gather_chunks(v->dev, sg.dp<const int4>(0), (uint32_t)n, sg.dp<float>(o_sdf), sg.dp<float>(o_w),
+                       sg.dp<uint16_t>(o_c), sg.dp<uint32_t>(o_f), v->stream);
   TF_HIP(hipGetLastError());
-  TF_HIP(hipMemcpyAsync(hb + o_sdf, db + o_sdf, (size_t)n * (per - 16), hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(sg.h + o_sdf, sg.d + o_sdf, L.size - o_sdf, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  const uint32_t* found = reinterpret_cast<const uint32_t*>(hb + o_f);
+  const uint32_t* found = sg.hp<const uint32_t>(o_f);
   for (int64_t i = 0; i < n; ++i)
-    if (!found[i]) {
-      set_error("chunk (" + std::to_string(ids[3 * i]) + "," + std::to_string(ids[3 * i + 1]) + "," +
-                std::to_string(ids[3 * i + 2]) + ") does not exist");
-      return TF_ERR_MISSING_CHUNK;
-    }
-  if (sdf) memcpy(sdf, hb + o_sdf, (size_t)n * 2048);
-  if (weight) memcpy(weight, hb + o_w, (size_t)n * 2048);
-  if (color) memcpy(color, hb + o_c, (size_t)n * 4096);
+    if (!found[i]) return missing_chunk_error(ids, i, "does not exist");
+  if (sdf) memcpy(sdf, sg.h + o_sdf, N * 2048);
+  if (weight) memcpy(weight, sg.h + o_w, N * 2048);
+  if (color) memcpy(color, sg.h + o_c, N * 4096);
   return TF_OK;
 }
 
@@ -1794,20 +1819,15 @@ int tf_chunk_upload(tf_volume* v, const int32_t id[3], const float* sdf, const f
   if (!v || !id) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   if ((sdf == nullptr) != (weight == nullptr)) { set_error("sdf and weight must be given together"); return TF_ERR_INVALID; }
-  int rc = ensure_tmp(v, 8192);
+  Stage sg;
+  int rc = stage_begin(v, v->scratch, 8192, 8192, &sg);
   if (rc) return rc;
-  rc = ensure_pinned(v, 8192);
-  if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  if (sdf) { memcpy(hb, sdf, 2048); memcpy(hb + 2048, weight, 2048); }
-  if (color) memcpy(hb + 4096, color, 4096);
-  TF_HIP(hipMemcpyAsync(db, hb, 8192, hipMemcpyHostToDevice, v->stream));
+  if (sdf) { memcpy(sg.h, sdf, 2048); memcpy(sg.h + 2048, weight, 2048); }
+  if (color) memcpy(sg.h + 4096, color, 4096);
+  TF_HIP(hipMemcpyAsync(sg.d, sg.h, 8192, hipMemcpyHostToDevice, v->stream));
   int4 i4 = make_int4(id[0], id[1], id[2], 0);
-  launch_scatter_chunk(v->dev, i4, sdf ? reinterpret_cast<float*>(db) : nullptr,
-                       sdf ? reinterpret_cast<float*>(db + 2048) : nullptr,
-                       color ? reinterpret_cast<uint16_t*>(db + 4096) : nullptr, v->stream);
+  launch_scatter_chunk(v->dev, i4, sdf ? sg.dp<float>(0) : nullptr, sdf ? sg.dp<float>(2048) : nullptr,
+                       color ? sg.dp<uint16_t>(4096) : nullptr, v->stream);
   TF_HIP(hipGetLastError());
   v->host_list_n = -1;
   CtlSnap ctl;
@@ -1818,27 +1838,19 @@ static int list_common(tf_volume* v, bool dirty, int32_t* out_ids, int64_t cap, 
   if (!v || !n) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   if (cap < 0) cap = 0;
-  int rc = ensure_tmp(v, (size_t)cap * 16 + 16);
+  int rc = reserve(v, v->scratch, (size_t)cap * 16 + 16, (size_t)cap * 16 + 16);
   if (rc) return rc;
-  rc = ensure_pinned(v, (size_t)cap * 16 + 16);
-  if (rc) return rc;
+  int4* list = reinterpret_cast<int4*>(v->scratch.d);
   TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
-  if (dirty) launch_list_dirty(v->dev, reinterpret_cast<int4*>(v->d_tmp), (uint32_t)cap, v->clear_floor, v->stream);
-  else launch_list_chunks(v->dev, reinterpret_cast<int4*>(v->d_tmp), (uint32_t)cap, v->stream);
+  if (dirty) launch_list_dirty(v->dev, list, (uint32_t)cap, v->clear_floor, v->stream);
+  else launch_list_chunks(v->dev, list, (uint32_t)cap, v->stream);
   TF_HIP(hipGetLastError());
   CtlSnap ctl;
   rc = fetch_ctl(v, &ctl);
   if (rc) return rc;
   *n = ctl.vc.n_tmp;
   const int64_t m = std::min<int64_t>(cap, ctl.vc.n_tmp);
-  if (m > 0 && out_ids) {
-    TF_HIP(hipMemcpyAsync(v->h_pinned, v->d_tmp, (size_t)m * 16, hipMemcpyDeviceToHost, v->stream));
-    TF_HIP(hipStreamSynchronize(v->stream));
-    const int32_t* st = reinterpret_cast<const int32_t*>(v->h_pinned);
-    for (int64_t i = 0; i < m; ++i) {
-      out_ids[3 * i] = st[4 * i]; out_ids[3 * i + 1] = st[4 * i + 1]; out_ids[3 * i + 2] = st[4 * i + 2];
-    }
-  }
+  if (m > 0 && out_ids && (rc = download_ids(v, v->scratch, m, out_ids))) return rc;
   if (ctl.vc.n_tmp > cap && out_ids) { set_error("output capacity too small"); return TF_ERR_CAPACITY; }
   return TF_OK;
 }
@@ -1863,13 +1875,13 @@ int tf_get_stats(tf_volume* v, tf_stats* out) {
   if (!v || !out) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   memset(out, 0, sizeof(*out));
-  int rc = ensure_tmp(v, 64);
+  int rc = reserve(v, v->scratch, 64, 0);
   if (rc) return rc;
-  TF_HIP(hipMemsetAsync(v->d_tmp, 0, 32, v->stream));
-  launch_rowstats(v->dev, reinterpret_cast<unsigned long long*>(v->d_tmp), v->stream);
+  TF_HIP(hipMemsetAsync(v->scratch.d, 0, 32, v->stream));
+  launch_rowstats(v->dev, reinterpret_cast<unsigned long long*>(v->scratch.d), v->stream);
   TF_HIP(hipGetLastError());
   unsigned long long r3[4];
-  TF_HIP(hipMemcpyAsync(r3, v->d_tmp, 32, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(r3, v->scratch.d, 32, hipMemcpyDeviceToHost, v->stream));
   CtlSnap ctl;
   rc = fetch_ctl(v, &ctl);
   if (rc) return rc;
@@ -1911,20 +1923,6 @@ int tf_profile_get(tf_volume* v, tf_profile* out, int reset) {
 }
 
 // ---- Chunk::observations on the device + the exports TexMap consumes -----------------
-// ids (host, int32[3n]) -> int4 list at the start of d_tmp (which must hold 16 n + extra bytes); returns after the copy
-// has been enqueued
-static int ids_to_device(tf_volume* v, const int32_t* ids, int64_t n, size_t extra) {
-  int rc = ensure_tmp(v, (size_t)n * 16 + extra + 64);
-  if (rc) return rc;
-  rc = ensure_pinned(v, (size_t)n * 16 + extra + 64);
-  if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));  // previous use of the staging buffer
-  int32_t* h = reinterpret_cast<int32_t*>(v->h_pinned);
-  for (int64_t i = 0; i < n; ++i) { h[4 * i] = ids[3 * i]; h[4 * i + 1] = ids[3 * i + 1]; h[4 * i + 2] = ids[3 * i + 2]; h[4 * i + 3] = 0; }
-  TF_HIP(hipMemcpyAsync(v->d_tmp, h, (size_t)n * 16, hipMemcpyHostToDevice, v->stream));
-  return TF_OK;
-}
-
 int tf_observations_record(tf_volume* v, int32_t keyframe_id) {
   if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
   TF_DEV(v);
@@ -1938,9 +1936,10 @@ int tf_observations_retract(tf_volume* v, int32_t keyframe_id, const int32_t* id
   if (!v || (n > 0 && !ids)) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   if (n <= 0) return TF_OK;
-  int rc = ids_to_device(v, ids, n, 0);
+  Stage sg;
+  int rc = stage_ids(v, v->scratch, (size_t)n * 16, ids, n, &sg);
   if (rc) return rc;
-  launch_obs_retract(v->dev, keyframe_id, reinterpret_cast<const int4*>(v->d_tmp), (uint32_t)n, v->stream);
+  launch_obs_retract(v->dev, keyframe_id, sg.dp<const int4>(0), (uint32_t)n, v->stream);
   TF_HIP(hipGetLastError());
   return TF_OK;
 }
@@ -1950,22 +1949,20 @@ int tf_export_datacost(tf_volume* v, const int32_t* ids, int64_t n, int32_t fram
   if (!v || (n > 0 && (!ids || !out)) || n_frames < 0 || (n_frames > 0 && !frames_to_update)) { set_error("invalid argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   if (n <= 0) return TF_OK;
-  const size_t cols = (size_t)1 + (size_t)n_frames;
-  const size_t o_fr = (size_t)n * 16, o_out = (o_fr + (size_t)n_frames * 4 + 15) & ~(size_t)15;
-  int rc = ids_to_device(v, ids, n, (size_t)n_frames * 4 + 16 + (size_t)n * cols * 4);
+  const size_t out_bytes = (size_t)n * (1 + (size_t)n_frames) * 4;
+  Layout L;
+  L.take((size_t)n * 16);
+  const size_t o_fr = L.take((size_t)n_frames * 4), o_out = L.take(out_bytes);
+  Stage sg;
+  int rc = stage_ids(v, v->scratch, L.size, ids, n, &sg);
   if (rc) return rc;
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
-  if (n_frames) {
-    memcpy(hb + o_fr, frames_to_update, (size_t)n_frames * 4);
-    TF_HIP(hipMemcpyAsync(db + o_fr, hb + o_fr, (size_t)n_frames * 4, hipMemcpyHostToDevice, v->stream));
-  }
-  launch_obs_export(v->dev, reinterpret_cast<const int4*>(db), (uint32_t)n, frame_index, reinterpret_cast<const int32_t*>(db + o_fr),
-                    n_frames, reinterpret_cast<float*>(db + o_out), v->stream);
+  if (n_frames && (rc = stage_in(v, sg, o_fr, frames_to_update, (size_t)n_frames * 4))) return rc;
+  launch_obs_export(v->dev, sg.dp<const int4>(0), (uint32_t)n, frame_index, sg.dp<const int32_t>(o_fr), n_frames,
+                    sg.dp<float>(o_out), v->stream);
   TF_HIP(hipGetLastError());
-  TF_HIP(hipMemcpyAsync(hb + o_out, db + o_out, (size_t)n * cols * 4, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(sg.h + o_out, sg.d + o_out, out_bytes, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  memcpy(out, hb + o_out, (size_t)n * cols * 4);
+  memcpy(out, sg.h + o_out, out_bytes);
   return TF_OK;
 }
 
@@ -1974,14 +1971,17 @@ int tf_export_adjacency(tf_volume* v, const int32_t* ids, int64_t n, int32_t* ou
   TF_DEV(v);
   *n_edges = 0;
   if (n <= 0) return TF_OK;
-  const size_t o_cnt = (size_t)n * 16, o_out = o_cnt + 16;
-  int rc = ids_to_device(v, ids, n, 16 + (size_t)cap_edges * 16);
+  Layout L;
+  L.take((size_t)n * 16);
+  const size_t o_cnt = L.take(16), o_out = L.take((size_t)cap_edges * 16);
+  Stage sg;
+  int rc = stage_ids(v, v->scratch, L.size, ids, n, &sg);
   if (rc) return rc;
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
+  uint8_t* db = sg.d;
+  uint8_t* hb = sg.h;
   TF_HIP(hipMemsetAsync(db + o_cnt, 0, 16, v->stream));
-  launch_adj_export(v->dev, reinterpret_cast<const int4*>(db), (uint32_t)n, reinterpret_cast<int4*>(db + o_out), (uint32_t)cap_edges,
-                    reinterpret_cast<uint32_t*>(db + o_cnt), v->stream);
+  launch_adj_export(v->dev, sg.dp<const int4>(0), (uint32_t)n, sg.dp<int4>(o_out), (uint32_t)cap_edges, sg.dp<uint32_t>(o_cnt),
+                    v->stream);
   TF_HIP(hipGetLastError());
   uint32_t cnt = 0;
   TF_HIP(hipMemcpyAsync(&cnt, db + o_cnt, 4, hipMemcpyDeviceToHost, v->stream));

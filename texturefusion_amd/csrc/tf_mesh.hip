@@ -1325,30 +1325,17 @@ __global__ __launch_bounds__(256) void k_mesh_gather(VolumeDev v, const int4* __
       for (int a = 0; a < 3; ++a) indices[i0 + 3 * i + a] = tri_plane(v, m.block, a)[i];
 }
 
-// ids (host, int32[3n]) -> device int4 list in d_tmp at byte offset `at`
-static int upload_ids(tf_volume* v, const int32_t* ids, int64_t n, size_t at) {
-  int rc = ensure_pinned(v, (size_t)n * 16 + 16);
-  if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  int32_t* hid = reinterpret_cast<int32_t*>(v->h_pinned);
-  for (int64_t i = 0; i < n; ++i) {
-    hid[4 * i] = ids[3 * i]; hid[4 * i + 1] = ids[3 * i + 1]; hid[4 * i + 2] = ids[3 * i + 2]; hid[4 * i + 3] = 0;
-  }
-  TF_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(v->d_tmp) + at, hid, (size_t)n * 16, hipMemcpyHostToDevice, v->stream));
-  return TF_OK;
-}
-
-// the dirty set (Chisel::meshesToUpdate) as a device list in d_tmp: [0,16) count word, ids from byte 16.  Enqueued only:
+// the dirty set (Chisel::meshesToUpdate) as a device list in scratch.d: [0,16) count word, ids from byte 16.  Enqueued only:
 // the count is also in VolCtl::n_tmp, which sync_status reads behind whatever the caller launches on the list.
-static int dirty_list_enqueue(tf_volume* v) {
+int dirty_list_enqueue(tf_volume* v) {
   const size_t cap = (size_t)v->dev.max_chunks;
-  int rc = ensure_tmp(v, cap * 16 + 16);
+  int rc = reserve(v, v->scratch, cap * 16 + 16, 0);
   if (rc) return rc;
+  uint8_t* db = reinterpret_cast<uint8_t*>(v->scratch.d);
   TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
-  launch_list_dirty(v->dev, reinterpret_cast<int4*>(reinterpret_cast<uint8_t*>(v->d_tmp) + 16), (uint32_t)cap,
-                    v->clear_floor, v->stream);
+  launch_list_dirty(v->dev, reinterpret_cast<int4*>(db + 16), (uint32_t)cap, v->clear_floor, v->stream);
   TF_HIP(hipGetLastError());
-  TF_HIP(hipMemcpyAsync(v->d_tmp, &v->dev.vctl->n_tmp, 4, hipMemcpyDeviceToDevice, v->stream));
+  TF_HIP(hipMemcpyAsync(db, &v->dev.vctl->n_tmp, 4, hipMemcpyDeviceToDevice, v->stream));
   return TF_OK;
 }
 
@@ -1416,7 +1403,7 @@ int tf_update_meshes(tf_volume* v, int64_t* n_meshed) {
   if (rc) return rc;
   // (the launches take the list's length from the device word: no synchronisation between the scan and the mesher; an
   // empty list costs two empty launches)
-  const uint8_t* db = reinterpret_cast<const uint8_t*>(v->d_tmp);
+  const uint8_t* db = reinterpret_cast<const uint8_t*>(v->scratch.d);
   prof_begin(v, TF_PROF_MESH);
   (void)nbr_next_seq(v);
   launch_mesh(v->dev, v->mesh_par, reinterpret_cast<const int4*>(db + 16), reinterpret_cast<const uint32_t*>(db), v->dev.max_chunks,
@@ -1430,7 +1417,7 @@ int tf_update_meshes(tf_volume* v, int64_t* n_meshed) {
   if (n_meshed) *n_meshed = n;
   if (rc) return rc;
   v->dirty_list_n = n;
-  v->dirty_list_seq = v->call_seq;  // d_tmp holds the list: a tf_compress_meshes right behind this call takes it from there
+  v->dirty_list_seq = v->call_seq;  // scratch.d holds the list: a tf_compress_meshes right behind this call takes it from there
   return TF_OK;
 }
 
@@ -1438,12 +1425,10 @@ int tf_list_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n) {
   if (!v || !n) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   if (cap < 0) cap = 0;
-  int rc = ensure_tmp(v, (size_t)cap * 16 + 16);
-  if (rc) return rc;
-  rc = ensure_pinned(v, (size_t)cap * 16 + 16);
+  int rc = reserve(v, v->scratch, (size_t)cap * 16 + 16, (size_t)cap * 16 + 16);
   if (rc) return rc;
   TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
-  hipLaunchKernelGGL(k_list_meshes, dim3(1024), dim3(256), 0, v->stream, v->dev, reinterpret_cast<int4*>(v->d_tmp),
+  hipLaunchKernelGGL(k_list_meshes, dim3(1024), dim3(256), 0, v->stream, v->dev, reinterpret_cast<int4*>(v->scratch.d),
                      (uint32_t)cap);
   TF_HIP(hipGetLastError());
   uint32_t cnt = 0;
@@ -1451,14 +1436,7 @@ int tf_list_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n) {
   TF_HIP(hipStreamSynchronize(v->stream));
   *n = cnt;
   const int64_t m = cnt < (uint64_t)cap ? cnt : cap;
-  if (m > 0 && out_ids) {
-    TF_HIP(hipMemcpyAsync(v->h_pinned, v->d_tmp, (size_t)m * 16, hipMemcpyDeviceToHost, v->stream));
-    TF_HIP(hipStreamSynchronize(v->stream));
-    const int32_t* st = reinterpret_cast<const int32_t*>(v->h_pinned);
-    for (int64_t i = 0; i < m; ++i) {
-      out_ids[3 * i] = st[4 * i]; out_ids[3 * i + 1] = st[4 * i + 1]; out_ids[3 * i + 2] = st[4 * i + 2];
-    }
-  }
+  if (m > 0 && out_ids && (rc = download_ids(v, v->scratch, m, out_ids))) return rc;
   if ((int64_t)cnt > cap && out_ids) { set_error("output capacity too small"); return TF_ERR_CAPACITY; }
   return TF_OK;
 }
@@ -1468,23 +1446,18 @@ int tf_mesh_counts(tf_volume* v, const int32_t* ids, int64_t n, int32_t* n_verti
   if (!v || (n > 0 && !ids)) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   if (n <= 0) return TF_OK;
-  int rc = ensure_tmp(v, (size_t)n * 32);
+  const size_t o_r = (size_t)n * 16;  // ids | counts
+  Stage sg;
+  int rc = stage_ids(v, v->scratch, 2 * o_r, ids, n, &sg);
   if (rc) return rc;
-  rc = upload_ids(v, ids, n, 0);
-  if (rc) return rc;
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  hipLaunchKernelGGL(k_mesh_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, v->dev,
-                     reinterpret_cast<const int4*>(db), (uint32_t)n, reinterpret_cast<int4*>(db + (size_t)n * 16));
+  hipLaunchKernelGGL(k_mesh_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, v->dev, sg.dp<const int4>(0),
+                     (uint32_t)n, sg.dp<int4>(o_r));
   TF_HIP(hipGetLastError());
-  TF_HIP(hipMemcpyAsync(v->h_pinned, db + (size_t)n * 16, (size_t)n * 16, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(sg.h + o_r, sg.d + o_r, o_r, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  const int32_t* r = reinterpret_cast<const int32_t*>(v->h_pinned);
+  const int32_t* r = sg.hp<const int32_t>(o_r);
   for (int64_t i = 0; i < n; ++i) {
-    if (!r[4 * i + 3]) {
-      set_error("chunk (" + std::to_string(ids[3 * i]) + "," + std::to_string(ids[3 * i + 1]) + "," +
-                std::to_string(ids[3 * i + 2]) + ") has no mesh");
-      return TF_ERR_MISSING_CHUNK;  // allMeshes.at() would throw
-    }
+    if (!r[4 * i + 3]) return missing_chunk_error(ids, i, "has no mesh");  // allMeshes.at() would throw
     if (n_vertices) n_vertices[i] = r[4 * i];
     if (n_indices) n_indices[i] = r[4 * i + 1];
     if (adj)
@@ -1501,38 +1474,28 @@ int tf_meshes_download(tf_volume* v, const int32_t* ids, int64_t n, const int64_
   TF_DEV(v);
   if (n <= 0) return TF_OK;
   const int64_t nv = vert_offsets[n], ni = index_offsets[n];
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
-  const size_t o_ids = take((size_t)n * 16), o_vo = take((size_t)(n + 1) * 8), o_io = take((size_t)(n + 1) * 8);
-  const size_t o_in_end = o;
-  const size_t o_v = take((size_t)nv * 12), o_n = take((size_t)nv * 12), o_c = take((size_t)nv * 12), o_i = take((size_t)ni * 4);
-  const size_t total = o;
-  int rc = ensure_tmp(v, total);
+  Layout L;
+  const size_t o_ids = L.take((size_t)n * 16), o_vo = L.take((size_t)(n + 1) * 8), o_io = L.take((size_t)(n + 1) * 8);
+  const size_t o_in_end = L.size;
+  const size_t o_v = L.take((size_t)nv * 12), o_n = L.take((size_t)nv * 12), o_c = L.take((size_t)nv * 12),
+               o_i = L.take((size_t)ni * 4);
+  Stage sg;
+  int rc = stage_begin(v, v->scratch, L.size, L.size, &sg);
   if (rc) return rc;
-  rc = ensure_pinned(v, total);
-  if (rc) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  int32_t* hid = reinterpret_cast<int32_t*>(hb + o_ids);
-  for (int64_t i = 0; i < n; ++i) {
-    hid[4 * i] = ids[3 * i]; hid[4 * i + 1] = ids[3 * i + 1]; hid[4 * i + 2] = ids[3 * i + 2]; hid[4 * i + 3] = 0;
-  }
-  memcpy(hb + o_vo, vert_offsets, (size_t)(n + 1) * 8);
-  memcpy(hb + o_io, index_offsets, (size_t)(n + 1) * 8);
-  TF_HIP(hipMemcpyAsync(db, hb, o_in_end, hipMemcpyHostToDevice, v->stream));
-  hipLaunchKernelGGL(k_mesh_gather, dim3((unsigned)n), dim3(256), 0, v->stream, v->dev,
-                     reinterpret_cast<const int4*>(db + o_ids), (uint32_t)n,
-                     reinterpret_cast<const long long*>(db + o_vo), reinterpret_cast<const long long*>(db + o_io),
-                     reinterpret_cast<float*>(db + o_v), reinterpret_cast<float*>(db + o_n),
-                     reinterpret_cast<float*>(db + o_c), reinterpret_cast<uint32_t*>(db + o_i));
+  pack_ids(ids, n, sg.hp<int32_t>(o_ids));
+  memcpy(sg.h + o_vo, vert_offsets, (size_t)(n + 1) * 8);
+  memcpy(sg.h + o_io, index_offsets, (size_t)(n + 1) * 8);
+  TF_HIP(hipMemcpyAsync(sg.d, sg.h, o_in_end, hipMemcpyHostToDevice, v->stream));
+  hipLaunchKernelGGL(k_mesh_gather, dim3((unsigned)n), dim3(256), 0, v->stream, v->dev, sg.dp<const int4>(o_ids), (uint32_t)n,
+                     sg.dp<const long long>(o_vo), sg.dp<const long long>(o_io), sg.dp<float>(o_v), sg.dp<float>(o_n),
+                     sg.dp<float>(o_c), sg.dp<uint32_t>(o_i));
   TF_HIP(hipGetLastError());
-  TF_HIP(hipMemcpyAsync(hb + o_v, db + o_v, total - o_v, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(sg.h + o_v, sg.d + o_v, L.size - o_v, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  if (verts) memcpy(verts, hb + o_v, (size_t)nv * 12);
-  if (normals) memcpy(normals, hb + o_n, (size_t)nv * 12);
-  if (colors) memcpy(colors, hb + o_c, (size_t)nv * 12);
-  if (indices) memcpy(indices, hb + o_i, (size_t)ni * 4);
+  if (verts) memcpy(verts, sg.h + o_v, (size_t)nv * 12);
+  if (normals) memcpy(normals, sg.h + o_n, (size_t)nv * 12);
+  if (colors) memcpy(colors, sg.h + o_c, (size_t)nv * 12);
+  if (indices) memcpy(indices, sg.h + o_i, (size_t)ni * 4);
   return TF_OK;
 }
 
@@ -1559,7 +1522,7 @@ int tf_compress_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n_o
   int rc = TF_OK;
   // (the call before this one was tf_update_meshes -- or a keyframe unit without its texture stage, which leaves the list in the
   // same place but, being asynchronous, not its length on the host: dirty_list_n == ~0u)
-  const bool have_list = v->dirty_list_seq + 1 == v->call_seq && v->d_tmp;
+  const bool have_list = v->dirty_list_seq + 1 == v->call_seq && v->scratch.d;
   if (!have_list) { rc = dirty_list_enqueue(v); if (rc) return rc; }
   const bool known_n = have_list && v->dirty_list_n != ~0u;
   const uint32_t cap_list = v->dev.max_chunks;
@@ -1567,9 +1530,9 @@ int tf_compress_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n_o
   const size_t cap_host = known_n ? (size_t)v->dirty_list_n : (size_t)cap_list;
   int64_t m = 0;
   if (cap_host) {
-    rc = ensure_pinned(v, cap_host * 16);
+    rc = reserve(v, v->scratch, 0, cap_host * 16);  // (the host half only: the device half holds the list)
     if (rc) return rc;
-    uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
+    uint8_t* db = reinterpret_cast<uint8_t*>(v->scratch.d);
     const int4* list = reinterpret_cast<const int4*>(db + 16);
     const uint32_t* cnt = reinterpret_cast<const uint32_t*>(db);
     launch_compress(v->dev, list, cnt, cap_list, true, v->stream);
@@ -1577,14 +1540,14 @@ int tf_compress_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n_o
     TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
     const uint32_t grid = known_n ? (v->dirty_list_n + 255u) / 256u : 1024u;
     hipLaunchKernelGGL(k_dirty_with_mesh, dim3(grid ? grid : 1u), dim3(256), 0, v->stream, v->dev, list, cnt, cap_list,
-                       reinterpret_cast<int4*>(v->h_pinned), (uint32_t)cap_host);
+                       reinterpret_cast<int4*>(v->scratch.h), (uint32_t)cap_host);
     TF_HIP(hipGetLastError());
     uint32_t got = 0;
     rc = sync_status(v, &got);
     if (rc) return rc;
     m = got < cap_host ? got : (int64_t)cap_host;
     // ascending id (std::set<ChunkID> order): one 64-bit key per id, x most significant
-    const int32_t* hid = reinterpret_cast<const int32_t*>(v->h_pinned);
+    const int32_t* hid = reinterpret_cast<const int32_t*>(v->scratch.h);
     std::vector<unsigned long long> keys((size_t)m);
     bool wide = false;
     for (int64_t i = 0; i < m; ++i) {
@@ -1625,13 +1588,13 @@ int tf_compress_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n_o
 int tf_check_summaries(tf_volume* v, int64_t* n_chunks, int64_t* n_missing, int64_t* n_stale) {
   if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
   TF_DEV(v);
-  int rc = ensure_tmp(v, 32);
+  int rc = reserve(v, v->scratch, 32, 0);
   if (rc) return rc;
-  TF_HIP(hipMemsetAsync(v->d_tmp, 0, 32, v->stream));
-  hipLaunchKernelGGL(k_check_summaries, dim3(1024), dim3(256), 0, v->stream, v->dev, reinterpret_cast<unsigned long long*>(v->d_tmp));
+  TF_HIP(hipMemsetAsync(v->scratch.d, 0, 32, v->stream));
+  hipLaunchKernelGGL(k_check_summaries, dim3(1024), dim3(256), 0, v->stream, v->dev, reinterpret_cast<unsigned long long*>(v->scratch.d));
   TF_HIP(hipGetLastError());
   unsigned long long h[3] = {0, 0, 0};
-  TF_HIP(hipMemcpyAsync(h, v->d_tmp, sizeof(h), hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(h, v->scratch.d, sizeof(h), hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   if (n_chunks) *n_chunks = (int64_t)h[0];
   if (n_missing) *n_missing = (int64_t)h[1];
@@ -1642,13 +1605,13 @@ int tf_check_summaries(tf_volume* v, int64_t* n_chunks, int64_t* n_missing, int6
 int tf_check_neighbours(tf_volume* v, int64_t out6[6]) {
   if (!v || !out6) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
-  int rc = ensure_tmp(v, 64);
+  int rc = reserve(v, v->scratch, 64, 0);
   if (rc) return rc;
-  TF_HIP(hipMemsetAsync(v->d_tmp, 0, 64, v->stream));
-  hipLaunchKernelGGL(k_check_neighbours, dim3(1024), dim3(256), 0, v->stream, v->dev, reinterpret_cast<unsigned long long*>(v->d_tmp));
+  TF_HIP(hipMemsetAsync(v->scratch.d, 0, 64, v->stream));
+  hipLaunchKernelGGL(k_check_neighbours, dim3(1024), dim3(256), 0, v->stream, v->dev, reinterpret_cast<unsigned long long*>(v->scratch.d));
   TF_HIP(hipGetLastError());
   unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-  TF_HIP(hipMemcpyAsync(h, v->d_tmp, sizeof(h), hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(h, v->scratch.d, sizeof(h), hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   for (int k = 0; k < 6; ++k) out6[k] = (int64_t)h[k];
   return TF_OK;

@@ -374,9 +374,9 @@ int tf_pre_refine_keyframe(tf_volume* v, float* d_depth_ref, float* d_weight_ref
   const PreCam c = pre_cam(v);
   const size_t np = (size_t)c.W * c.H, bytes = np * sizeof(float);
   // scratch: original depth | estimate A | estimate B | new weight | flag
-  int rc = ensure_tmp(v, 4 * bytes + 64);
+  int rc = reserve(v, v->scratch, 4 * bytes + 64, 0);
   if (rc) return rc;
-  float* orig = reinterpret_cast<float*>(v->d_tmp);
+  float* orig = reinterpret_cast<float*>(v->scratch.d);
   float* est[2] = {orig + np, orig + 2 * np};
   float* wout = orig + 3 * np;
   uint32_t* flag = reinterpret_cast<uint32_t*>(orig + 4 * np);
@@ -432,9 +432,9 @@ int tf_pre_frame_depth(tf_volume* v, uint16_t* d_depth, float* d_refined, float 
     }
   const size_t np = (size_t)c.W * c.H;
   const size_t lut_at = 64, img_at = lut_at + ((kBfBins + 2) * sizeof(float) + 63) / 64 * 64;
-  int rc = ensure_tmp(v, img_at + np * sizeof(float));
+  int rc = reserve(v, v->scratch, img_at + np * sizeof(float), 0);
   if (rc) return rc;
-  uint8_t* base = reinterpret_cast<uint8_t*>(v->d_tmp);
+  uint8_t* base = reinterpret_cast<uint8_t*>(v->scratch.d);
   BfState* st = reinterpret_cast<BfState*>(base);
   float* lut = reinterpret_cast<float*>(base + lut_at);
   float* metres = reinterpret_cast<float*>(base + img_at);

@@ -501,6 +501,20 @@ int query_check(tf_volume* v, const float* xyz, int64_t n, uint32_t want, const 
 
 struct RayCam { float fx, fy, cx, cy; int W, H; };
 
+bool pose_finite(const float* pose) {
+  for (int i = 0; i < 12; ++i)
+    if (!isfinite(pose[i])) return false;
+  return true;
+}
+
+// camera-to-world 3x4 pose -> rotation (row-major) and translation
+void split_pose(const float* pose, float R[9], float t[3]) {
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) R[3 * r + c] = pose[4 * r + c];
+    t[r] = pose[4 * r + 3];
+  }
+}
+
 int ray_check(tf_volume* v, const float* pose, float near_plane, float far_plane, int32_t max_steps, RayCam* cam) {
   if (!v || !pose) { set_error("null argument"); return TF_ERR_INVALID; }
   if (!(near_plane >= 0.f) || !(far_plane > near_plane) || !isfinite(far_plane)) {
@@ -508,8 +522,7 @@ int ray_check(tf_volume* v, const float* pose, float near_plane, float far_plane
     return TF_ERR_INVALID;
   }
   if (max_steps <= 0) { set_error("max_steps must be positive"); return TF_ERR_INVALID; }
-  for (int i = 0; i < 12; ++i)
-    if (!isfinite(pose[i])) { set_error("pose is not finite"); return TF_ERR_INVALID; }
+  if (!pose_finite(pose)) { set_error("pose is not finite"); return TF_ERR_INVALID; }
   if (v->ray_w > 0) *cam = {v->ray_fx, v->ray_fy, v->ray_cx, v->ray_cy, v->ray_w, v->ray_h};
   else *cam = {v->cam.fxi, v->cam.fyi, v->cam.cxi, v->cam.cyi, v->cam.W, v->cam.H};
   if (cam->W <= 0 || cam->H <= 0 || !(cam->fx > 0.f) || !(cam->fy > 0.f)) {
@@ -522,10 +535,7 @@ int ray_check(tf_volume* v, const float* pose, float near_plane, float far_plane
 int ray_launch(tf_volume* v, const float* pose, float near_plane, float far_plane, int32_t max_steps, const RayCam& cam,
                float* depth, float* normal, uint8_t* rgba, float* vertex) {
   RayArgs a;
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) a.R[3 * r + c] = pose[4 * r + c];
-    a.t[r] = pose[4 * r + 3];
-  }
+  split_pose(pose, a.R, a.t);
   a.fx = cam.fx; a.fy = cam.fy; a.cxs = cam.cx + 0.5f; a.cys = cam.cy + 0.5f;
   a.W = cam.W; a.H = cam.H; a.tiles_x = (cam.W + 7) / 8;
   a.near_p = near_plane; a.far_p = far_plane; a.max_steps = max_steps; a.res = v->res;
@@ -552,18 +562,14 @@ int surf_check(tf_volume* v, const float* xyz, int64_t n, const float* dist, con
 
 int refine_check(tf_volume* v, const float* depth, const float* weight, const float* pose) {
   if (!v || !depth || !weight || !pose) { set_error("null argument"); return TF_ERR_INVALID; }
-  for (int i = 0; i < 12; ++i)
-    if (!isfinite(pose[i])) { set_error("pose is not finite"); return TF_ERR_INVALID; }
+  if (!pose_finite(pose)) { set_error("pose is not finite"); return TF_ERR_INVALID; }
   if (v->cam.W <= 0 || v->cam.H <= 0) { set_error("no camera (tf_set_camera)"); return TF_ERR_INVALID; }
   return TF_OK;
 }
 
 int refine_launch(tf_volume* v, const float* pose, float* d_depth, float* d_weight) {
   RefineArgs a;
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) a.R[3 * r + c] = pose[4 * r + c];
-    a.t[r] = pose[4 * r + 3];
-  }
+  split_pose(pose, a.R, a.t);
   a.fx = v->cam.fxi; a.fy = v->cam.fyi; a.cx = v->cam.cxi; a.cy = v->cam.cyi;
   a.W = v->cam.W; a.H = v->cam.H; a.tiles_x = (v->cam.W + 7) / 8;
   a.near_p = v->cam.nearP; a.far_p = v->cam.farP;
@@ -594,30 +600,24 @@ int tf_query_points(tf_volume* v, const float* xyz, int64_t n, uint32_t want_mas
   if (rc) return rc;
   TF_DEV(v);
   if (n == 0) return TF_OK;
-  // device layout: xyz | sdf | weight | grad | sdf_tri | flags | rgb, 16-byte aligned
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
+  // staging: xyz | sdf | weight | grad | sdf_tri | flags | rgb
+  Layout L;
   const size_t N = (size_t)n;
-  const size_t o_xyz = take(12 * N), o_s = take(4 * N), o_w = take(4 * N), o_g = take(12 * N), o_t = take(4 * N),
-               o_f = take(4 * N), o_c = take(3 * N);
-  if ((rc = ensure_tmp(v, o)) || (rc = ensure_pinned(v, o))) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));  // the scratch buffers may still be read by an earlier call
-  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  memcpy(hb + o_xyz, xyz, 12 * N);
-  TF_HIP(hipMemcpyAsync(db + o_xyz, hb + o_xyz, 12 * N, hipMemcpyHostToDevice, v->stream));
-  rc = query_launch(v, reinterpret_cast<const float*>(db + o_xyz), (uint32_t)n, want_mask,
-                    reinterpret_cast<float*>(db + o_s), reinterpret_cast<float*>(db + o_w), reinterpret_cast<float*>(db + o_g),
-                    reinterpret_cast<float*>(db + o_t), db + o_c, reinterpret_cast<uint32_t*>(db + o_f));
+  const size_t o_xyz = L.take(12 * N), o_s = L.take(4 * N), o_w = L.take(4 * N), o_g = L.take(12 * N), o_t = L.take(4 * N),
+               o_f = L.take(4 * N), o_c = L.take(3 * N);
+  Stage sg;
+  if ((rc = stage_begin(v, v->scratch, L.size, L.size, &sg)) || (rc = stage_in(v, sg, o_xyz, xyz, 12 * N))) return rc;
+  rc = query_launch(v, sg.dp<const float>(o_xyz), (uint32_t)n, want_mask, sg.dp<float>(o_s), sg.dp<float>(o_w),
+                    sg.dp<float>(o_g), sg.dp<float>(o_t), sg.d + o_c, sg.dp<uint32_t>(o_f));
   if (rc) return rc;
-  TF_HIP(hipMemcpyAsync(hb + o_s, db + o_s, o - o_s, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(sg.h + o_s, sg.d + o_s, L.size - o_s, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  if (want_mask & 1u) memcpy(sdf, hb + o_s, 4 * N);
-  if (want_mask & 2u) memcpy(weight, hb + o_w, 4 * N);
-  if (want_mask & 4u) memcpy(grad3, hb + o_g, 12 * N);
-  if (want_mask & 8u) memcpy(sdf_tri, hb + o_t, 4 * N);
-  if (want_mask & 16u) memcpy(rgb3, hb + o_c, 3 * N);
-  memcpy(flags, hb + o_f, 4 * N);
+  if (want_mask & 1u) memcpy(sdf, sg.h + o_s, 4 * N);
+  if (want_mask & 2u) memcpy(weight, sg.h + o_w, 4 * N);
+  if (want_mask & 4u) memcpy(grad3, sg.h + o_g, 12 * N);
+  if (want_mask & 8u) memcpy(sdf_tri, sg.h + o_t, 4 * N);
+  if (want_mask & 16u) memcpy(rgb3, sg.h + o_c, 3 * N);
+  memcpy(flags, sg.h + o_f, 4 * N);
   return TF_OK;
 }
 
@@ -658,25 +658,21 @@ int tf_raycast(tf_volume* v, const float pose[12], float near_plane, float far_p
   if (rc) return rc;
   TF_DEV(v);
   const size_t P = (size_t)cam.W * cam.H;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
-  const size_t o_d = take(depth ? 4 * P : 0), o_n = take(normal ? 12 * P : 0), o_c = take(rgba ? 4 * P : 0),
-               o_v = take(vertex ? 12 * P : 0);
-  if (o == 0) return TF_OK;
-  if ((rc = ensure_tmp(v, o)) || (rc = ensure_pinned(v, o))) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  rc = ray_launch(v, pose, near_plane, far_plane, max_steps, cam, depth ? reinterpret_cast<float*>(db + o_d) : nullptr,
-                  normal ? reinterpret_cast<float*>(db + o_n) : nullptr, rgba ? db + o_c : nullptr,
-                  vertex ? reinterpret_cast<float*>(db + o_v) : nullptr);
+  Layout L;
+  const size_t o_d = L.take(depth ? 4 * P : 0), o_n = L.take(normal ? 12 * P : 0), o_c = L.take(rgba ? 4 * P : 0),
+               o_v = L.take(vertex ? 12 * P : 0);
+  if (L.size == 0) return TF_OK;
+  Stage sg;
+  if ((rc = stage_begin(v, v->scratch, L.size, L.size, &sg))) return rc;
+  rc = ray_launch(v, pose, near_plane, far_plane, max_steps, cam, depth ? sg.dp<float>(o_d) : nullptr,
+                  normal ? sg.dp<float>(o_n) : nullptr, rgba ? sg.d + o_c : nullptr, vertex ? sg.dp<float>(o_v) : nullptr);
   if (rc) return rc;
-  TF_HIP(hipMemcpyAsync(hb, db, o, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(sg.h, sg.d, L.size, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  if (depth) memcpy(depth, hb + o_d, 4 * P);
-  if (normal) memcpy(normal, hb + o_n, 12 * P);
-  if (rgba) memcpy(rgba, hb + o_c, 4 * P);
-  if (vertex) memcpy(vertex, hb + o_v, 12 * P);
+  if (depth) memcpy(depth, sg.h + o_d, 4 * P);
+  if (normal) memcpy(normal, sg.h + o_n, 12 * P);
+  if (rgba) memcpy(rgba, sg.h + o_c, 4 * P);
+  if (vertex) memcpy(vertex, sg.h + o_v, 12 * P);
   return TF_OK;
 }
 
@@ -694,20 +690,16 @@ int tf_distance_from_surface(tf_volume* v, const float* xyz, int64_t n, float* d
   TF_DEV(v);
   if (n == 0) return TF_OK;
   const size_t N = (size_t)n;
-  const size_t o_d = (12 * N + 15) & ~(size_t)15, o_w = o_d + ((4 * N + 15) & ~(size_t)15), total = o_w + 4 * N;
-  if ((rc = ensure_tmp(v, total)) || (rc = ensure_pinned(v, total))) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));  // the scratch buffers may still be read by an earlier call
-  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  memcpy(hb, xyz, 12 * N);
-  TF_HIP(hipMemcpyAsync(db, hb, 12 * N, hipMemcpyHostToDevice, v->stream));
-  rc = surf_launch(v, reinterpret_cast<const float*>(db), (uint32_t)n, reinterpret_cast<float*>(db + o_d),
-                   reinterpret_cast<float*>(db + o_w));
+  Layout L;
+  const size_t o_xyz = L.take(12 * N), o_d = L.take(4 * N), o_w = L.take(4 * N);
+  Stage sg;
+  if ((rc = stage_begin(v, v->scratch, L.size, L.size, &sg)) || (rc = stage_in(v, sg, o_xyz, xyz, 12 * N))) return rc;
+  rc = surf_launch(v, sg.dp<const float>(o_xyz), (uint32_t)n, sg.dp<float>(o_d), sg.dp<float>(o_w));
   if (rc) return rc;
-  TF_HIP(hipMemcpyAsync(hb + o_d, db + o_d, total - o_d, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(sg.h + o_d, sg.d + o_d, L.size - o_d, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  memcpy(dist, hb + o_d, 4 * N);
-  memcpy(tsdf_weight, hb + o_w, 4 * N);
+  memcpy(dist, sg.h + o_d, 4 * N);
+  memcpy(tsdf_weight, sg.h + o_w, 4 * N);
   return TF_OK;
 }
 
@@ -723,20 +715,19 @@ int tf_refine_frame_in_voxel(tf_volume* v, float* depth, float* weight, const fl
   if (rc) return rc;
   TF_DEV(v);
   const size_t P = (size_t)v->cam.W * v->cam.H;
-  const size_t o_w = (4 * P + 15) & ~(size_t)15, total = o_w + 4 * P;
-  if ((rc = ensure_tmp(v, total)) || (rc = ensure_pinned(v, total))) return rc;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  uint8_t* hb = reinterpret_cast<uint8_t*>(v->h_pinned);
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  memcpy(hb, depth, 4 * P);
-  memcpy(hb + o_w, weight, 4 * P);  // (skipped pixels keep the caller's weight)
-  TF_HIP(hipMemcpyAsync(db, hb, total, hipMemcpyHostToDevice, v->stream));
-  rc = refine_launch(v, pose, reinterpret_cast<float*>(db), reinterpret_cast<float*>(db + o_w));
+  Layout L;
+  const size_t o_d = L.take(4 * P), o_w = L.take(4 * P);
+  Stage sg;
+  if ((rc = stage_begin(v, v->scratch, L.size, L.size, &sg))) return rc;
+  memcpy(sg.h + o_d, depth, 4 * P);
+  memcpy(sg.h + o_w, weight, 4 * P);  // (skipped pixels keep the caller's weight)
+  TF_HIP(hipMemcpyAsync(sg.d, sg.h, L.size, hipMemcpyHostToDevice, v->stream));
+  rc = refine_launch(v, pose, sg.dp<float>(o_d), sg.dp<float>(o_w));
   if (rc) return rc;
-  TF_HIP(hipMemcpyAsync(hb, db, total, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(sg.h, sg.d, L.size, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  memcpy(depth, hb, 4 * P);
-  memcpy(weight, hb + o_w, 4 * P);
+  memcpy(depth, sg.h + o_d, 4 * P);
+  memcpy(weight, sg.h + o_w, 4 * P);
   return TF_OK;
 }
 

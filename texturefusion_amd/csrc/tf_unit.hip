@@ -383,18 +383,15 @@ int tf_keyframe_unit_device(tf_volume* v, const tf_unit_group* fresh, const tf_u
   // exchanges the adjacency flags and clears meshesToUpdate (MobileFusion.cpp:343-355), its view selection runs, and
   // tf_generate_patches / tf_update_atlas take its labels.
   const size_t cap = (size_t)v->dev.max_chunks;
-  rc = ensure_tmp(v, cap * 16 + 16);
+  rc = dirty_list_enqueue(v);
   if (rc) return rc;
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->d_tmp);
-  TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
-  launch_list_dirty(v->dev, reinterpret_cast<int4*>(db + 16), (uint32_t)cap, v->clear_floor, v->stream);
-  TF_HIP(hipMemcpyAsync(db, &v->dev.vctl->n_tmp, 4, hipMemcpyDeviceToDevice, v->stream));
+  const uint8_t* db = reinterpret_cast<const uint8_t*>(v->scratch.d);
   (void)nbr_next_seq(v);
   launch_mesh(v->dev, v->mesh_par, reinterpret_cast<const int4*>(db + 16), reinterpret_cast<const uint32_t*>(db), (uint32_t)cap,
               ++v->mesh_epoch, v->res, false, -1, 1u << 30, nullptr, -1, v->stream);
   v->mesh_par ^= 1;
   TF_HIP(hipGetLastError());
-  // (d_tmp holds the dirty list: a tf_compress_meshes right behind this call takes it from there instead of scanning the
+  // (scratch.d holds the dirty list: a tf_compress_meshes right behind this call takes it from there instead of scanning the
   // chunks' marks again; its length stays on the device -- this call does not wait)
   v->dirty_list_n = ~0u;
   v->dirty_list_seq = v->call_seq;

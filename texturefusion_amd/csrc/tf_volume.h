@@ -59,6 +59,49 @@ void set_error(const std::string& msg);
     }                                                                                       \
   } while (0)
 
+// Scratch pool: a device half and a pinned host half, each grown on demand to a power of two.  Before a half that is in use
+// grows, the stream is synchronised and the old allocation freed.  The halves grow independently: growing the host half
+// never frees the device half (which may hold the dirty list tf_compress_meshes takes over, tf_volume::dirty_list_seq).
+struct Scratch {
+  void* d = nullptr;
+  size_t d_bytes = 0;
+  void* h = nullptr;
+  size_t h_bytes = 0;
+};
+int reserve(tf_volume* v, Scratch& s, size_t dev_bytes, size_t host_bytes);
+void scratch_free(Scratch& s);
+
+// Byte layout of a staging area: each block at a 16-byte aligned offset; size = the total.
+struct Layout {
+  size_t size = 0;
+  size_t take(size_t bytes) {
+    const size_t at = size;
+    size = (size + bytes + 15) & ~(size_t)15;
+    return at;
+  }
+};
+
+// Host and device base of a staging area in a pool.
+struct Stage {
+  uint8_t* h = nullptr;
+  uint8_t* d = nullptr;
+  template <typename T> T* hp(size_t at) const { return reinterpret_cast<T*>(h + at); }
+  template <typename T> T* dp(size_t at) const { return reinterpret_cast<T*>(d + at); }
+};
+// Reserves the pool, then synchronises the stream once: an earlier call may still read or write the pool.
+int stage_begin(tf_volume* v, Scratch& s, size_t dev_bytes, size_t host_bytes, Stage* st);
+// Host bytes in at offset `at` of the staging area, and their upload to the same offset of the device half (enqueued).
+int stage_in(tf_volume* v, const Stage& st, size_t at, const void* src, size_t bytes);
+// stage_begin for `bytes` on both halves, then ids (host, int32[3n]) as an int4 list at offset 0, its upload enqueued.
+int stage_ids(tf_volume* v, Scratch& s, size_t bytes, const int32_t* ids, int64_t n, Stage* st);
+// The first m entries of the int4 list at the start of the pool's device half -> out (int32[3m]); returns after the copy.
+int download_ids(tf_volume* v, const Scratch& s, int64_t m, int32_t* out);
+// int32[3n] -> int4[n] (w: the fourth word per id, or 0), and back.
+void pack_ids(const int32_t* ids, int64_t n, int32_t* out4, const int* w = nullptr);
+void unpack_ids(const int32_t* in4, int64_t n, int32_t* ids);
+// set_error("chunk (x,y,z) <what>") for entry i of ids; returns TF_ERR_MISSING_CHUNK
+int missing_chunk_error(const int32_t* ids, int64_t i, const char* what);
+
 struct ProfEvent {
   hipEvent_t a, b;
   int kind;
@@ -106,11 +149,7 @@ struct AtlasState {
   // phase 2 (boundary meshes behind the caller's unpack, pending patch stage) has not
   bool phase1_on = false;
   uint32_t phase1_epoch = 0;
-  // staging
-  void* d_stage = nullptr;
-  size_t d_stage_bytes = 0;
-  void* h_stage = nullptr;
-  size_t h_stage_bytes = 0;
+  Scratch stage;  // the atlas entry points' own pool (they leave tf_volume::scratch alone)
 };
 
 // RCCL communicator of the handle (tf_comm_init) and the exchange buffers
@@ -193,8 +232,6 @@ struct tf_volume {
   long host_waits = 0;  // copies a launch had to wait for in the stream (TF_HOST_TRACE prints it)
   double host_trace[6] = {0, 0, 0, 0, 0, 0};  // TF_HOST_TRACE=1: microseconds per phase of tf_integrate_frame_host, [5] = calls
   tf::CopyPool* copy_pool = nullptr;  // helper threads of the staging copy (TF_COPY_THREADS, default 3)
-  void* h_pinned = nullptr;      // pinned host staging (uploads / downloads)
-  size_t h_pinned_bytes = 0;
   tf::FrameImages frame{nullptr, nullptr, nullptr};
   bool frame_bound = false;
   // host shadow of the device-resident visible list (int32[3*n]); -1 = device list unknown
@@ -205,7 +242,7 @@ struct tf_volume {
   // keyframe's frames does -- costs no upload
   std::vector<uint8_t> host_needs, host_new;
   int64_t host_flags_n = -2;
-  // entry points counted (TF_DEV*): tf_compress_meshes reuses the dirty list tf_update_meshes left in d_tmp when that was
+  // entry points counted (TF_DEV*): tf_compress_meshes reuses the dirty list tf_update_meshes left in scratch.d when that was
   // the call right before it (MobileFusion.cpp:327-345 calls them back to back; nothing in between can have marked a chunk)
   uint64_t call_seq = 0, dirty_list_seq = ~0ull;
   uint32_t dirty_list_n = 0;
@@ -235,9 +272,7 @@ struct tf_volume {
   hipEvent_t last_upload = nullptr;  // the newest frame's upload (tf_host_frame_fence waits for it)
   float* d_group = nullptr;  // staging of tf_integrate_depth_group_host: six depth images
   size_t d_group_pixels = 0;
-  // on-demand device scratch
-  void* d_tmp = nullptr;
-  size_t d_tmp_bytes = 0;
+  tf::Scratch scratch;  // on-demand staging of the entry points (uploads / downloads, device scratch)
   // profiling
   bool prof_open = false;
   uint32_t prof_mask = 0;  // bit k = time kernels of kind TF_PROF_k
@@ -287,7 +322,6 @@ struct AtlasWriteScope {
 };
 // stream synchronisation + control blocks; VolCtl::n_tmp as read (may be NULL); sticky status -> error code
 int sync_status(tf_volume* v, uint32_t* n_tmp);
-int ensure_tmp(tf_volume* v, size_t bytes);
 int launch_prepare(tf_volume* v, const Pose& pose, bool with_acquire, hipStream_t s = nullptr);  // tf_capi.cpp
 struct KfStoreArgs;  // tf_kf_store.h
 // ride_filter: a patch stage still pending when the stage starts rides on its filter launch (the keyframe unit: there is
@@ -301,11 +335,12 @@ int texture_stage_finish(tf_volume* v, const FrameImages& img, uint32_t frame_ep
 int xchg_band_counts(tf_volume* v, const FrameCtl* ctl, uint32_t tag, uint32_t cnt[4], hipStream_t s = nullptr);
 uint32_t nbr_next_seq(tf_volume* v);  // neighbour table: the seq of the filter launch about to go out (tf_capi.cpp)
 int flush_deferred(tf_volume* v);
+// the dirty set (Chisel::meshesToUpdate) as a device list in scratch.d: [0,16) count word, ids from byte 16 (tf_mesh.hip)
+int dirty_list_enqueue(tf_volume* v);
 void launch_dirty_frame_store(const VolumeDev& v, int par, uint32_t stamp, const KfStoreArgs& a, hipStream_t s);  // tf_mesh.hip
 int patch_flush(tf_volume* v);
 bool host_defer_default();  // !(TF_HOST_DEFER=0 in the environment)
 int fused_arm(tf_volume* v);  // the fused flow's counter sets in their start state (no-op once armed)
-int ensure_pinned(tf_volume* v, size_t bytes);
 void prof_begin(tf_volume* v, int kind, hipStream_t s = nullptr);
 void prof_end(tf_volume* v, hipStream_t s = nullptr);
 int atlas_init(tf_volume* v);
