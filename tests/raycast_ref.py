@@ -145,9 +145,10 @@ class RefVolume:
         c = np.zeros((8, n), np.float32)
         cnt = np.zeros((8, n, 4), np.float32)
         okc = ok.copy()
-        for k in range(8):
+        inr = ok.copy()  # (the corners are looked up wherever the coordinates are in range: colour validity does not
+        for k in range(8):  # depend on the corners' weights -- a colour-only voxel, weight 0, count > 0, counts as coloured)
             vx, vy, vz = i[0] + (k & 1), i[1] + ((k >> 1) & 1), i[2] + ((k >> 2) & 1)
-            sl = np.where(ok, self.slot(vx >> 3, vy >> 3, vz >> 3), -1)
+            sl = np.where(inr, self.slot(vx >> 3, vy >> 3, vz >> 3), -1)
             vi = ((vz & 7) * 8 + (vy & 7)) * 8 + (vx & 7)
             s0 = np.maximum(sl, 0)
             ok_k = sl >= 0

@@ -254,7 +254,8 @@ static int init_device_state(tf_volume* v) {
 // The kernels of Chisel::PrepareIntersectChunks (Structure/Chisel.h:103-140).  The fused per-frame
 // unit skips the stand-alone slot lookup: k_integrate<FUSED> does it per chunk.
 // Selections made ahead for frames of a previous streaming call (n_ahead) depend on the camera, the truncation
-// model and the partition: a setter that changes one of these discards them, so that the next call selects again.
+// model, the weight (the list records hold weight / (2 truncation), chunk_pre) and the partition: a setter that changes
+// one of these discards them, so that the next call selects again.
 static void discard_primed(tf_volume* v) {
   for (int k = 0; k < v->n_primed; ++k) {
     VolumeDev d = v->dev;
@@ -606,6 +607,7 @@ int tf_set_truncation(tf_volume* v, float q, float l, float c, float s) {
 int tf_set_weight(tf_volume* v, float w) {
   if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
   TF_DEV(v);
+  discard_primed(v);
   v->ig.weight = w;
   return TF_OK;
 }
