@@ -18,26 +18,30 @@ Frame windows (ORBIT = 200 frames = one turn of the camera; every window starts 
   pre-roll   one full orbit, untimed: every later frame meets a steady-state volume (~2.9 k meshes per frame)
   warm-up    W frames through the timed entry point
   timed      K frames -> "value", "ms_per_step" (wall clock, barrier + device synchronisation on both sides)
+A plain run is that: set-up, these three windows, --dump-outputs, the line.  --full adds, behind the timed window,
+  repeats    the same K orbit positions in later turns, each behind its own W warm-up frames -> "repeats"
   resident   the same K orbit positions one turn later, frames already in HBM (no H2D) -> "resident"
   staged     the same positions as host frames from unregistered arrays (staging copy by helper threads) -> "staged_host_frames"
   rgb host   the same positions as host frames with Frame::rgb (3 B per pixel) instead of the RGBA staging image -> "rgb_host_frames"
   events     the same positions again with HIP events around every launch -> per-kernel times
   replay     the same positions again, frame by frame, reading back the exact integer counts -> algorithmic bytes
-A rocprofv3 --kernel-trace child pass and two --pmc child passes of the same command (same pre-roll / warm-up /
-steps: the same frames, the launches of the timed window sliced out) give the profiler's kernel durations and
-the HBM-side traffic.
+then the keyframe flows and the CPU baseline; and ahead of them all, before this process touches the GPU, the side runs
+(configs[1], configs[3]) and a rocprofv3 --kernel-trace child pass and two --pmc child passes of the same command (same
+pre-roll / warm-up / steps: the same frames, the launches of the timed window sliced out), which give the profiler's
+kernel durations and the HBM-side traffic.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (metric/value/... + "roofline" + "cpu_baseline").
+Rank 0 prints ONE JSON line (metric/value/...; with --full also "roofline", "cpu_baseline", "side", ...).
 --dump-outputs DIR: right after the timed window, rank 0 writes what a caller reads of the volume (voxels, meshes, patches,
 atlas texels; seeded samples, float32 / float64 .npy, under 64 MB) -- the same arguments give the same inputs, so two builds
 can be compared output for output.
 N > 1: one process per GPU, static chunk-range partition of ONE stream (slabs of the key x + y + z) -- every
 rank sees every frame, selects / integrates / meshes / textures only the chunks of its slab ("strong"
-scaling); the ranks exchange the chunks of their ghost bands over RCCL.
+scaling); the ranks exchange the chunks of their ghost bands over RCCL.  "per_rank" comes from the
+timed window itself; --full adds the independent-streams and sharded-keyframe-unit figures.
 """
 from __future__ import annotations
 
@@ -101,12 +105,17 @@ def parse():
                     help="run the N>1 code path (partition + boundary exchange) even with one rank (smoke test)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the caller reads of the volume as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: side runs of the other configurations, rocprofv3 child passes, repeat / "
+                         "resident / other host-frame / event windows, roofline, keyframe flows, CPU baseline; N>1: the per-rank "
+                         "event pass, independent streams, the sharded keyframe unit.  The --no-* / --cpu-* / --repeats flags "
+                         "shape these figures")
     return ap.parse_args()
 
 
 # ---------------------------------------------------------------------------------------------------------
-# the synthetic stream: generated once per parameter set, kept in /tmp so that the profiler child passes (and a
-# second run on the same box) load it instead of generating it again
+# the synthetic stream: generated afresh by every process that needs it (nothing is kept between runs), its frames
+# spread over a pool of threads
 # ---------------------------------------------------------------------------------------------------------
 def cgroup_cpu_quota():
     """CPUs' worth of CFS quota of this container (cgroup v2 cpu.max / v1 cfs_quota_us), or None when unlimited"""
@@ -124,34 +133,32 @@ def cgroup_cpu_quota():
 
 
 def load_stream(args, cam):
+    """the orbit's host images and poses.  Every frame is a pure function of its index (synth.room_frame), so the frames
+    are computed side by side -- numpy leaves the interpreter lock for its array loops -- each straight into its slot:
+    the same arrays as one frame after the other (tests/test_host_logic.py), in a fraction of the time (that loop spends
+    ~60 ms per 640x480 frame)."""
+    from concurrent.futures import ThreadPoolExecutor
     from texturefusion_amd import synth
     n = args.unique_frames
-    key = "%s_%dx%d_%d" % (args.scene, cam.width, cam.height, n)
-    base = os.path.join("/tmp", "tf_bench_stream_" + key)
-    names = [base + suf for suf in ("_depth.npy", "_rgba.npy", "_pose.npy")]
-    try:
-        if all(os.path.exists(f) for f in names):
-            depth, rgba, pose = (np.load(f) for f in names)
-            if depth.shape == (n, cam.height, cam.width) and rgba.shape == (n, cam.height, cam.width, 4):
-                return depth, rgba, pose
-    except Exception:
-        pass
     depth = np.empty((n, cam.height, cam.width), np.float32)
     rgba = np.empty((n, cam.height, cam.width, 4), np.uint8)
     pose = np.empty((n, 3, 4), np.float32)
-    for k in range(n):
+
+    def frame(k):
         if args.scene == "big":
             f = synth.room_frame(k, cam, half=(4.0, 3.0, 4.0), radius=0.5, with_quality=False)
         else:
             f = synth.room_frame(k, cam, with_quality=False)
         depth[k], rgba[k], pose[k] = f[0], f[1], np.asarray(f[3], np.float32).reshape(3, 4)
+
     try:
-        for f, a in zip(names, (depth, rgba, pose)):
-            tmp = f + ".%d.tmp.npy" % os.getpid()
-            np.save(tmp, a)
-            os.replace(tmp, f)
+        cpus = len(os.sched_getaffinity(0))
     except Exception:
-        pass
+        cpus = os.cpu_count() or 1
+    quota = cgroup_cpu_quota()
+    workers = max(1, min(16, cpus, int(quota) if quota is not None else cpus))
+    with ThreadPoolExecutor(workers) as pool:
+        list(pool.map(frame, range(n)))  # (list(): a frame that raises raises here)
     return depth, rgba, pose
 
 
@@ -318,10 +325,11 @@ class Job:
         if args.child:
             args.no_roofline = args.no_group = True
             args.cpu_frames = 0
+            args.full = False
         self.side = self.prof_child = None
         self.pos = 0
 
-    # ---- phase 1: the processes that must run BEFORE this one touches the GPU ------------------------------------------
+    # ---- phase 1 (--full): the processes that must run BEFORE this one touches the GPU ---------------------------------
     def children(self):
         # The other single-GPU configurations of BASELINE.json come FIRST, each a bench.py process of its own (the default line
         # carries their headline figures as scalars); then the profiler child passes of this line.  All of them before this process
@@ -670,7 +678,7 @@ class Job:
                 "bytes_received_per_record_received": (st["bytes_received"] / st["records_received"]) if st["records_received"] else None,
                 "exchange_form": "neighbours (sized by the frame's selection)" if st["mode"] == 0 else "all-gather (fixed capacity)",
                 "transport": "RCCL inside the library" if self.use_rccl else "torch.distributed test hook"}
-        if self.use_rccl and self.textured and not args.child:
+        if self.use_rccl and self.textured and args.full:
             # the same window once more with HIP events around every launch and around the exchange (untimed diagnostic)
             vol.sync()
             vol.profile_enable(("integrate", "dirty", "mesh", "xchg", "xchg_wait"))
@@ -721,7 +729,7 @@ class Job:
                 sharded_unit = {"error": repr(e)[:300]}
         return indep, sharded_unit
 
-    # ---- phase 7 (N = 1): the timed window's orbit positions again, other ways ----------------------------------------
+    # ---- phase 7 (N = 1, --full): the timed window's orbit positions again, other ways --------------------------------
     def _time_host_window(self, fn):
         """Wm frames through `fn` (untimed) from Wm frames ahead of the window, then the K frames timed -> seconds"""
         self.land_before_window()
@@ -987,7 +995,11 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.child:
         raise SystemExit(spawn_ranks(args))
     job = Job(args)            # environment, affinity, the stream on the host
-    job.children()             # side runs + profiler child passes: before this process touches the GPU
+    # A plain run sets up, warms up, times the K steps, dumps (--dump-outputs) and prints the line; every other figure,
+    # and every process or window it needs, belongs to --full.
+    full = args.full           # (never in a profiler child pass: Job clears it there)
+    if full:
+        job.children()         # side runs + profiler child passes: before this process touches the GPU
     job.device()               # torch, process group, the stream in HBM
     job.volume()
     if job.multi:
@@ -1003,19 +1015,19 @@ def main():
         vol.close()
         return
     indep = sharded_unit = None
-    if multi and not args.no_independent:
+    if full and multi and not args.no_independent:
         indep, sharded_unit = job.replicas()
 
     # ---- N = 1: the timed window's orbit positions again -- its spread, and the other ways a frame can come in ----
-    single_host = job.use_host and not multi
-    repeats = job.repeat_windows() if (not multi and args.repeats > 0) else None
+    single_host = full and job.use_host and not multi
+    repeats = job.repeat_windows() if (full and not multi and args.repeats > 0) else None
     resident = job.resident_window() if single_host else None
     other_host = _side_figure(job.other_host_window) if single_host else None
     async_host = _side_figure(job.async_host_window) if (single_host and job.host_registered) else None
     rgb_host = _side_figure(job.rgb_host_window) if single_host else None
     prof = dt_instr = pair_us = None
     kinds = STEP_KERNELS if job.textured else ("integrate",)
-    if not args.no_roofline and not multi:
+    if full and not args.no_roofline and not multi:
         prof, dt_instr, pair_us = job.event_window(kinds)
 
     out = job.line()
@@ -1054,15 +1066,15 @@ def main():
         job.pos += job.K
 
     # ---- the keyframe-group flow of TSDFFusion: 1 colour + 6 depth-only frames over one chunk list -------
-    if rank == 0 and not multi and not args.no_group and not args.no_roofline:
+    if full and rank == 0 and not multi and not args.no_group and not args.no_roofline:
         out["keyframe_group"] = keyframe_group(args, cam, res, job.d_depth, job.d_rgba, job.poses, n_unique, job.local_rank)
 
     # ---- the keyframe unit: tsdfFusion as one asynchronous call per keyframe -------------------------------
-    if rank == 0 and not multi and not args.no_group and not args.no_roofline:
+    if full and rank == 0 and not multi and not args.no_group and not args.no_roofline:
         out["keyframe_unit"] = keyframe_unit(args, cam, res, job.d_depth, job.d_rgba, job.poses, job.pinv, n_unique, job.local_rank)
 
     # ---- CPU baseline: the oracle (C port of the reference path) on the host cores ------------
-    if rank == 0 and world == 1 and args.cpu_frames > 0:  # (rank 0 at N = 1 only)
+    if full and rank == 0 and world == 1 and args.cpu_frames > 0:  # (rank 0 at N = 1 only)
         if job.orig_affinity:
             try:
                 os.sched_setaffinity(0, job.orig_affinity)  # the CPU port gets every core of the host
@@ -1440,8 +1452,8 @@ def side_runs(args):
             ("hall", ["--scene", "big", "--hires", "--steps", str(hall_steps), "--warmup", str(min(args.warmup, 5))],
              "configs[3]: S-hall 8x6x8 m, 1280x960, 5 mm, textured unit (host frames, H2D inside)"))
     for tag, flags, what in runs:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + flags + ["--no-side", "--no-traffic", "--cpu-frames", "0", "--no-group",
-                                                                         "--repeats", "2", "--res", repr(args.res)]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + flags + ["--full", "--no-side", "--no-traffic", "--cpu-frames", "0",
+                                                                         "--no-group", "--repeats", "2", "--res", repr(args.res)]
         t0 = time.time()
         try:
             r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=420)

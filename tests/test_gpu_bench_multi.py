@@ -32,12 +32,12 @@ def test_two_ranks_on_one_gpu_under_torchrun(gpu_required):
 
 
 def test_bench_spawns_its_own_ranks(gpu_required):
-    """`python bench.py --gpus 2` without a launcher: two ranks, n_gpus == 2 in the line, the independent-streams figure
-    (two whole volumes, no exchange) next to the strong-scaling value."""
+    """`python bench.py --gpus 2 --full` without a launcher: two ranks, n_gpus == 2 in the line, the independent-streams
+    figure (two whole volumes, no exchange) next to the strong-scaling value."""
     env = dict(os.environ, TF_BENCH_DEVICE="0", TF_BENCH_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + SMALL
     d = _one_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
     ind = d["independent_streams"]

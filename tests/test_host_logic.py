@@ -121,6 +121,23 @@ def test_bench_refuses_more_ranks_than_devices():
     assert "device" in r.stderr
 
 
+def test_bench_stream_is_the_serial_stream():
+    """bench.py computes the orbit's frames on a pool of threads: every array holds the bytes synth.room_frame gives frame
+    by frame, for both scenes"""
+    import argparse
+
+    import bench
+    cam = synth.Camera()
+    for scene, kw in (("room", {}), ("big", dict(half=(4.0, 3.0, 4.0), radius=0.5))):
+        depth, rgba, pose = bench.load_stream(argparse.Namespace(unique_frames=12, scene=scene), cam)
+        assert depth.shape == (12, cam.height, cam.width) and rgba.shape == (12, cam.height, cam.width, 4)
+        for k in range(12):
+            d, c, _, p = synth.room_frame(k, cam, with_quality=False, **kw)
+            assert np.array_equal(depth[k].view(np.uint32), d.view(np.uint32))
+            assert np.array_equal(rgba[k], c)
+            assert np.array_equal(pose[k].view(np.uint32), np.asarray(p, np.float32).reshape(3, 4).view(np.uint32))
+
+
 def test_bench_rejects_a_world_size_that_contradicts_the_flag():
     import subprocess
     import sys

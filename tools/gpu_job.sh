@@ -11,15 +11,15 @@ for step in "$@"; do
   case $step in
     tests)  timeout 1500 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; echo "tests rc=$?"; tail -5 $O/pytest.log ;;
     testsx) timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "tests rc=$?"; tail -30 $O/pytest.log ;;
-    bench)  timeout 900 python bench.py --steps 200 --warmup 20 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 3000 $O/bench.json ;;
-    drv)    timeout 900 python bench.py --steps 20 --warmup 5 > $O/drv.json 2> $O/drv.err; echo "drv rc=$?"; tail -c 1500 $O/drv.json ;;
-    tsdf)   timeout 900 python bench.py --mode tsdf --steps 200 --warmup 20 > $O/tsdf.json 2> $O/tsdf.err; echo "tsdf rc=$?"; tail -c 1500 $O/tsdf.json ;;
-    hall)   timeout 900 python bench.py --scene big --hires --steps 60 --warmup 10 > $O/hall.json 2> $O/hall.err; echo "hall rc=$?"; tail -c 1500 $O/hall.json ;;
-    quick)  timeout 600 python bench.py --steps 200 --warmup 20 --no-pmc --cpu-frames 0 --no-group > $O/quick.json 2> $O/quick.err; echo "quick rc=$?"; tail -c 2500 $O/quick.json ;;
+    bench)  timeout 900 python bench.py --full --steps 200 --warmup 20 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 3000 $O/bench.json ;;
+    drv)    timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/drv.json 2> $O/drv.err; echo "drv rc=$?"; tail -c 1500 $O/drv.json ;;
+    tsdf)   timeout 900 python bench.py --full --mode tsdf --steps 200 --warmup 20 > $O/tsdf.json 2> $O/tsdf.err; echo "tsdf rc=$?"; tail -c 1500 $O/tsdf.json ;;
+    hall)   timeout 900 python bench.py --full --scene big --hires --steps 60 --warmup 10 > $O/hall.json 2> $O/hall.err; echo "hall rc=$?"; tail -c 1500 $O/hall.json ;;
+    quick)  timeout 600 python bench.py --full --steps 200 --warmup 20 --no-pmc --cpu-frames 0 --no-group > $O/quick.json 2> $O/quick.err; echo "quick rc=$?"; tail -c 2500 $O/quick.json ;;
     prof|prof_tsdf|prof_hall)   # rocprofv3 --kernel-trace --stats of the same command as bench / tsdf / hall (whole run: pre-roll, windows, replay)
             case $step in prof) A="--steps 200 --warmup 20";; prof_tsdf) A="--mode tsdf --steps 200 --warmup 20";; prof_hall) A="--scene big --hires --steps 60 --warmup 10";; esac
             U=$PWD/$O/$step; mkdir -p $U
-            (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $U/trace -o t -- python3 $OLDPWD/bench.py $A --no-pmc --cpu-frames 0 --no-group --repeats 0 > $U/bench_line_profiled.json 2> $U/prof.err)
+            (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $U/trace -o t -- python3 $OLDPWD/bench.py --full $A --no-pmc --cpu-frames 0 --no-group --repeats 0 > $U/bench_line_profiled.json 2> $U/prof.err)
             rc=$?  # (the profiler's / the benchmark's, not rm's)
             S=$(find $U/trace -name "*kernel_stats.csv" | head -1)
             if [ $rc -eq 0 ] && [ -n "$S" ]; then cp $S $O/${step}_kernel_stats.csv; head -8 $O/${step}_kernel_stats.csv | cut -c1-150; fi

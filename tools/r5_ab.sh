@@ -10,7 +10,7 @@ i=0
 for cfg in "$@"; do
   i=$((i+1))
   [ "$cfg" = "-" ] && cfg=""
-  env $cfg timeout 600 python bench.py --steps ${STEPS:-200} --warmup 20 --no-pmc --cpu-frames 0 --no-group --repeats 2 ${BENCH_ARGS:-} > $O/cfg$i.json 2> $O/cfg$i.err
+  env $cfg timeout 600 python bench.py --full --steps ${STEPS:-200} --warmup 20 --no-pmc --cpu-frames 0 --no-group --repeats 2 ${BENCH_ARGS:-} > $O/cfg$i.json 2> $O/cfg$i.err
   python - $O/cfg$i.json "$cfg" <<'PY'
 import json,sys
 try:
