@@ -627,7 +627,15 @@ TF_API int tf_meshes_upload(tf_volume* v, const int32_t* ids, int64_t n, const i
  *   Atlas.cpp:43-64; later calls keep it, Patch::clear) -> Patch::CalculateTexCoords in keyframe labels[i]
  *   (Patch.cpp:40-108) -> SetFrameid / SetImage.  out_hot = atlas.hot_start / hot_end.
  *   Returns TF_ERR_ATLAS_FULL when the atlas overflows (GeneratePatches' -1): the entry that did not get a
- *   slot and everything behind it in the list stays unprocessed. */
+ *   slot and everything behind it in the list stays unprocessed.
+ *   At the image's borders the reference's arithmetic is kept as it is: cameraX >= W clamps to W (not W - 1), x == W
+ *   reads the next row's first pixel (cv::Mat::at is unchecked), the bilinear tap kinds are its four.  Undefined
+ *   behaviour of the reference, defined here (every entry point that runs this stage, the fused ones included): a
+ *   read past the image's last pixel returns 0; an image coordinate that is NOT A NUMBER (0 / 0 for a vertex at the
+ *   keyframe's centre, a NaN in the pose or the vertex) counts as outside the image -- the patch is flagged caution
+ *   and the coordinate clamps to 0 like a negative one -- so box, texcoords and texcolors are finite and do not
+ *   depend on the vertex order (the reference's min / max fold keeps the extremum of the vertices
+ *   behind the last NaN, and converts floor(NaN) to int). */
 TF_API int tf_generate_patches(tf_volume* v, const int32_t* ids, int64_t n, const int32_t* labels,
                                uint64_t out_hot[2]);
 /* Chisel::CompensateColor()  Structure/Chisel.cpp:198-286 (+ computeMeanAndCov, Structure/Patch.cpp:342-348)

@@ -1103,10 +1103,13 @@ int tfo_patch_project(const float* verts, const float* colors, int64_t n_v, cons
     float x = vl[0] / vl[2], y = vl[1] / vl[2];
     float cX = (float)((double)(x * (float)fxi + (float)cxi) + 0.5); /* :55-56 */
     float cY = (float)((double)(y * (float)fyi + (float)cyi) + 0.5);
-    if (cX < 0 || cX >= (float)W || cY < 0 || cY >= (float)H) { flag = -1; ncau++; }
-    if (cX < 0) cX = 0;
+    /* :58-62.  A coordinate that is not a number is undefined in the reference (it passes every clamp, the box
+     * fold then depends on the vertex order, floor(NaN) -> int on the target); defined here, as on the device,
+     * as outside the image: caution, clamped to 0.  Identical for every other value. */
+    if (!(cX >= 0 && cX < (float)W && cY >= 0 && cY < (float)H)) { flag = -1; ncau++; }
+    if (!(cX >= 0)) cX = 0;
     if (cX >= (float)W) cX = (float)W;
-    if (cY < 0) cY = 0;
+    if (!(cY >= 0)) cY = 0;
     if (cY >= (float)H) cY = (float)H;
     texcoord[2 * i] = cX; texcoord[2 * i + 1] = cY;
     minX = minX < cX ? minX : cX; maxX = maxX > cX ? maxX : cX;

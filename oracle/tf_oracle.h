@@ -150,7 +150,9 @@ int tfo_atlas_patch_h(const tfo_atlas* a);
 int tfo_atlas_alloc(tfo_atlas* a, uint64_t* texloc);
 uint64_t tfo_atlas_loc_next(const tfo_atlas* a);
 uint8_t* tfo_atlas_buffer(tfo_atlas* a);
-/* Patch::CalculateTexCoords (Patch.cpp:40-108) */
+/* Patch::CalculateTexCoords (Patch.cpp:40-108).  Undefined in the reference, defined here and on the device: a read
+ * past the image's last pixel is 0; an image coordinate that is NaN counts as outside the image (caution, clamped
+ * to 0).  tests/patch_ref.py is an independent second statement of this function. */
 int tfo_patch_project(const float* verts, const float* colors, int64_t n_v, const float T[16],
                       const uint8_t* rgb, const float* depth, const tfo_camera* cam,
                       float* texcoord, float* texcolor, int32_t bbox[4], int* wrong_mapping,

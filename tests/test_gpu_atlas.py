@@ -3,7 +3,8 @@ DrawMeshes (Structure/Chisel.cpp:149-355), Atlas::AddPatch / UpdateBuffer (Struc
 Patch::CalculateTexCoords (Structure/Patch.cpp:40-108) -- against the oracle, on meshes both sides produced
 by marching cubes from the same integrated frames.  Everything integer (slots, boxes, flags, texels) and the
 per-vertex projections are compared bit for bit; colour compensation within the tolerance stated in
-tests/test_color_compensate.py."""
+tests/test_color_compensate.py.  The walls here are seen head-on: what CalculateTexCoords does at and beyond the
+image's borders (clamps, tap kinds, out-of-image reads, clipped boxes) is tests/test_gpu_patch_borders.py's."""
 import numpy as np
 import pytest
 

@@ -382,10 +382,13 @@ __device__ __forceinline__ void patch_body(const VolumeDev& v, const Cam& cam, c
           const float x = vl[0] / vl[2], y = vl[1] / vl[2];
           float a = (float)((double)(x * cam.fxi + cam.cxi) + 0.5);  // :55-56
           float b = (float)((double)(y * cam.fyi + cam.cyi) + 0.5);
-          cau[j] = (a < 0 || a >= Wf || b < 0 || b >= Hf);  // :58-62
-          if (a < 0) a = 0;
+          // :58-62.  Written so that a coordinate that is not a number (0 / 0 at the keyframe's centre, a NaN in the pose or
+          // the vertex: undefined in the reference) counts as outside the image and clamps to 0 -- behind the
+          // clamps every coordinate is finite, so the box fold below is order-free and the taps stay inside the image
+          cau[j] = !(a >= 0 && a < Wf && b >= 0 && b < Hf);
+          if (!(a >= 0)) a = 0;
           if (a >= Wf) a = Wf;
-          if (b < 0) b = 0;
+          if (!(b >= 0)) b = 0;
           if (b >= Hf) b = Hf;
           cX[j] = a; cY[j] = b;
           tp[j] = make_taps(W, H, a, b);
@@ -432,7 +435,7 @@ __device__ __forceinline__ void patch_body(const VolumeDev& v, const Cam& cam, c
           if (one_sweep) { keepX[j] = cX[j]; keepY[j] = cY[j]; }
         }
       }
-      // min / max are exact and order-free
+      // min / max are exact and order-free (no NaN gets here: see the clamps)
 #pragma unroll
       for (int o = 32; o >= 1; o >>= 1) {
         float q = __shfl_xor(minX, o); minX = q < minX ? q : minX;
