@@ -198,9 +198,11 @@ TF_API int tf_integrate(tf_volume* v, const float pose[12], const int32_t* ids, 
  *   the NEW keyframe group (`fresh`, may be NULL), flag 1;
  *   Chisel::UpdateMeshes over everything marked since the last CompressMeshes (:327);
  *   texture != 0: CompressMeshes, GeneratePatches with the new keyframe as the label of every chunk of chunksToUpdate,
- *     UpdateAtlas (:355-382; pose_inv16 = f32(SE3d.inverse().matrix()) of the new keyframe, Patch.cpp:51).  With
- *     texture == 0 the unit ends behind UpdateMeshes: the caller's tf_compress_meshes returns chunksToUpdate, its view
- *     selection (host code outside the path) runs, tf_generate_patches / tf_update_atlas take its labels.
+ *     UpdateAtlas (:355-382; pose_inv16 = f32(SE3d.inverse().matrix()) of the new keyframe, Patch.cpp:51).  That labelling
+ *     is a shortcut, not the reference's: the reference runs TexMap::view_selection between CompressMeshes and
+ *     GeneratePatches (:355-374).  With texture == 0 the unit ends behind UpdateMeshes: the caller's tf_compress_meshes
+ *     returns chunksToUpdate, the view selection runs on the device too (tf_view_select below; the host mirror's
+ *     TexMap::view_selection builds its problem), tf_generate_patches / tf_update_atlas take its labels.
  * Visible lists, needsUpdate / new flags, every keyframe's validChunks and Chunk::observations (tf_observations_*)
  * stay in HBM; nothing is copied back and the host does not wait.  All images are device pointers (depth f32 16-B
  * aligned; rgba u8[H][W][4] = valid ? (r, g, b, 1) : 0, MobileFusion.cpp:144-163; quality f32 or NULL) that must stay
@@ -254,6 +256,46 @@ TF_API int tf_export_datacost(tf_volume* v, const int32_t* ids, int64_t n, int32
                               const int32_t* frames_to_update, int32_t n_frames, float* out);
 TF_API int tf_export_adjacency(tf_volume* v, const int32_t* ids, int64_t n, int32_t* out_edges, int64_t cap_edges,
                                int64_t* n_edges);
+/* TexMap::view_selection's solve (Structure/TexMap.cpp:120-255; the chunksToUpdate overload :257-406 hands over its
+ * sub-problem): what the reference gives to mapMAP -- mgraph (:123-137), label_set (:139-155), unaries (:157-180), the
+ * Potts pairwise term (:159, :197), the warm start (:208-217) -- and solver.optimize (:199-225) itself.  The objective is
+ * mapMAP's (3rd_party/mapmap/source/tree_optimizer.impl.h:158-192, pairwise_potts.impl.h:121-134):
+ *   E(x) = sum_i costs_i[x_i] + edge_cost * sum over edges [label_i != label_j]     (edge_cost = adjacent_cost * pairwise_cost)
+ * The method is not mapMAP's, and no result of mapMAP is reproduced (it cannot be built here: DESIGN.md s.5): block-
+ * coordinate descent over the lattice lines of the chunk graph, each line solved exactly by dynamic programming with the
+ * rest held fixed, lines of one axis and one parity class in one launch; a round is the six (axis, class) phases; the
+ * solve ends after the first round that changes no label or after max_rounds.  The energy never rises from round to round.
+ * All f32 without contraction, ties to the same label and then to the lowest offset: the result is a function of the
+ * arguments alone, identical from run to run (tests/mrf_ref.py restates it in numpy).
+ *   n_nodes == 0 returns TF_OK and writes nothing.  A node has at most 512 labels (TF_ERR_CAPACITY beyond).
+ *   TF_ERR_INVALID (outputs unwritten, no line walked) for: an empty column / col_off not ascending from 0, labels of a
+ *   node not strictly ascending or negative, a cost that is not finite, an init offset outside the node's list, a nbr
+ *   entry that is not a node, nbr[nbr[i][k]][k ^ 1] != i, ids[nbr[i][k]] != ids[i] + d[k].  One launch in front of the
+ *   solve checks all of it; the host form reports the first offending node through tf_last_error.
+ * The solve is a pure function of its arguments: it reads and writes no chunk, mesh, atlas texel or observation; the
+ * handle supplies the stream and the scratch pool.
+ *   out_energy: f64 energies from a fixed-shape reduction, [0] the start labelling, [r] after round r, r <= *out_rounds;
+ *   entries behind *out_rounds are left unwritten. */
+TF_API int tf_view_select(tf_volume* v, int64_t n_nodes,
+    const int32_t* ids,          /* 3 per node: the chunk id */
+    const int32_t* nbr,          /* 6 per node, chisel::neighbourhood order: node index across that face, -1 = no edge */
+    const int64_t* col_off,      /* n_nodes + 1 */
+    const int32_t* labels,       /* nnz, strictly ascending within a node, >= 0 */
+    const float*   costs,        /* nnz */
+    float edge_cost, const int32_t* init_offsets /* n or NULL = argmin cost, lowest offset */,
+    int32_t max_rounds /* 0 = default (32) */,
+    int32_t* out_offsets /* n: index into the node's label list, as mapMAP's solution vector */,
+    double* out_energy /* NULL or max_rounds + 1: [0] initial, [r] after round r */, int32_t* out_rounds);
+/* The same with every array a device pointer (d_init_offsets may be d_out_offsets): enqueues on the handle's stream and
+ * does not synchronise.  nnz = col_off[n_nodes]: the host form reads it from its argument, this form cannot without
+ * waiting for the device, and its scratch is sized by it (a d_col_off that does not end at nnz is an invalid argument).
+ * It cannot return what only the device finds out: when the checking launch finds the arguments invalid (the list
+ * above; more than 512 labels) every later launch of the solve returns at once, and d_out_offsets, d_out_energy and
+ * d_out_rounds stay unwritten -- a caller that must tell presets d_out_rounds to -1. */
+TF_API int tf_view_select_device(tf_volume* v, int64_t n_nodes, const int32_t* d_ids, const int32_t* d_nbr,
+                                 const int64_t* d_col_off, int64_t nnz, const int32_t* d_labels, const float* d_costs,
+                                 float edge_cost, const int32_t* d_init_offsets, int32_t max_rounds, int32_t* d_out_offsets,
+                                 double* d_out_energy, int32_t* d_out_rounds);
 /* The local frames of a keyframe group in one visit per chunk (GCFusion/MobileFusion.cpp:187-203: after the keyframe's
  * own IntegrateDepthScanColor, its corresponding frames are integrated depth-only over the SAME chunk list, each with
  * its own pose).  Equivalent, bit for bit, to n_frames successive tf_integrate(use_color = 0) calls with these depth

@@ -49,7 +49,7 @@ SYMBOLS = (
     "tf_pre_refine_newframe", "tf_pre_refine_keyframe", "tf_pre_frame_depth", "tf_integrate_depth_group", "tf_integrate_depth_group_host",
     "tf_query_points", "tf_query_points_device", "tf_raycast", "tf_raycast_device", "tf_raycast_camera",
     "tf_distance_from_surface", "tf_distance_from_surface_device", "tf_refine_frame_in_voxel",
-    "tf_refine_frame_in_voxel_device",
+    "tf_refine_frame_in_voxel_device", "tf_view_select", "tf_view_select_device",
 )
 
 # tf_query_points want_mask bits
@@ -238,6 +238,9 @@ def lib():
     L.tf_distance_from_surface_device.argtypes = [vp, vp, C.c_int64, vp, vp]
     L.tf_refine_frame_in_voxel.argtypes = [vp, fp, fp, fp]
     L.tf_refine_frame_in_voxel_device.argtypes = [vp, vp, vp, fp]
+    L.tf_view_select.argtypes = [vp, C.c_int64, i32p, i32p, i64p, i32p, fp, C.c_float, i32p, C.c_int32, i32p,
+                                 C.POINTER(C.c_double), i32p]
+    L.tf_view_select_device.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_float, vp, C.c_int32, vp, vp, vp]
     _lib = L
     return L
 
@@ -625,6 +628,38 @@ class Volume:
     def refine_frame_device(self, d_depth, d_weight, pose):
         pose = _f32(pose).reshape(12)
         self._ck(self.L.tf_refine_frame_in_voxel_device(self.h, d_depth or None, d_weight or None, _p(pose, C.c_float)))
+
+    # -- view selection (the solve of TexMap::view_selection)
+    def view_select(self, ids, nbr, col_off, labels, costs, edge_cost=0.5, init=None, max_rounds=0, out=None):
+        """tf_view_select over a chunk graph: ids [n, 3], nbr [n, 6] (node index across each face of chisel::neighbourhood,
+        -1 = no edge), col_off [n + 1], labels / costs [nnz] -> (offsets [n] i32, rounds, energy trace f64[rounds + 1]).
+        out: (offsets, energy, rounds) arrays to write into instead of fresh ones (they keep their content on an error)."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1, 3)
+        n = len(ids)
+        nbr = np.ascontiguousarray(nbr, np.int32).reshape(-1, 6)
+        col_off = np.ascontiguousarray(col_off, np.int64).reshape(-1)
+        labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        costs = _f32(costs).reshape(-1)
+        if len(nbr) != n or len(col_off) != n + 1 or len(labels) != len(costs) or (n and len(labels) < col_off[n]):
+            raise TFError(TF_ERR_INVALID, "view_select: array lengths disagree")
+        init = None if init is None else np.ascontiguousarray(init, np.int32).reshape(-1)
+        if init is not None and len(init) != n:
+            raise TFError(TF_ERR_INVALID, "view_select: init needs one offset per node")
+        cap = (int(max_rounds) if max_rounds > 0 else 32) + 1
+        off, en, rounds = out if out is not None else (np.zeros(n, np.int32), np.zeros(cap, np.float64), np.zeros(1, np.int32))
+        self._ck(self.L.tf_view_select(self.h, n, _p(ids, C.c_int32), _p(nbr, C.c_int32), _p(col_off, C.c_int64),
+                                       _p(labels, C.c_int32), _p(costs, C.c_float), float(edge_cost), _p(init, C.c_int32),
+                                       int(max_rounds), _p(off, C.c_int32), _p(en, C.c_double), _p(rounds, C.c_int32)))
+        r = int(rounds[0]) if n else 0
+        return off, r, en[:r + 1] if n else en[:0]
+
+    def view_select_device(self, n, d_ids, d_nbr, d_col_off, nnz, d_labels, d_costs, edge_cost, d_init, max_rounds,
+                           d_out_offsets, d_out_energy, d_out_rounds):
+        """tf_view_select_device: every array a device pointer (d_init / d_out_energy may be 0); enqueues, does not wait."""
+        self._ck(self.L.tf_view_select_device(self.h, int(n), d_ids or None, d_nbr or None, d_col_off or None, int(nnz),
+                                              d_labels or None, d_costs or None, float(edge_cost), d_init or None,
+                                              int(max_rounds), d_out_offsets or None, d_out_energy or None,
+                                              d_out_rounds or None))
 
     # -- meshing (Chisel::UpdateMeshes / CompressMeshes, ChunkManager::allMeshes)
     def update_meshes(self):

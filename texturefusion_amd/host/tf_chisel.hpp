@@ -1188,10 +1188,24 @@ class Chisel {
 };
 typedef std::shared_ptr<Chisel> ChiselPtr;
 
-// Structure/TexMap.{h,cpp}: the bookkeeping of the view selection that consumes this path's outputs -- the chunk
-// graph from the meshes' adjacency flags (update_chunkgraph, TexMap.cpp:50-62) and the data costs from the
-// chunks' observation qualities (update_datacost, :64-105; check_graph, :107-119).  The MRF solve itself
-// (view_selection, mapMAP) is third-party host code outside the path and stays where it is.
+}  // namespace chisel
+
+// GCSLAM/MultiViewGeometry.h: of a keyframe's record TexMap::view_selection reads only the frame index its label stands for
+namespace MultiViewGeometry {
+struct KeyFrameDatabase {
+  int keyFrameIndex = 0;
+};
+}  // namespace MultiViewGeometry
+
+namespace chisel {
+
+// Structure/TexMap.{h,cpp}: the view selection that consumes this path's outputs -- the chunk graph from the meshes'
+// adjacency flags (update_chunkgraph, TexMap.cpp:50-62), the data costs from the chunks' observation qualities
+// (update_datacost, :64-105; check_graph, :107-119) and the MRF solve (view_selection, :120-255 and :257-406).  The
+// two overloads build the problem exactly as the reference builds it for mapMAP -- nodes, label sets, unaries, the
+// edges, the warm start -- and hand it to tf_view_select: the solve runs on the device, with the method described at its
+// declaration (include/tf_fusion.h), not with mapMAP's, so the labels are a labelling of the same energy and not mapMAP's
+// own (which cannot be built here).  `vol` is the handle whose stream the solve runs on; the *_device updates set it.
 class TexMap {
  public:
   float adjacent_cost = 0.5f;  // TexMap.h:53-54
@@ -1199,6 +1213,10 @@ class TexMap {
   UniGraph chunkGraph;
   DataCosts dataCost;
   std::vector<float> statistic;
+  std::vector<int> labelstorage;      // TexMap.h:66: the labels of the last full solve, the warm start of the next
+  tf_volume* vol = nullptr;
+  std::vector<double> energy_trace;   // of the last solve: [0] the start labelling, [r] after round r
+  std::vector<int> solved_labels;     // of the last solve: label (row + 1, 0 = none) per problem node
 
   void update_chunkgraph(ChunkIDList& chunksToUpdate, ChunkManager& chunkManager) {
     MeshMap& allMeshes = chunkManager.GetAllMutableMeshes();
@@ -1242,6 +1260,7 @@ class TexMap {
   // ---- the same two updates fed by the device's exports instead of the host mirrors (tf_export_adjacency /
   // tf_export_datacost: Mesh::adj and Chunk::observations stay in HBM, tf_observations_record / _retract keep the latter)
   int update_chunkgraph_device(ChunkIDList& chunksToUpdate, tf_volume* vol) {
+    this->vol = vol;
     for (const ChunkID& id : chunksToUpdate) chunkGraph.add_node(id);
     const int64_t n = (int64_t)chunksToUpdate.size();
     if (!n) return TF_OK;
@@ -1260,6 +1279,7 @@ class TexMap {
   }
   int update_datacost_device(ChunkIDList& chunksToUpdate, tf_volume* vol, std::vector<int>& lookup, int frameindex,
                              std::vector<int>& framesToUpdate) {
+    this->vol = vol;
     const int64_t n = (int64_t)chunksToUpdate.size();
     if (!n) return TF_OK;
     const std::size_t m = framesToUpdate.size();
@@ -1296,7 +1316,103 @@ class TexMap {
     }
   }
 
-  void clear() { chunkGraph.clear(); dataCost.clear(); statistic.clear(); }
+  // TexMap.cpp:120-255: every node of the graph; warm start from labelstorage, which is then cleared and refilled
+  void view_selection(const std::vector<MultiViewGeometry::KeyFrameDatabase>& kflist) {
+    std::vector<std::size_t> all(chunkGraph.num_nodes());
+    for (std::size_t i = 0; i < all.size(); ++i) all[i] = i;
+    solve(all, labelstorage.empty() ? nullptr : &labelstorage);
+    labelstorage.clear();
+    assign(all, kflist);
+    labelstorage = solved_labels;
+  }
+  // TexMap.cpp:257-406: the sub-problem over the chunks of chunksToUpdate that are nodes (`concerns`); edges to nodes
+  // outside it are dropped, there is no warm start, labelstorage is left alone
+  void view_selection(ChunkIDList& chunksToUpdate, const std::vector<MultiViewGeometry::KeyFrameDatabase>& kflist) {
+    std::vector<std::size_t> concerns;
+    for (const ChunkID& id : chunksToUpdate) {
+      auto it = chunkGraph.chunks.find(id);
+      if (it != chunkGraph.chunks.end()) concerns.push_back(it->second);
+    }
+    if (concerns.empty()) return;
+    solve(concerns, nullptr);
+    assign(concerns, kflist);
+  }
+
+  void clear() { chunkGraph.clear(); dataCost.clear(); statistic.clear(); labelstorage.clear(); }
+
+ private:
+  // The problem over `nodes` (problem node i = graph node nodes[i]) as the reference hands it to mapMAP, solved by
+  // tf_view_select -> solved_labels, energy_trace.
+  void solve(const std::vector<std::size_t>& nodes, const std::vector<int>* warm) {
+    if (!vol) throw std::runtime_error("TexMap::view_selection: no volume (set vol, or use the *_device updates)");
+    const std::size_t n = nodes.size();
+    std::vector<ChunkID> id_of(chunkGraph.num_nodes());
+    for (const auto& it : chunkGraph.chunks) id_of[it.second] = it.first;
+    std::vector<int64_t> local(chunkGraph.num_nodes(), -1);
+    for (std::size_t i = 0; i < n; ++i) local[nodes[i]] = (int64_t)i;
+    static const SparseMat::Column none;
+    auto column = [&](std::size_t k) -> const SparseMat::Column& { return k < dataCost.cols() ? dataCost.col(k) : none; };
+    std::vector<int32_t> ids(3 * n), nbr(6 * n, -1), labels, init;
+    std::vector<int64_t> col_off(n + 1, 0);
+    std::vector<float> costs;
+    for (std::size_t i = 0; i < n; ++i) {
+      const std::size_t k = nodes[i];
+      for (int a = 0; a < 3; ++a) ids[3 * i + a] = id_of[k](a);
+      const SparseMat::Column& col = column(k);
+      if (col.empty()) {  // :145-146, :165-166: the single label 0 at cost 1, no edges (:125)
+        labels.push_back(0);
+        costs.push_back(1.0f);
+      } else {
+        float column_max = col.begin()->second;  // :168-170
+        for (const auto& e : col) if (column_max < e.second) column_max = e.second;
+        for (const auto& e : col) {
+          labels.push_back((int32_t)static_cast<std::uint16_t>(e.first + 1));  // :150-151
+          costs.push_back(1.0f - e.second / column_max);                      // :173-174
+        }
+        for (std::size_t adj : chunkGraph.get_adj_nodes(k)) {  // :126-135 (each pair once = both directions of nbr)
+          if (local[adj] < 0 || column(adj).empty()) continue;
+          for (int f = 0; f < 6; ++f) {
+            static const int d[6][3] = {{-1, 0, 0}, {1, 0, 0}, {0, -1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}};
+            if (id_of[adj](0) == id_of[k](0) + d[f][0] && id_of[adj](1) == id_of[k](1) + d[f][1] &&
+                id_of[adj](2) == id_of[k](2) + d[f][2])
+              nbr[6 * i + f] = (int32_t)local[adj];
+          }
+        }
+      }
+      col_off[i + 1] = (int64_t)labels.size();
+    }
+    if (warm) {  // :208-217: a stored label that is no longer in the node's set, and every node added since: offset 0
+      init.assign(n, 0);
+      for (std::size_t i = 0; i < n && i < warm->size(); ++i)
+        for (int64_t j = col_off[i]; j < col_off[i + 1]; ++j)
+          if (labels[(std::size_t)j] == (*warm)[i]) init[i] = (int32_t)(j - col_off[i]);
+    }
+    std::vector<int32_t> off(n);
+    energy_trace.assign(33, 0.0);
+    int32_t rounds = 0;
+    tf_check(tf_view_select(vol, (int64_t)n, ids.data(), nbr.data(), col_off.data(), labels.data(), costs.data(),
+                            adjacent_cost * pairwise_cost, warm ? init.data() : nullptr, 0, off.data(), energy_trace.data(),
+                            &rounds),
+             "view_selection");
+    energy_trace.resize((std::size_t)rounds + 1);
+    solved_labels.resize(n);
+    for (std::size_t i = 0; i < n; ++i) solved_labels[i] = labels[(std::size_t)(col_off[i] + off[i])];
+  }
+  // :227-246 / :386-405: labels back to keyframe indices; label 0 keeps the node's label, or takes the keyframe before
+  // the newest when the node never had one
+  void assign(const std::vector<std::size_t>& nodes, const std::vector<MultiViewGeometry::KeyFrameDatabase>& kflist) {
+    for (std::size_t i = 0; i < nodes.size(); ++i) {
+      const int label = solved_labels[i];
+      if (label < 0 || (std::size_t)label > dataCost.rows() || (std::size_t)label > kflist.size())
+        throw std::runtime_error("Incorrect labeling");
+      if (label == 0) {
+        if (chunkGraph.get_label(nodes[i]) == 0 && kflist.size() >= 2)
+          chunkGraph.set_label(nodes[i], (std::size_t)kflist[kflist.size() - 2].keyFrameIndex);
+      } else {
+        chunkGraph.set_label(nodes[i], (std::size_t)kflist[(std::size_t)label - 1].keyFrameIndex);
+      }
+    }
+  }
 };
 typedef TexMap* TexPtr;
 
