@@ -200,9 +200,14 @@ TF_API int tf_integrate(tf_volume* v, const float pose[12], const int32_t* ids, 
  *   texture != 0: CompressMeshes, GeneratePatches with the new keyframe as the label of every chunk of chunksToUpdate,
  *     UpdateAtlas (:355-382; pose_inv16 = f32(SE3d.inverse().matrix()) of the new keyframe, Patch.cpp:51).  That labelling
  *     is a shortcut, not the reference's: the reference runs TexMap::view_selection between CompressMeshes and
- *     GeneratePatches (:355-374).  With texture == 0 the unit ends behind UpdateMeshes: the caller's tf_compress_meshes
- *     returns chunksToUpdate, the view selection runs on the device too (tf_view_select below; the host mirror's
- *     TexMap::view_selection builds its problem), tf_generate_patches / tf_update_atlas take its labels.
+ *     GeneratePatches (:355-374).  With texture == 0 the unit ends behind UpdateMeshes and the reference's tail follows
+ *     with the TexMap resident on the device (tf_texmap_* below): tf_compress_meshes returns chunksToUpdate,
+ *     tf_texmap_update / tf_texmap_check_graph / tf_texmap_view_selection keep the chunk graph and the data costs in
+ *     HBM, assemble the problem there and assign the solved labels there, tf_generate_patches_selected reads them
+ *     there, tf_update_atlas ends the keyframe -- or all of it as ONE call with one host wait, tf_texture_tail_device.
+ *     (The host-built path stays: tf_export_* + the host mirror's
+ *     TexMap::view_selection + tf_view_select + tf_generate_patches.)  When the resident map exists the unit's
+ *     RetractObservations also removes the moved keyframes' data-cost entries (MobileFusion.cpp:261-267).
  * Visible lists, needsUpdate / new flags, every keyframe's validChunks and Chunk::observations (tf_observations_*)
  * stay in HBM; nothing is copied back and the host does not wait.  All images are device pointers (depth f32 16-B
  * aligned; rgba u8[H][W][4] = valid ? (r, g, b, 1) : 0, MobileFusion.cpp:144-163; quality f32 or NULL) that must stay
@@ -296,6 +301,89 @@ TF_API int tf_view_select_device(tf_volume* v, int64_t n_nodes, const int32_t* d
                                  const int64_t* d_col_off, int64_t nnz, const int32_t* d_labels, const float* d_costs,
                                  float edge_cost, const int32_t* d_init_offsets, int32_t max_rounds, int32_t* d_out_offsets,
                                  double* d_out_energy, int32_t* d_out_rounds);
+/* ---- TexMap resident on the device (Structure/TexMap.{h,cpp}; tf_texmap.hip) -------------------------------------
+ * chunkGraph (UniGraph: nodes, edges, labels), dataCost (SparseMat columns) and labelstorage live in HBM per pool slot,
+ * allocated by the first tf_texmap_* call (a handle that never makes one keeps its footprint) and freed by
+ * tf_volume_reset / tf_volume_destroy.  The reference's `statistic` vector is written and never read
+ * (TexMap.cpp:71-75,95) and is not kept.  Every call is asynchronous on the handle's stream unless it says otherwise.
+ * tf_texmap_set_keyframes   the kflist of this call: row r <-> kflist[r].keyFrameIndex on the device; its inverse
+ *                           frameIndexToKeyframeDB (GCFusion/MobileFusion.cpp:293-296) is kept on the host, where it
+ *                           checks the frames an update names (the device keys its costs by frame index).  1 <= n_rows <= 65534 (labels
+ *                           are cast to uint16_t, TexMap.cpp:150-151); frame indices >= 0 and distinct.
+ * tf_texmap_update          TexMap::update_chunkgraph then update_datacost (TexMap.cpp:50-105) for chunksToUpdate: every
+ *                           listed chunk becomes a node (uni_graph.cpp:22-28); then for every listed chunk that owns a
+ *                           mesh and every set Mesh::adj flag whose face neighbour is a node the edge is set on both
+ *                           ends (uni_graph.cpp:41-49; edges persist until remove_node); observations[frame_index] > 0
+ *                           is inserted only where the column has no entry for it (SparseMat::add_value,
+ *                           sparse_matrix.cpp:27-36), observations[f] > 0 overwrites for each f of frames_to_update
+ *                           (set_value, :38-43), an absent observation removes the entry (:45-50).  The result does not
+ *                           depend on the order of ids.  TF_ERR_INVALID for a frame outside the keyframe table.
+ * tf_texmap_retract         the data-cost half of MobileFusion::RetractObservations (MobileFusion.cpp:261-267): the entry
+ *                           (chunk, keyframe_id) of the listed chunks that exist is removed (a chunk that is no node has
+ *                           no column).  tf_keyframe_unit_device does this for its moved keyframes by itself.
+ * tf_texmap_remove_wrong_mapping   MobileFusion.cpp:330-342: every mesh in the map whose patch has wrong_mapping loses
+ *                           the entry (chunk, patch->frameid); a chunk that is no node is skipped (the reference
+ *                           dereferences chunks.find() unchecked).  *n_removed = entries that were there.
+ * tf_texmap_check_graph     TexMap::check_graph (TexMap.cpp:107-118): nodes whose mesh has left allMeshes lose their
+ *                           edges, on both ends (uni_graph.cpp:89-107), and their column (sparse_matrix.h:67-70); they
+ *                           stay nodes.  *n_removed = such nodes.  (n_removed != NULL waits for the count, in both calls.)
+ * tf_texmap_view_selection  TexMap::view_selection.  ids == NULL: the full overload (TexMap.cpp:120-255) over every node,
+ *                           warm start from the stored labels once a full solve has run (a node without a stored label,
+ *                           or whose stored label has left its column, starts at offset 0), the stored labels replaced
+ *                           afterwards.  ids != NULL: the sub-problem overload (:257-406) over the listed chunks that
+ *                           are nodes; edges to nodes outside it are dropped, cold start, stored labels left alone.
+ *                           The problem is assembled on the device as the host mirror's TexMap::solve assembles it
+ *                           (labels row + 1 ascending, costs 1.0f - q / column_max in f32, an empty column = the single
+ *                           label 0 at cost 1.0f without edges, an edge needs both ends in the problem with non-empty
+ *                           columns, edge_cost = 0.5f * 1.0f), solved by tf_view_select_device's launches, and the
+ *                           labels are assigned on the device (:227-246): label 0 keeps the chunk's label, or takes
+ *                           key_frame_index[n_rows - 2] when the chunk has none and n_rows >= 2; otherwise
+ *                           key_frame_index[label - 1].  The host waits ONCE, for the fixed-size control block
+ *                           {n_nodes, nnz} that sizes the solver's scratch; no per-chunk data crosses.  max_rounds: 0 =
+ *                           32, at most 4096.  out_rounds != NULL (and out_energy, max_rounds + 1 doubles, as in
+ *                           tf_view_select) waits for the solve as well; all three outputs may be NULL.
+ * tf_texmap_download        mirrors of the listed chunks: is_node, edges (bit k = face k of chisel::neighbourhood),
+ *                           label (UniGraph::labels), stored (labelstorage entry, -1 = none at the last full solve) and
+ *                           the column as (frame index, quality) pairs in ascending row, packed by col_off[n + 1].
+ *                           Any output may be NULL.  Synchronises.
+ * tf_texmap_download_problem   the problem assembled last, in tf_view_select's layout (node order = the builder's), with
+ *                           the start offsets (-1 each = cold start) and the solved offsets.  Synchronises.
+ * tf_texmap_clear           TexMap::clear (TexMap.cpp:408-412), the stored labels included as in the host mirror's; the keyframe table stays. */
+TF_API int tf_texmap_set_keyframes(tf_volume* v, const int32_t* key_frame_index, int32_t n_rows);
+TF_API int tf_texmap_update(tf_volume* v, const int32_t* ids, int64_t n, int32_t frame_index, const int32_t* frames_to_update,
+                            int32_t n_frames);
+TF_API int tf_texmap_retract(tf_volume* v, int32_t keyframe_id, const int32_t* ids, int64_t n);
+TF_API int tf_texmap_remove_wrong_mapping(tf_volume* v, int64_t* n_removed);
+TF_API int tf_texmap_check_graph(tf_volume* v, int64_t* n_removed);
+TF_API int tf_texmap_view_selection(tf_volume* v, const int32_t* ids, int64_t n, int32_t max_rounds, double* out_energy,
+                                    int32_t* out_rounds, int64_t* out_n_nodes);
+TF_API int tf_texmap_download(tf_volume* v, const int32_t* ids, int64_t n, uint8_t* is_node, uint8_t* edges, int32_t* label,
+                              int32_t* stored, int64_t* col_off, int32_t* col_frame, float* col_q, int64_t cap_entries);
+TF_API int tf_texmap_download_problem(tf_volume* v, int64_t cap_nodes, int64_t cap_nnz, int64_t* n_nodes, int64_t* nnz,
+                                      int32_t* ids, int32_t* nbr, int64_t* col_off, int32_t* labels, float* costs,
+                                      int32_t* init_offsets, int32_t* offsets);
+TF_API int tf_texmap_clear(tf_volume* v);
+/* MobileFusion::tsdfFusion's tail (GCFusion/MobileFusion.cpp:330-382) in ONE call, behind tf_keyframe_unit_device(texture = 0)
+ *   or tf_update_meshes: the wrong-mapping removal (:330-342; TF_TAIL_WRONG_MAPPING = the caller's integrateKeyframeIndex > 3),
+ *   chunksToUpdate (:345-353), CompressMeshes (:355), update_chunkgraph + update_datacost (:356-359), check_graph (:360-361;
+ *   TF_TAIL_CHECK_GRAPH = keyframesToUpdate is not empty), view_selection (:362-369; the full overload, or with
+ *   TF_TAIL_SUB_PROBLEM the chunksToUpdate overload), GeneratePatches with the labels just assigned (:374) and UpdateAtlas
+ *   (:382).  chunksToUpdate never leaves the device: the dirty keys that own a mesh are ranked into ascending chunk id there
+ *   (the order the path defines for Atlas::AddPatch) and every stage reads that list.  The host waits ONCE, for the control
+ *   block of the solve (which also brings the list's length); nothing else is read back -- an atlas overflow or a label
+ *   without a cached keyframe stays in the status word and is reported by the next synchronising call (TF_ERR_ATLAS_FULL /
+ *   TF_ERR_INVALID).  Chisel::CompensateColor (:380) is NOT part of the tail: it waits for the host's eigen-solves; it reads
+ *   what GeneratePatches wrote and nothing UpdateAtlas writes, so tf_compensate_color behind the tail equals the reference's
+ *   order.  Chunk ids must lie within +-2^20 per axis (the range of the chunk hash's packed key).
+ * tf_texture_tail_list   chunksToUpdate of the last tail, for the caller's DrawMeshes bookkeeping: *n = its length (known
+ *   since the tail's wait: out_ids == NULL asks for nothing else and does not synchronise), out_ids = the list in
+ *   ascending chunk id (synchronises). */
+#define TF_TAIL_WRONG_MAPPING 1u
+#define TF_TAIL_CHECK_GRAPH 2u
+#define TF_TAIL_SUB_PROBLEM 4u
+TF_API int tf_texture_tail_device(tf_volume* v, int32_t frame_index, const int32_t* frames_to_update, int32_t n_frames,
+                                  uint32_t flags, int32_t max_rounds);
+TF_API int tf_texture_tail_list(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n);
 /* The local frames of a keyframe group in one visit per chunk (GCFusion/MobileFusion.cpp:187-203: after the keyframe's
  * own IntegrateDepthScanColor, its corresponding frames are integrated depth-only over the SAME chunk list, each with
  * its own pose).  Equivalent, bit for bit, to n_frames successive tf_integrate(use_color = 0) calls with these depth
@@ -680,6 +768,13 @@ TF_API int tf_meshes_upload(tf_volume* v, const int32_t* ids, int64_t n, const i
  *   behind the last NaN, and converts floor(NaN) to int). */
 TF_API int tf_generate_patches(tf_volume* v, const int32_t* ids, int64_t n, const int32_t* labels,
                                uint64_t out_hot[2]);
+/* Chisel::GeneratePatches with labelset = the resident chunk graph (Structure/Chisel.cpp:156-182, tf_texmap_* above): the
+ *   keyframe of entry i is its chunk's resident label, looked up on the device in the keyframe cache (what
+ *   tf_generate_patches does on the host per label).  A listed chunk with a mesh that is no node, or whose label names no
+ *   cached keyframe: TF_ERR_INVALID; that entry and everything behind it in the list stays unprocessed, as for a full
+ *   atlas.  tf_compensate_color reads what this call wrote and nothing tf_update_atlas writes, so calling it behind
+ *   tf_update_atlas equals the reference's order (MobileFusion.cpp:374-382). */
+TF_API int tf_generate_patches_selected(tf_volume* v, const int32_t* ids, int64_t n, uint64_t out_hot[2]);
 /* Chisel::CompensateColor()  Structure/Chisel.cpp:198-286 (+ computeMeanAndCov, Structure/Patch.cpp:342-348)
  *   over every mesh with a patch, in ascending chunk-id order (the reference iterates an unordered_map).
  *   Patches with has_adjusted are skipped; the rest is clustered by frame id (cluster order = first

@@ -50,6 +50,9 @@ SYMBOLS = (
     "tf_query_points", "tf_query_points_device", "tf_raycast", "tf_raycast_device", "tf_raycast_camera",
     "tf_distance_from_surface", "tf_distance_from_surface_device", "tf_refine_frame_in_voxel",
     "tf_refine_frame_in_voxel_device", "tf_view_select", "tf_view_select_device",
+    "tf_texmap_set_keyframes", "tf_texmap_update", "tf_texmap_retract", "tf_texmap_remove_wrong_mapping",
+    "tf_texmap_check_graph", "tf_texmap_view_selection", "tf_texmap_download", "tf_texmap_download_problem",
+    "tf_texmap_clear", "tf_generate_patches_selected", "tf_texture_tail_device", "tf_texture_tail_list",
 )
 
 # tf_query_points want_mask bits
@@ -241,6 +244,18 @@ def lib():
     L.tf_view_select.argtypes = [vp, C.c_int64, i32p, i32p, i64p, i32p, fp, C.c_float, i32p, C.c_int32, i32p,
                                  C.POINTER(C.c_double), i32p]
     L.tf_view_select_device.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_float, vp, C.c_int32, vp, vp, vp]
+    L.tf_texmap_set_keyframes.argtypes = [vp, i32p, C.c_int32]
+    L.tf_texmap_update.argtypes = [vp, i32p, C.c_int64, C.c_int32, i32p, C.c_int32]
+    L.tf_texmap_retract.argtypes = [vp, C.c_int32, i32p, C.c_int64]
+    L.tf_texmap_remove_wrong_mapping.argtypes = [vp, i64p]
+    L.tf_texmap_check_graph.argtypes = [vp, i64p]
+    L.tf_texmap_view_selection.argtypes = [vp, i32p, C.c_int64, C.c_int32, C.POINTER(C.c_double), i32p, i64p]
+    L.tf_texmap_download.argtypes = [vp, i32p, C.c_int64, u8p, u8p, i32p, i32p, i64p, i32p, fp, C.c_int64]
+    L.tf_texmap_download_problem.argtypes = [vp, C.c_int64, C.c_int64, i64p, i64p, i32p, i32p, i64p, i32p, fp, i32p, i32p]
+    L.tf_texmap_clear.argtypes = [vp]
+    L.tf_generate_patches_selected.argtypes = [vp, i32p, C.c_int64, u64p]
+    L.tf_texture_tail_device.argtypes = [vp, C.c_int32, i32p, C.c_int32, C.c_uint32, C.c_int32]
+    L.tf_texture_tail_list.argtypes = [vp, i32p, C.c_int64, i64p]
     _lib = L
     return L
 
@@ -794,6 +809,111 @@ class Volume:
         n = C.c_int64(0)
         self._ck(self.L.tf_export_adjacency(self.h, _p(ids, C.c_int32), len(ids), _p(out, C.c_int32), len(out), C.byref(n)))
         return out[:n.value]
+
+    # -- TexMap resident on the device (tf_texmap_*)
+    def texmap_set_keyframes(self, key_frame_index):
+        kf = np.ascontiguousarray(key_frame_index, np.int32).reshape(-1)
+        self._ck(self.L.tf_texmap_set_keyframes(self.h, _p(kf, C.c_int32), len(kf)))
+
+    def texmap_update(self, ids, frame_index, frames_to_update=()):
+        """TexMap::update_chunkgraph + update_datacost for chunksToUpdate"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1, 3)
+        fr = np.ascontiguousarray(frames_to_update, np.int32).reshape(-1)
+        self._ck(self.L.tf_texmap_update(self.h, _p(ids, C.c_int32), len(ids), int(frame_index),
+                                         _p(fr, C.c_int32) if len(fr) else None, len(fr)))
+
+    def texmap_retract(self, keyframe_id, ids):
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1, 3)
+        self._ck(self.L.tf_texmap_retract(self.h, int(keyframe_id), _p(ids, C.c_int32), len(ids)))
+
+    def texmap_remove_wrong_mapping(self):
+        n = C.c_int64(0)
+        self._ck(self.L.tf_texmap_remove_wrong_mapping(self.h, C.byref(n)))
+        return n.value
+
+    def texmap_check_graph(self):
+        n = C.c_int64(0)
+        self._ck(self.L.tf_texmap_check_graph(self.h, C.byref(n)))
+        return n.value
+
+    def texmap_view_selection(self, ids=None, max_rounds=0, wait=True):
+        """TexMap::view_selection: the full overload (ids None) or the sub-problem over ids -> (n_nodes, rounds, trace);
+        wait=False enqueues only and returns (n_nodes, None, None)"""
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int32).reshape(-1, 3)
+        nn, r = C.c_int64(0), C.c_int32(0)
+        en = np.zeros((max_rounds or 32) + 1, np.float64)
+        self._ck(self.L.tf_texmap_view_selection(self.h, _p(ids, C.c_int32), 0 if ids is None else len(ids), int(max_rounds),
+                                                 _p(en, C.c_double) if wait else None, C.byref(r) if wait else None,
+                                                 C.byref(nn)))
+        if not wait:
+            return nn.value, None, None
+        return nn.value, r.value, (en[:r.value + 1].copy() if nn.value else en[:0].copy())
+
+    def texmap_download(self, ids):
+        """-> dict(is_node u8[n], edges u8[n] (bit k = face k), label i32[n], stored i32[n] (-1 = none), col_off i64[n + 1],
+        col_frame i32[m], col_q f32[m])"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1, 3)
+        n = len(ids)
+        out = dict(is_node=np.zeros(n, np.uint8), edges=np.zeros(n, np.uint8), label=np.zeros(n, np.int32),
+                   stored=np.zeros(n, np.int32), col_off=np.zeros(n + 1, np.int64))
+        # first the lengths, then the columns
+        self._ck(self.L.tf_texmap_download(self.h, _p(ids, C.c_int32), n, _p(out["is_node"], C.c_uint8), _p(out["edges"], C.c_uint8),
+                                           _p(out["label"], C.c_int32), _p(out["stored"], C.c_int32), _p(out["col_off"], C.c_int64),
+                                           None, None, 0))
+        m = int(out["col_off"][-1])
+        out["col_frame"], out["col_q"] = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.float32)
+        if m:
+            self._ck(self.L.tf_texmap_download(self.h, _p(ids, C.c_int32), n, None, None, None, None, None,
+                                               _p(out["col_frame"], C.c_int32), _p(out["col_q"], C.c_float), m))
+        out["col_frame"], out["col_q"] = out["col_frame"][:m], out["col_q"][:m]
+        return out
+
+    def texmap_problem(self):
+        """the problem assembled last -> dict(ids, nbr, col_off, labels, costs, init (-1 = cold), offsets)"""
+        n, z = C.c_int64(0), C.c_int64(0)
+        rc = self.L.tf_texmap_download_problem(self.h, 0, 0, C.byref(n), C.byref(z), None, None, None, None, None, None, None)
+        if rc not in (TF_OK, TF_ERR_CAPACITY):
+            self._ck(rc)
+        nn, nz = n.value, z.value
+        out = dict(ids=np.zeros((nn, 3), np.int32), nbr=np.zeros((nn, 6), np.int32), col_off=np.zeros(nn + 1, np.int64),
+                   labels=np.zeros(nz, np.int32), costs=np.zeros(nz, np.float32), init=np.zeros(nn, np.int32),
+                   offsets=np.zeros(nn, np.int32))
+        if nn:
+            self._ck(self.L.tf_texmap_download_problem(
+                self.h, nn, nz, C.byref(n), C.byref(z), _p(out["ids"], C.c_int32), _p(out["nbr"], C.c_int32),
+                _p(out["col_off"], C.c_int64), _p(out["labels"], C.c_int32), _p(out["costs"], C.c_float),
+                _p(out["init"], C.c_int32), _p(out["offsets"], C.c_int32)))
+        return out
+
+    def texmap_clear(self):
+        self._ck(self.L.tf_texmap_clear(self.h))
+
+    def generate_patches_selected(self, ids):
+        """Chisel::GeneratePatches with the resident chunk graph as labelset -> (rc, (hot_start, hot_end))"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1, 3)
+        hot = np.zeros(2, np.uint64)
+        rc = self.L.tf_generate_patches_selected(self.h, _p(ids, C.c_int32), len(ids), _p(hot, C.c_uint64))
+        if rc != TF_ERR_ATLAS_FULL:
+            self._ck(rc)
+        return rc, (int(hot[0]), int(hot[1]))
+
+    def texture_tail(self, frame_index, frames_to_update=(), wrong_mapping=True, check_graph=False, sub_problem=False,
+                     max_rounds=0):
+        """tf_texture_tail_device: tsdfFusion's tail in one call (one host wait)"""
+        fr = np.ascontiguousarray(frames_to_update, np.int32).reshape(-1)
+        flags = (1 if wrong_mapping else 0) | (2 if check_graph else 0) | (4 if sub_problem else 0)
+        self._ck(self.L.tf_texture_tail_device(self.h, int(frame_index), _p(fr, C.c_int32) if len(fr) else None, len(fr), flags,
+                                               int(max_rounds)))
+
+    def texture_tail_list(self):
+        """chunksToUpdate of the last tail, ascending chunk id"""
+        n = C.c_int64(0)
+        self._ck(self.L.tf_texture_tail_list(self.h, None, 0, C.byref(n)))
+        ids = np.zeros((max(n.value, 1), 3), np.int32)
+        if n.value:
+            self._ck(self.L.tf_texture_tail_list(self.h, _p(ids, C.c_int32), n.value, C.byref(n)))
+        return ids[:n.value]
 
     def profile_calibrate(self, n_pairs=200):
         """microseconds a HIP-event pair around an empty launch reads (the floor inside every profile_get time)"""

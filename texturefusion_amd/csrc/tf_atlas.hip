@@ -871,6 +871,74 @@ int tf_generate_patches(tf_volume* v, const int32_t* ids, int64_t n, const int32
   return rc;  // TF_ERR_ATLAS_FULL = GeneratePatches' -1 (Chisel.cpp:170-173)
 }
 
+// Chisel::GeneratePatches with labelset = the resident chunk graph (Chisel.cpp:156-182): tf_generate_patches with the
+// keyframe of every entry looked up on the device (its chunk's label in the keyframe table) instead of handed over.
+int tf_generate_patches_selected(tf_volume* v, const int32_t* ids, int64_t n, uint64_t out_hot[2]) {
+  if (!v || (n > 0 && !ids)) { set_error("null argument"); return TF_ERR_INVALID; }
+  TF_DEV(v);
+  AtlasState& a = v->atlas;
+  if (out_hot) {  // Chisel.cpp:153-154,184-186 with an empty loop
+    const uint64_t ls = (uint64_t)a.aw * (uint64_t)a.ah;
+    out_hot[0] = (ls / a.aw) * a.aw;
+    out_hot[1] = (0 / a.aw + a.ph) * a.aw;
+  }
+  if (n <= 0) return TF_OK;
+  if (!v->tm.node) { set_error("texmap: no resident chunk graph (tf_texmap_update)"); return TF_ERR_INVALID; }
+  const size_t o_ctl = ((size_t)n * 16 + 16 + 63) & ~(size_t)63;
+  const size_t o_ff = o_ctl + ((sizeof(AtlasCtl) + 63) & ~(size_t)63);  // device half: the first entry the label lookup refused
+  int rc = reserve(v, a.stage, o_ff + 64, o_ff + 64);
+  if (rc) return rc;
+  rc = upload_work(v, ids, nullptr, n);
+  if (rc) return rc;
+  a.fused_armed = false;
+  hipLaunchKernelGGL(k_work_lookup, dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, v->stream, v->dev, (uint32_t)n);
+  launch_tm_work_labels(v, (uint32_t)n, reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(a.stage.d) + o_ff));
+  hipLaunchKernelGGL(k_patch_assign, dim3(1), dim3(1024), 0, v->stream, v->dev, (uint32_t)n);
+  prof_begin(v, TF_PROF_PATCH_PROJECT);
+  hipLaunchKernelGGL((k_patch<true, false, false>), dim3(1024), dim3(256), 0, v->stream, v->dev, v->cam, 0, KfDev{});
+  prof_end(v);
+  TF_HIP(hipGetLastError());
+  AtlasCtl* hc = reinterpret_cast<AtlasCtl*>(reinterpret_cast<uint8_t*>(a.stage.h) + o_ctl);
+  TF_HIP(hipMemcpyAsync(hc, a.d_actl, sizeof(AtlasCtl), hipMemcpyDeviceToHost, v->stream));
+  rc = sync_status(v, nullptr);
+  const AtlasCtl c = *hc;
+  if (out_hot && c.n_done > 0) {  // Chisel.cpp:184-186
+    out_hot[0] = (c.loc_min / (uint64_t)a.aw) * (uint64_t)a.aw;
+    out_hot[1] = (c.loc_max / (uint64_t)a.aw + a.ph) * (uint64_t)a.aw;
+  }
+  return rc;
+}
+
+}  // extern "C"
+
+// tf_generate_patches_selected + tf_update_atlas over a list that is already on the device, without their waits: an atlas
+// overflow or a refused label stays in the status word for the next synchronising call
+int tf::patch_stage_device(tf_volume* v, const int4* d_list, uint32_t n, uint32_t* d_first_fail) {
+  AtlasState& a = v->atlas;
+  if (!n) return TF_OK;
+  if (n > v->dev.max_chunks) { set_error("chunk list longer than tf_config.max_chunks"); return TF_ERR_CAPACITY; }
+  TF_HIP(hipMemcpyAsync(a.d_work_ids, d_list, (size_t)n * 16, hipMemcpyDeviceToDevice, v->stream));
+  a.fused_armed = false;
+  hipLaunchKernelGGL(k_work_lookup, dim3((n + 255u) / 256u), dim3(256), 0, v->stream, v->dev, n);
+  launch_tm_work_labels(v, n, d_first_fail);
+  hipLaunchKernelGGL(k_patch_assign, dim3(1), dim3(1024), 0, v->stream, v->dev, n);
+  prof_begin(v, TF_PROF_PATCH_PROJECT);
+  hipLaunchKernelGGL((k_patch<true, false, false>), dim3(1024), dim3(256), 0, v->stream, v->dev, v->cam, 0, KfDev{});
+  prof_end(v);
+  // UpdateAtlas over the same list (the lookup again: the assignment took refused entries out of the stage)
+  hipLaunchKernelGGL(k_work_lookup, dim3((n + 255u) / 256u), dim3(256), 0, v->stream, v->dev, n);
+  prof_begin(v, TF_PROF_ATLAS_BLIT);
+  {
+    AtlasWriteScope aw(v, INT32_MIN);
+    hipLaunchKernelGGL((k_patch<false, true, false>), dim3(1024), dim3(256), 0, v->stream, v->dev, v->cam, 0, KfDev{});
+  }
+  prof_end(v);
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+
+extern "C" {
+
 int tf_update_atlas(tf_volume* v, const int32_t* ids, int64_t n) {
   if (!v || (n > 0 && !ids)) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);

@@ -187,8 +187,10 @@ static int status_to_error(uint32_t st) {
   if (st & kStMeshFull) m += " the mesh store is exhausted: no block left for a chunk's first mesh (raise tf_config.mesh_blocks) or for a mesh beyond mesh_max_vertices / mesh_max_triangles (raise tf_config.mesh_overflow_blocks or those)";
   if (st & kStAtlasFull) m += " No enough space for texture storage.";  // std::overflow_error text, Atlas.cpp:53
   if (st & kStXchgFull) m += " a rank's ghost band did not fit the boundary exchange block (raise cap_records)";
+  if (st & kStInvalid) m += " a listed chunk is no node of the resident chunk graph, or its label names no cached keyframe";
   set_error(m);
   if (st & kStAtlasFull) return TF_ERR_ATLAS_FULL;
+  if (st & kStInvalid) return TF_ERR_INVALID;
   if (st & kStMissing) return TF_ERR_MISSING_CHUNK;
   return TF_ERR_CAPACITY;
 }
@@ -520,6 +522,7 @@ int tf_volume_destroy(tf_volume* v) {
   tf_keyframe_unit_release(v);
   prof_collect(v);
   for (hipEvent_t e : v->prof_pool) hipEventDestroy(e);
+  texmap_release(v);
   atlas_destroy(v);
   comm_destroy(v);
   for (void* p : v->allocs) hipFree(p);
@@ -566,6 +569,8 @@ int tf_volume_reset(tf_volume* v) {
   TF_DEV(v);
   int rc = tf_keyframe_unit_release(v);  // Frame::validChunks of the keyframes integrated so far
   if (rc) return rc;
+  TF_HIP(hipStreamSynchronize(v->stream));
+  texmap_release(v);  // TexMap::clear, and its storage given back
   rc = init_device_state(v);
   if (rc) return rc;
   return atlas_reset(v);

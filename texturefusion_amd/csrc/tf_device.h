@@ -33,6 +33,7 @@ constexpr uint32_t kStHashFull = 16u;
 constexpr uint32_t kStMeshFull = 32u;   // a mesh exceeds tf_config.mesh_max_vertices / mesh_max_triangles
 constexpr uint32_t kStAtlasFull = 64u;
 constexpr uint32_t kStXchgFull = 128u;  // a rank's ghost band did not fit the exchange block (raise cap_records)  // Atlas::AddPatch overflow (std::overflow_error, Atlas.cpp:52-53)
+constexpr uint32_t kStInvalid = 256u;   // a work entry the call cannot process (tf_generate_patches_selected: no node / label without a cached keyframe)
 
 struct Cam {
   int W, H;
@@ -198,6 +199,38 @@ struct AtlasCtl {
   } set[2];
 };
 
+// TexMap (Structure/TexMap.h: chunkGraph, dataCost, labelstorage) resident per pool slot (tf_texmap.hip; tf_volume::tm).  Every pointer is
+// null until the first tf_texmap_* call: a handle that never uses the map allocates nothing for it.  Pool slots never move
+// and hash entries are never removed, so a slot names the same chunk id for the life of the volume.
+constexpr uint32_t kTmNode = 1u;         // node word: the chunk is a node of chunkGraph (UniGraph::chunks)
+constexpr int kTmEdgeShift = 1;          // bits 1..6: an edge across face k of chisel::neighbourhood (UniGraph::adj_lists)
+constexpr uint32_t kTmEdges = 0x7Eu;
+constexpr uint32_t kTmTmp = 0x200u;      // scratch bit of the sub-problem's collection (a chunk listed twice is one node)
+constexpr uint32_t kTmHadLabel = 0x80u;  // the node had an entry of labelstorage at the last full solve (i < labelstorage.size())
+struct TexMapCtl {
+  uint32_t solved;       // a full solve has run (!labelstorage.empty()): the next full solve starts from the stored labels
+  uint32_t n_nodes;      // nodes of the problem being assembled
+  unsigned long long nnz;  // its labels
+  uint32_t n_removed;    // what the last check_graph / wrong-mapping pass removed
+  uint32_t n_list;       // tf_texture_tail_device: entries of chunksToUpdate as the device sorted it
+  uint32_t first_fail;   // patch stage behind the tail: the first work entry the label lookup refused (~0: none)
+  uint32_t pad;
+};
+struct TexMapDev {
+  uint32_t* node;     // [max_chunks] node word
+  int32_t* label;     // [max_chunks] UniGraph::labels: a keyframe index, 0 = none
+  int32_t* stored;    // [max_chunks] labelstorage[i]: row + 1, or 0
+  uint32_t* idx;      // [max_chunks] index of the slot's node in the problem assembled last (valid where prob_slot[idx] == slot)
+  // dataCost: open addressing like the observation table, key = (pool slot << 32 | keyframe frame index) -> quality; a
+  // removed entry keeps its key with quality 0
+  unsigned long long* key;  // [mask + 1], kEmptyKey = free
+  float* q;
+  uint32_t mask;
+  int32_t n_rows;         // kflist.size() of the last tf_texmap_set_keyframes
+  const int32_t* kf_row;  // [n_rows] kflist[r].keyFrameIndex
+  TexMapCtl* ctl;
+};
+
 constexpr uint32_t kMeshShards = 32;  // survivor rows are appended shard by shard: 32 counters instead of one
 constexpr uint32_t kMeshCntWords = kMeshShards * 48;  // VolumeDev::mesh_cnt per launch parity: row counters, statistics, deferred-reset counters
 constexpr int kPhaseWaves = 16384;  // rows of the wave-timeline table (tuning aid)
@@ -292,6 +325,12 @@ struct VolumeDev {
   uint32_t* xl_ent;  // [2][max_chunks]
   uint32_t xl_par;
   SelBuf sel;  // the selection set the launch works on
+};
+// What the kernels of the resident TexMap (and k_kf_load of the keyframe unit) take: the volume and the map next to it.  The
+// map's words are NOT members of VolumeDev itself: that struct is an argument of every kernel of the path, and the frame
+// kernel's register budget (tests/test_kernel_resources.py) does not survive a longer argument block.
+struct TmDev : VolumeDev {
+  TexMapDev tm;  // all null until first use
 };
 // planes of the mesh stored in block `blk` (MeshRec::block; only dereferenced for a mesh with vertices, i.e. blk != kBlkNone)
 __host__ __device__ inline float* mesh_plane(const VolumeDev& v, uint32_t blk, int plane) {

@@ -1585,6 +1585,32 @@ int tf_compress_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n_o
   return TF_OK;
 }
 
+}  // extern "C"
+
+// tf_compress_meshes without its host half (tf_texture_tail_device): the list stays on the device, unsorted
+int tf::compress_device_list(tf_volume* v, int4* d_out, uint32_t cap_out, uint32_t* d_count, uint32_t* bound) {
+  int rc = TF_OK;
+  const bool have_list = v->dirty_list_seq + 1 == v->call_seq && v->scratch.d;
+  if (!have_list) { rc = dirty_list_enqueue(v); if (rc) return rc; }
+  const bool known_n = have_list && v->dirty_list_n != ~0u;
+  const uint32_t cap_list = v->dev.max_chunks;
+  *bound = known_n ? v->dirty_list_n : cap_list;
+  uint8_t* db = reinterpret_cast<uint8_t*>(v->scratch.d);
+  const int4* list = reinterpret_cast<const int4*>(db + 16);
+  const uint32_t* cnt = reinterpret_cast<const uint32_t*>(db);
+  launch_compress(v->dev, list, cnt, cap_list, true, v->stream);
+  TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
+  const uint32_t grid = known_n ? (v->dirty_list_n + 255u) / 256u : 1024u;
+  hipLaunchKernelGGL(k_dirty_with_mesh, dim3(grid ? grid : 1u), dim3(256), 0, v->stream, v->dev, list, cnt, cap_list, d_out, cap_out);
+  TF_HIP(hipGetLastError());
+  TF_HIP(hipMemcpyAsync(d_count, &v->dev.vctl->n_tmp, 4, hipMemcpyDeviceToDevice, v->stream));
+  v->dirty_list_seq = ~0ull;
+  v->clear_floor = v->epoch;  // chunksToUpdate.clear() (Chisel.cpp:146), as tf_clear_dirty
+  return TF_OK;
+}
+
+extern "C" {
+
 int tf_check_summaries(tf_volume* v, int64_t* n_chunks, int64_t* n_missing, int64_t* n_stale) {
   if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
   TF_DEV(v);

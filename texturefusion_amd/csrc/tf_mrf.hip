@@ -25,14 +25,15 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "tf_mrf.h"
 #include "tf_volume.h"
 
 namespace tf {
 namespace {
 
 constexpr int kMaxLabels = 512;      // labels of one node (the previous node's row of the table lives in LDS)
-constexpr int kEnergyBlocks = 256;   // shape of the energy reduction: fixed, whatever n is
-constexpr int kDefaultRounds = 32;
+constexpr int kEnergyBlocks = kMrfEnergyBlocks;
+constexpr int kDefaultRounds = kMrfDefaultRounds;
 constexpr int kPhaseBlocks = 4096;   // waves of a phase launch (they stride over the phase's line heads)
 constexpr int kHostBatch = 4;        // host form: rounds enqueued between two looks at the control block
 constexpr int kChoiceLds = 8192;     // line arrays: back pointers of a line kept in LDS when its table has at most this many entries
@@ -46,38 +47,6 @@ enum : uint32_t {
   kBadIds = 6,       // ids[nbr[i][k]] != ids[i] + d[k]
   kBadCost = 7,      // cost not finite
   kBadTooMany = 8,   // more than kMaxLabels labels
-};
-
-struct MrfCtl {
-  unsigned long long bad;  // min over the offending nodes of (node << 4 | code); ~0: the arguments are consistent
-  int32_t done;            // a round changed nothing: every later launch of the solve returns at once
-  int32_t changed;         // a line of the running round was rewritten
-  uint32_t n_heads[6];     // [2 * axis + class]
-  uint32_t top[3];         // line arrays: entries of order[axis] handed out
-  int32_t pad[3];
-};
-static_assert(sizeof(MrfCtl) == 64, "MrfCtl");
-
-struct MrfArgs {
-  int32_t n;
-  int64_t nnz;
-  const int32_t* ids;
-  const int32_t* nbr;
-  const int64_t* col_off;
-  const int32_t* labels;
-  const float* costs;
-  const int32_t* init;  // or null
-  float w;
-  int32_t* off;         // the labelling, as offsets (= out_offsets)
-  double* energy;       // or null
-  int32_t* rounds;
-  MrfCtl* ctl;
-  int32_t* cur;         // [n] label of every node under `off`
-  int32_t* choice;      // [nnz] the table's back pointers
-  int32_t* heads;       // [3][n] line heads of axis a: class 0 from the front, class 1 from the back
-  double* partial;      // [kEnergyBlocks]
-  int32_t* order;       // line arrays: [3][n] the nodes of axis a in line order, or null = walk the +a pointers
-  int4* line;           // [3][n] per head slot: {start in order[a], nodes, labels of all its nodes (saturated), 0}
 };
 
 __device__ __forceinline__ bool mrf_live(const MrfCtl* c) { return c->bad == ~0ull && !c->done; }
@@ -414,38 +383,14 @@ int mrf_check(tf_volume* v, int64_t n, const void* ids, const void* nbr, const v
   return TF_OK;
 }
 
+}  // namespace
+
 // TF_MRF_WALK=pointers: walk the lines through the nodes' +a pointers instead of the line arrays (tools/view_selection_time.py
 // measures both; DESIGN.md s.7d has the numbers the default rests on).  Both give the same bytes.
 bool mrf_line_arrays() {
   const char* e = getenv("TF_MRF_WALK");
   return !(e && strcmp(e, "pointers") == 0);
 }
-
-struct MrfScratch {
-  size_t ctl, cur, choice, heads, partial, order = 0, line = 0;
-  bool arrays = false;
-  void take(Layout& L, int64_t n, int64_t nnz) {
-    arrays = mrf_line_arrays();
-    ctl = L.take(sizeof(MrfCtl));
-    cur = L.take(4 * (size_t)n);
-    choice = L.take(4 * (size_t)nnz);
-    heads = L.take(12 * (size_t)n);
-    partial = L.take(8 * (size_t)kEnergyBlocks);
-    if (arrays) {
-      order = L.take(12 * (size_t)n);
-      line = L.take(48 * (size_t)n);
-    }
-  }
-  void bind(MrfArgs& a, uint8_t* d) const {
-    a.ctl = reinterpret_cast<MrfCtl*>(d + ctl);
-    a.cur = reinterpret_cast<int32_t*>(d + cur);
-    a.choice = reinterpret_cast<int32_t*>(d + choice);
-    a.heads = reinterpret_cast<int32_t*>(d + heads);
-    a.partial = reinterpret_cast<double*>(d + partial);
-    a.order = arrays ? reinterpret_cast<int32_t*>(d + order) : nullptr;
-    a.line = arrays ? reinterpret_cast<int4*>(d + line) : nullptr;
-  }
-};
 
 int mrf_enqueue_start(tf_volume* v, const MrfArgs& a) {
   hipStream_t s = v->stream;
@@ -495,7 +440,6 @@ int mrf_bad_to_error(unsigned long long bad) {
   return code == kBadTooMany ? TF_ERR_CAPACITY : TF_ERR_INVALID;
 }
 
-}  // namespace
 }  // namespace tf
 
 using namespace tf;

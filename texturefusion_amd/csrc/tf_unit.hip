@@ -54,7 +54,7 @@ __global__ __launch_bounds__(1024) void k_kf_store(VolumeDev v, KfStoreArgs a) {
 // slots resolved like tf_integrate does for a caller's list (a missing chunk is an error: chunks.at() throws)
 // ... and MobileFusion::RetractObservations' chunk side over the same entries: observations.erase(frame_id)
 __global__ __launch_bounds__(256) void k_kf_load(VolumeDev v, const KfTab* tab, uint32_t slots, const int4* arena, int slot,
-                                                 int32_t kf_id) {
+                                                 int32_t kf_id, TexMapDev tm) {
   const SelBuf& L = v.sel;
   uint32_t n = kf_off(tab)[slots + slot];
   if (n > v.max_list) { n = 0; if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&v.vctl->status, kStListFull); }
@@ -80,6 +80,17 @@ __global__ __launch_bounds__(256) void k_kf_load(VolumeDev v, const KfTab* tab, 
       if (cur == key) { v.obs_q[i] = 0.0f; break; }
       if (cur == kEmptyKey) break;
       i = (i + 1) & v.obs_mask;
+    }
+    // ... and its data-cost side (MobileFusion.cpp:261-267: dataCost.remove_observation(node, keyframe row)) when the
+    // TexMap is resident (tf_texmap.hip); a handle without one has a null table here
+    if (tm.key) {
+      i = hash_key(key) & tm.mask;
+      for (uint32_t probe = 0; probe <= tm.mask; ++probe) {
+        const unsigned long long cur = tm.key[i];
+        if (cur == key) { tm.q[i] = 0.0f; break; }
+        if (cur == kEmptyKey) break;
+        i = (i + 1) & tm.mask;
+      }
     }
   }
 }
@@ -185,7 +196,7 @@ static int integrate_group(tf_volume* v, UnitState* u, const tf_unit_group* g, i
     launch_bbox(d, img.depth, v->cam, P, fs);
     launch_select(d, img.depth, v->cam, v->ig, P, v->res, /*emit=*/true, fs, /*plain=*/true);
   } else {
-    hipLaunchKernelGGL(k_kf_load, dim3(256), dim3(256), 0, s, d, u->tab, u->slots, u->arena, kf_slot, g->kf_id);
+    hipLaunchKernelGGL(k_kf_load, dim3(256), dim3(256), 0, s, d, u->tab, u->slots, u->arena, kf_slot, g->kf_id, v->tm);
   }
   // the per-chunk records and centroid tables of all the group's frames in ONE launch (k_pre + k_pre_group were two)
   const float* dd[kGroupFrames];

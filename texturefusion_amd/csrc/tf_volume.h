@@ -152,6 +152,27 @@ struct AtlasState {
   Scratch stage;  // the atlas entry points' own pool (they leave tf_volume::scratch alone)
 };
 
+// Host side of the resident TexMap (tf_volume::tm, tf_texmap.hip): what the host has to know without asking the device.
+struct TexMapState {
+  std::vector<int32_t> kf_row;       // kflist[r].keyFrameIndex of the last tf_texmap_set_keyframes
+  std::vector<int32_t> kf_inv;       // frame index -> row, -1 = none (frameIndexToKeyframeDB, MobileFusion.cpp:293-296)
+  int32_t* d_kf_row = nullptr;       // device copy of kf_row
+  size_t kf_cap = 0;
+  int32_t* h_kf = nullptr;           // pinned staging of the upload, and the event behind it
+  hipEvent_t kf_ev = nullptr;
+  int64_t nodes_bound = 0;           // chunks ever handed to tf_texmap_update: an upper bound of the node count
+  // the problem assembled last: per-node arrays (pn, room for pn_cap nodes) and per-label arrays (pz, room for pz_cap labels)
+  void* pn = nullptr;
+  void* pz = nullptr;
+  size_t pn_cap = 0, pz_cap = 0;
+  int64_t n = 0, nnz = 0;            // its size
+  TexMapCtl* h_ctl = nullptr;        // pinned: the control block as read back
+  // tf_texture_tail_device: chunksToUpdate as a device list (raw = as the dirty set gave it, ctu = ascending chunk id)
+  int4* d_ctu_raw = nullptr;
+  int4* d_ctu = nullptr;
+  int64_t ctu_n = 0;                 // its length, known since the tail's one wait
+};
+
 // RCCL communicator of the handle (tf_comm_init) and the exchange buffers
 struct CommState {
   void* comm = nullptr;  // ncclComm_t
@@ -281,6 +302,8 @@ struct tf_volume {
   tf_profile prof_acc{};
   tf::AtlasState atlas;
   tf::CommState comm;
+  tf::TexMapDev tm{};   // TexMap resident on the device: null pointers until the first tf_texmap_* call
+  tf::TexMapState tmx;
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
   // band counts of a frame's selection as the host sees them: pinned words [0] tag (frame epoch + 1), [1..4] FrameCtl::band_cnt
   uint32_t* h_xchg = nullptr;
@@ -353,6 +376,23 @@ int boundary_pack_block_on(tf_volume* v, void* d_block, int64_t cap_records, hip
 int boundary_pack_bands2_on(tf_volume* v, void* d_block_down, int64_t cap_down, void* d_block_up, int64_t cap_up, hipStream_t s);
 void comm_destroy(tf_volume* v);
 int kf_push(tf_volume* v, int slot);
+// the volume and the map as the map's kernels take them
+inline TmDev tm_dev(const tf_volume* v) {
+  TmDev d;
+  static_cast<VolumeDev&>(d) = v->dev;
+  d.tm = v->tm;
+  return d;
+}
+void texmap_release(tf_volume* v);  // frees the resident TexMap (tf_texmap.hip); the handle is back at its footprint without one
+// work entries [first offending entry, n) of the patch work list out of the stage: an entry with a mesh whose chunk is no node of
+// the resident graph or whose label names no cached keyframe (tf_generate_patches_selected); w of the others = keyframe-table entry
+void launch_tm_work_labels(tf_volume* v, uint32_t n, uint32_t* d_first_fail);
+// tf_texture_tail_device's pieces outside tf_texmap.hip.  compress_device_list (tf_mesh.hip): CompressMeshes over the dirty set,
+// the dirty keys that own a mesh appended to d_out (order free), their count copied to *d_count, the dirty set cleared;
+// *bound = what the host knows about the count.  patch_stage_device (tf_atlas.hip): GeneratePatches with the resident labels
+// and UpdateAtlas over a device list of n entries, nothing read back.
+int compress_device_list(tf_volume* v, int4* d_out, uint32_t cap_out, uint32_t* d_count, uint32_t* bound);
+int patch_stage_device(tf_volume* v, const int4* d_list, uint32_t n, uint32_t* d_first_fail);
 void launch_patch_fused(tf_volume* v, const VolumeDev& d, int par, const KfDev& kf, hipStream_t s);
 inline uint64_t host_pack_id(const int32_t id[3]) {
   return ((uint64_t)((uint32_t)(id[0] + (1 << 20)) & 0x1FFFFFu) << 42) |

@@ -1033,6 +1033,43 @@ class Chisel {
     return rc == TF_ERR_ATLAS_FULL ? -1 : 0;  // Chisel.cpp:170-173
   }
 
+  // The same with labelset = the chunk graph RESIDENT on the device (TexMap::*_resident, tf_texmap_*): the patch stage
+  // looks every chunk's label up there (tf_generate_patches_selected).  The labels are read back here for one purpose
+  // only -- the keyframes they name must be cached in HBM with their current poses before the stage runs; a caller that
+  // caches its keyframes as it fuses them (tf_keyframe_cache_device / tf_keyframe_set_pose) can call the entry point itself.
+  int GeneratePatches(ChunkIDList& chunksToUpdate, std::vector<Frame>& frame_list, PinholeCamera& cameraModel) {
+    ProjectionIntegrator dummy;
+    Configure(dummy, cameraModel, false);
+    const size_t n = chunksToUpdate.size();
+    std::vector<int32_t> ids(n * 3 + 3), labels(n + 1);
+    std::vector<uint8_t> is_node(n + 1);
+    for (size_t i = 0; i < n; ++i)
+      for (int a = 0; a < 3; ++a) ids[3 * i + a] = chunksToUpdate[i](a);
+    tf_check(tf_texmap_download(vol, ids.data(), (int64_t)n, is_node.data(), nullptr, labels.data(), nullptr, nullptr, nullptr,
+                                nullptr, 0), "GeneratePatches: labels");
+    for (size_t i = 0; i < n; ++i) {
+      const int frameid = labels[i];
+      if (!is_node[i] || frameid < 0 || (size_t)frameid >= frame_list.size()) continue;  // (the stage reports it)
+      Frame& f = frame_list[(size_t)frameid];
+      if (!cached_kf.count(frameid) || cached_kf[frameid] != f.rgb) {
+        tf_check(tf_keyframe_cache(vol, frameid, f.rgb, f.refined_depth), "GeneratePatches: keyframe");
+        cached_kf[frameid] = f.rgb;
+      }
+      if (!pose_set.count(frameid) || std::memcmp(pose_set[frameid].data(), f.pose_inv, 64) != 0) {
+        tf_check(tf_keyframe_set_pose(vol, frameid, f.pose_inv), "GeneratePatches: pose");
+        pose_set[frameid].assign(f.pose_inv, f.pose_inv + 16);
+      }
+    }
+    uint64_t hot[2] = {0, 0};
+    const int rc = tf_generate_patches_selected(vol, ids.data(), (int64_t)n, hot);
+    if (rc != TF_ERR_ATLAS_FULL) tf_check(rc, "GeneratePatches");
+    RefreshPatches(ids, n);
+    atlas.hot_start = hot[0];
+    atlas.hot_end = hot[1];
+    atlas.Refresh();
+    return rc == TF_ERR_ATLAS_FULL ? -1 : 0;  // Chisel.cpp:170-173
+  }
+
   // Structure/Chisel.cpp:198-286
   void CompensateColor() {
     int64_t ncl = 0;
@@ -1307,6 +1344,68 @@ class TexMap {
     return TF_OK;
   }
 
+  // ---- the same bookkeeping RESIDENT on the device (tf_texmap_*, include/tf_fusion.h): thin calls; chunkGraph, dataCost
+  // and labelstorage of this object are not touched -- the graph, the columns and the stored labels live in HBM per pool
+  // slot, the problem is assembled there and the labels are assigned there.  A caller uses either this family or the
+  // host-built one above for the life of a map, not both.  set_keyframes_resident hands over the kflist of the call
+  // (row <-> keyFrameIndex, what `lookup` is on the host); update_chunkgraph_resident + update_datacost_resident are ONE
+  // device call, issued by the latter.
+  int set_keyframes_resident(tf_volume* vol, const std::vector<MultiViewGeometry::KeyFrameDatabase>& kflist) {
+    this->vol = vol;
+    std::vector<int32_t> rows(kflist.size());
+    for (std::size_t r = 0; r < kflist.size(); ++r) rows[r] = kflist[r].keyFrameIndex;
+    return tf_texmap_set_keyframes(vol, rows.data(), (int32_t)rows.size());
+  }
+  int update_chunkgraph_resident(ChunkIDList& chunksToUpdate, tf_volume* vol) {
+    this->vol = vol;
+    (void)chunksToUpdate;  // nodes and edges are set by the update call below, nodes first (TexMap.cpp:53-60)
+    return TF_OK;
+  }
+  int update_datacost_resident(ChunkIDList& chunksToUpdate, tf_volume* vol, int frameindex, std::vector<int>& framesToUpdate) {
+    this->vol = vol;
+    const int64_t n = (int64_t)chunksToUpdate.size();
+    std::vector<int32_t> ids((std::size_t)n * 3), fr(framesToUpdate.begin(), framesToUpdate.end());
+    for (int64_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) ids[(std::size_t)(3 * i + a)] = chunksToUpdate[(std::size_t)i](a);
+    return tf_texmap_update(vol, ids.data(), n, frameindex, fr.empty() ? nullptr : fr.data(), (int32_t)fr.size());
+  }
+  int check_graph_resident(int64_t* n_removed = nullptr) { return tf_texmap_check_graph(vol, n_removed); }
+  // the full overload (TexMap.cpp:120-255): energy_trace is filled, solved_labels is not (the labels stay in HBM)
+  int view_selection_resident() { return select_resident(nullptr, 0); }
+  // the chunksToUpdate overload (:257-406)
+  int view_selection_resident(ChunkIDList& chunksToUpdate) {
+    const int64_t n = (int64_t)chunksToUpdate.size();
+    std::vector<int32_t> ids((std::size_t)n * 3 + 3);
+    for (int64_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) ids[(std::size_t)(3 * i + a)] = chunksToUpdate[(std::size_t)i](a);
+    return select_resident(ids.data(), n);
+  }
+  // UniGraph::get_label of listed chunks, from the device (0 for a chunk that is no node)
+  int labels_resident(ChunkIDList& chunks, std::vector<int32_t>& out) {
+    const int64_t n = (int64_t)chunks.size();
+    std::vector<int32_t> ids((std::size_t)n * 3 + 3);
+    for (int64_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) ids[(std::size_t)(3 * i + a)] = chunks[(std::size_t)i](a);
+    out.assign((std::size_t)n, 0);
+    return tf_texmap_download(vol, ids.data(), n, nullptr, nullptr, out.data(), nullptr, nullptr, nullptr, nullptr, 0);
+  }
+  int clear_resident() { return vol ? tf_texmap_clear(vol) : TF_OK; }
+  // MobileFusion.cpp:330-382 without CompensateColor as ONE device call with one host wait (tf_texture_tail_device): the
+  // wrong-mapping removal when integrateKeyframeIndex > 3, chunksToUpdate, CompressMeshes, the two updates, check_graph when
+  // keyframes moved, view_selection, GeneratePatches, UpdateAtlas.  chunksToUpdate comes back for DrawMeshes' bookkeeping.
+  // The keyframes the labels can name must be cached (tf_keyframe_cache_device / tf_keyframe_set_pose) before the call.
+  int texture_tail_resident(tf_volume* vol, int integrateKeyframeIndex, std::vector<int>& keyframesToUpdate, ChunkIDList& chunksToUpdate) {
+    this->vol = vol;
+    std::vector<int32_t> fr(keyframesToUpdate.begin(), keyframesToUpdate.end());
+    const uint32_t flags = (integrateKeyframeIndex > 3 ? TF_TAIL_WRONG_MAPPING : 0u) | (fr.empty() ? 0u : TF_TAIL_CHECK_GRAPH);
+    int rc = tf_texture_tail_device(vol, integrateKeyframeIndex, fr.empty() ? nullptr : fr.data(), (int32_t)fr.size(), flags, 0);
+    if (rc) return rc;
+    int64_t n = 0;
+    if ((rc = tf_texture_tail_list(vol, nullptr, 0, &n))) return rc;
+    std::vector<int32_t> ids((std::size_t)n * 3 + 3);
+    if ((rc = tf_texture_tail_list(vol, ids.data(), n, &n))) return rc;
+    chunksToUpdate.clear();
+    for (int64_t i = 0; i < n; ++i) chunksToUpdate.emplace_back(ids[3 * (std::size_t)i], ids[3 * (std::size_t)i + 1], ids[3 * (std::size_t)i + 2]);
+    return TF_OK;
+  }
+
   void check_graph(ChunkManager& chunkManager) {  // nodes whose mesh is gone lose their edges and costs
     const MeshMap& allMeshes = chunkManager.GetAllMeshes();
     for (const auto& it : chunkGraph.chunks) {
@@ -1341,6 +1440,15 @@ class TexMap {
   void clear() { chunkGraph.clear(); dataCost.clear(); statistic.clear(); labelstorage.clear(); }
 
  private:
+  int select_resident(const int32_t* ids, int64_t n) {
+    if (!vol) throw std::runtime_error("TexMap::view_selection_resident: no volume");
+    energy_trace.assign(33, 0.0);
+    int32_t rounds = 0;
+    int64_t nodes = 0;
+    const int rc = tf_texmap_view_selection(vol, ids, n, 0, energy_trace.data(), &rounds, &nodes);
+    energy_trace.resize(rc == TF_OK && nodes > 0 ? (std::size_t)rounds + 1 : 0);
+    return rc;
+  }
   // The problem over `nodes` (problem node i = graph node nodes[i]) as the reference hands it to mapMAP, solved by
   // tf_view_select -> solved_labels, energy_trace.
   void solve(const std::vector<std::size_t>& nodes, const std::vector<int>* warm) {
