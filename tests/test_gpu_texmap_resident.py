@@ -230,6 +230,51 @@ def test_sub_problem_overload(gpu_required):
         gv.close()
 
 
+def test_problem_arrays_and_keyframe_table_grow(gpu_required):
+    """The two growth paths of the map's own buffers, each crossed once with the map compared against the host model
+    behind it (as _check_map / _check_problem do, tolerance 0).
+
+    Problem arrays: their capacity follows the length of the list handed to the sub-problem overload (a power of two of at
+    least 1024), so with no solve before, 600 ids give room for 1024 nodes and 1 500 ids make it grow to 2048.  No
+    chunksToUpdate of the sequence is that long (589, 468, 200, 1429, 1283, 1394 ids), so the list is every node of the
+    graph after the first step that leaves at least 1 500 of them (keyframe 12: 1 678).
+
+    Keyframe table: 2 rows, then 200 rows -- past the first table of 256 words, which keeps 64 behind its rows -- then an
+    update that names keyframes to update and a full solve whose column walk covers four blocks of 64 rows."""
+    gv = _volume()
+    run = I.Run(gv)
+    try:
+        for i in range(len(I.STEPS)):
+            o = run.step(i, select="none")
+            nodes = np.array(sorted(run.tm.chunkGraph.chunks), np.int32)
+            if len(nodes) >= 1500:
+                break
+        assert len(nodes) >= 1500, len(nodes)
+        for m in (600, 1500):
+            what = "sub-problem over %d ids" % m
+            run.tm.view_selection_sub(nodes[:m], run.kflist)
+            g = gv.texmap_view_selection(nodes[:m])
+            assert g[0] == m, (what, g[0])  # (all distinct nodes: the second problem does not fit the first capacity)
+            _check_problem(run, gv, g, what)
+            _check_map(run, gv, what)
+        gv.texmap_set_keyframes(run.kflist[:2])
+        run.kflist += list(range(1000, 1000 + 200 - len(run.kflist)))
+        assert len(run.kflist) == 200
+        gv.texmap_set_keyframes(run.kflist)
+        to_update = [k for k, _, _ in I.STEPS[:i]][:2]
+        assert len(to_update) == 2
+        run.tm.update_chunkgraph(o["ids"], lambda c: run.ov.get_mesh(c)["adj"])
+        run.tm.update_datacost(o["ids"], lambda c: run.ov.observations(c), run.lookup(), o["kf"], to_update)
+        gv.texmap_update(o["ids"], o["kf"], to_update)
+        run.tm.view_selection(run.kflist)
+        g = gv.texmap_view_selection()
+        _check_problem(run, gv, g, "200 rows")
+        assert _check_map(run, gv, "200 rows") == len(nodes)
+    finally:
+        run.close()
+        gv.close()
+
+
 def _snapshot(v):
     st = v.stats()
     ids = sorted_ids(v.list_chunks())

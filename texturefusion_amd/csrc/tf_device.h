@@ -214,7 +214,7 @@ struct TexMapCtl {
   uint32_t n_removed;    // what the last check_graph / wrong-mapping pass removed
   uint32_t n_list;       // tf_texture_tail_device: entries of chunksToUpdate as the device sorted it
   uint32_t first_fail;   // patch stage behind the tail: the first work entry the label lookup refused (~0: none)
-  uint32_t pad;
+  uint32_t n_raw;        // tf_texture_tail_device: entries of chunksToUpdate as the dirty set gave it (unsorted, not yet capped)
 };
 struct TexMapDev {
   uint32_t* node;     // [max_chunks] node word

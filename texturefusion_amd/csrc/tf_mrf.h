@@ -1,6 +1,8 @@
 // tf_mrf.h -- what the view-selection solve (tf_mrf.hip) shares with the code that assembles its problem on the device
-// (tf_texmap.hip): the argument block of its kernels, its scratch layout and the two functions that put it on the stream.
+// (tf_texmap.hip): the argument block of its kernels, its scratch layout, how it is put on the stream and read back.
 #pragma once
+
+#include <stddef.h>
 
 #include "tf_volume.h"
 
@@ -70,6 +72,18 @@ struct MrfScratch {
   }
 };
 
+struct MrfResult {     // what a solve's caller reads back, in pinned memory
+  int32_t rounds[4];  // [0]: rounds run, -1 = the checking launch refused the problem
+  MrfCtl ctl;
+  double energy[1];   // [R + 1], of which [0 .. rounds] are written
+  static size_t bytes(int R) { return offsetof(MrfResult, energy) + 8 * (size_t)(R + 1); }
+};
+// Every solve starts here.  `a` comes with the problem (n .. rounds, device pointers); the solver's scratch is laid out behind
+// the first `at` bytes of the handle's pool (the caller's), the pool's device half reserved, the scratch members of `a`
+// bound and the start put on the stream (mrf_enqueue_start).
+int mrf_begin(tf_volume* v, MrfArgs& a, size_t at);
+// the result of a solve of at most R rounds into h (pinned, MrfResult::bytes(R)); waits; MrfCtl::bad -> mrf_bad_to_error
+int mrf_read_back(tf_volume* v, const MrfArgs& a, int R, MrfResult* h);
 // the checking launch, the start labelling, the line arrays and the energy of round 0
 int mrf_enqueue_start(tf_volume* v, const MrfArgs& a);
 // rounds r0 .. r1 (1-based, inclusive); every launch is a no-op once the solve has ended

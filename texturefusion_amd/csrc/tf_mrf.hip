@@ -392,6 +392,24 @@ bool mrf_line_arrays() {
   return !(e && strcmp(e, "pointers") == 0);
 }
 
+int mrf_begin(tf_volume* v, MrfArgs& a, size_t at) {
+  Layout L{at};
+  MrfScratch sc;
+  sc.take(L, a.n, a.nnz);
+  if (int rc = reserve(v, v->scratch, L.size, 0)) return rc;
+  sc.bind(a, reinterpret_cast<uint8_t*>(v->scratch.d));
+  return mrf_enqueue_start(v, a);
+}
+
+int mrf_read_back(tf_volume* v, const MrfArgs& a, int R, MrfResult* h) {
+  hipStream_t s = v->stream;
+  TF_HIP(hipMemcpyAsync(h->rounds, a.rounds, sizeof(h->rounds), hipMemcpyDeviceToHost, s));
+  TF_HIP(hipMemcpyAsync(&h->ctl, a.ctl, sizeof(MrfCtl), hipMemcpyDeviceToHost, s));
+  TF_HIP(hipMemcpyAsync(h->energy, a.energy, 8 * (size_t)(R + 1), hipMemcpyDeviceToHost, s));
+  TF_HIP(hipStreamSynchronize(s));
+  return h->ctl.bad != ~0ull ? mrf_bad_to_error(h->ctl.bad) : TF_OK;
+}
+
 int mrf_enqueue_start(tf_volume* v, const MrfArgs& a) {
   hipStream_t s = v->stream;
   TF_HIP(hipMemsetAsync(a.ctl, 0, sizeof(MrfCtl), s));
@@ -455,16 +473,11 @@ int tf_view_select_device(tf_volume* v, int64_t n_nodes, const int32_t* d_ids, c
   if (n_nodes && nnz < n_nodes) { set_error("view selection: nnz < n_nodes (a column would be empty)"); return TF_ERR_INVALID; }
   TF_DEV(v);
   if (n_nodes == 0) return TF_OK;
-  Layout L;
-  MrfScratch sc;
-  sc.take(L, n_nodes, nnz);
-  if ((rc = reserve(v, v->scratch, L.size, 0))) return rc;
   MrfArgs a{};
   a.n = (int32_t)n_nodes; a.nnz = nnz; a.ids = d_ids; a.nbr = d_nbr; a.col_off = d_col_off; a.labels = d_labels;
   a.costs = d_costs; a.init = d_init_offsets; a.w = edge_cost; a.off = d_out_offsets; a.energy = d_out_energy;
   a.rounds = d_out_rounds;
-  sc.bind(a, reinterpret_cast<uint8_t*>(v->scratch.d));
-  if ((rc = mrf_enqueue_start(v, a))) return rc;
+  if ((rc = mrf_begin(v, a, 0))) return rc;
   return mrf_enqueue_rounds(v, a, 1, max_rounds ? max_rounds : kDefaultRounds);
 }
 
@@ -482,43 +495,40 @@ int tf_view_select(tf_volume* v, int64_t n_nodes, const int32_t* ids, const int3
       return mrf_bad_to_error(((unsigned long long)i << 4) | kBadColumn);
   const int64_t nnz = col_off[n];
   const int R = max_rounds ? max_rounds : kDefaultRounds;
-  // staging: rounds | ctl copy | offsets | energy trace || ids | nbr | col_off | labels | costs | init || device scratch
+  // staging: rounds, ctl copy, energy trace (MrfResult) | offsets || ids | nbr | col_off | labels | costs | init || device scratch
   Layout L;
-  const size_t o_r = L.take(16), o_c = L.take(sizeof(MrfCtl)), o_off = L.take(4 * n), o_e = L.take(8 * (size_t)(R + 1));
-  const size_t out_end = L.size;
+  const size_t o_res = L.take(MrfResult::bytes(R)), o_off = L.take(4 * n);
   const size_t o_ids = L.take(12 * n), o_nbr = L.take(24 * n), o_co = L.take(8 * (n + 1)), o_l = L.take(4 * (size_t)nnz),
                o_u = L.take(4 * (size_t)nnz), o_i = L.take(init_offsets ? 4 * n : 0);
   const size_t host_end = L.size;
-  MrfScratch sc;
-  sc.take(L, n_nodes, nnz);
+  MrfScratch().take(L, n_nodes, nnz);  // (mrf_begin lays it out at host_end again: the pool is reserved for all of it here)
   Stage sg;
   if ((rc = stage_begin(v, v->scratch, L.size, host_end, &sg)) || (rc = stage_in(v, sg, o_ids, ids, 12 * n)) ||
       (rc = stage_in(v, sg, o_nbr, nbr, 24 * n)) || (rc = stage_in(v, sg, o_co, col_off, 8 * (n + 1))) ||
       (rc = stage_in(v, sg, o_l, labels, 4 * (size_t)nnz)) || (rc = stage_in(v, sg, o_u, costs, 4 * (size_t)nnz)) ||
       (init_offsets && (rc = stage_in(v, sg, o_i, init_offsets, 4 * n))))
     return rc;
+  MrfResult* res = sg.hp<MrfResult>(o_res);
   MrfArgs a{};
   a.n = (int32_t)n_nodes; a.nnz = nnz; a.ids = sg.dp<const int32_t>(o_ids); a.nbr = sg.dp<const int32_t>(o_nbr);
   a.col_off = sg.dp<const int64_t>(o_co); a.labels = sg.dp<const int32_t>(o_l); a.costs = sg.dp<const float>(o_u);
   a.init = init_offsets ? sg.dp<const int32_t>(o_i) : nullptr; a.w = edge_cost; a.off = sg.dp<int32_t>(o_off);
-  a.energy = sg.dp<double>(o_e); a.rounds = sg.dp<int32_t>(o_r);
-  sc.bind(a, sg.d);
-  if ((rc = mrf_enqueue_start(v, a))) return rc;
+  a.energy = sg.dp<MrfResult>(o_res)->energy; a.rounds = sg.dp<MrfResult>(o_res)->rounds;
+  if ((rc = mrf_begin(v, a, host_end))) return rc;
   // the host form waits for the result anyway: it looks at the control block every kHostBatch rounds and stops
   // enqueueing once the solve has ended (the launches behind the end would all return at once)
-  const MrfCtl* hc = sg.hp<const MrfCtl>(o_c);
   for (int r = 1;; r += kHostBatch) {
-    TF_HIP(hipMemcpyAsync(sg.h + o_c, a.ctl, sizeof(MrfCtl), hipMemcpyDeviceToHost, v->stream));
+    TF_HIP(hipMemcpyAsync(&res->ctl, a.ctl, sizeof(MrfCtl), hipMemcpyDeviceToHost, v->stream));
     TF_HIP(hipStreamSynchronize(v->stream));
-    if (hc->bad != ~0ull) return mrf_bad_to_error(hc->bad);
-    if (hc->done || r > R) break;
+    if (res->ctl.bad != ~0ull) return mrf_bad_to_error(res->ctl.bad);
+    if (res->ctl.done || r > R) break;
     if ((rc = mrf_enqueue_rounds(v, a, r, r + kHostBatch - 1 < R ? r + kHostBatch - 1 : R))) return rc;
   }
-  TF_HIP(hipMemcpyAsync(sg.h, sg.d, out_end, hipMemcpyDeviceToHost, v->stream));
-  TF_HIP(hipStreamSynchronize(v->stream));
-  const int32_t rounds = *sg.hp<const int32_t>(o_r);
+  TF_HIP(hipMemcpyAsync(sg.h + o_off, a.off, 4 * n, hipMemcpyDeviceToHost, v->stream));
+  if ((rc = mrf_read_back(v, a, R, res))) return rc;
+  const int32_t rounds = res->rounds[0];
   memcpy(out_offsets, sg.h + o_off, 4 * n);
-  if (out_energy) memcpy(out_energy, sg.h + o_e, 8 * (size_t)(rounds + 1));
+  if (out_energy) memcpy(out_energy, res->energy, 8 * (size_t)(rounds + 1));
   *out_rounds = rounds;
   return TF_OK;
 }

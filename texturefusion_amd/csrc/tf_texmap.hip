@@ -3,7 +3,9 @@
 // on the device, its solved labels assigned there -- the piece between Chunk::observations / Mesh::adj (already in HBM) and
 // the solve (tf_mrf.hip) that used to travel through the host for every chunk.
 //
-// State (tf_volume::tm, handed to the kernels as TmDev; every pointer null until the first tf_texmap_* call, freed by tf_volume_reset / tf_volume_destroy):
+// State (tf_volume::tm, handed to the kernels as TmDev; every pointer null until the first tf_texmap_* call, freed by
+// tf_volume_reset / tf_volume_destroy).  node .. ctl are ONE device allocation laid out by the table tm_arrays, which first
+// use (all or nothing), tf_texmap_clear and the release share:
 //   node   [max_chunks] u32   bit 0: the chunk is a node (UniGraph::chunks); bits 1..6: an edge across face k of
 //                             chisel::neighbourhood, kept on both ends (UniGraph::adj_lists); bit 7: the node had an entry
 //                             of labelstorage at the last full solve (i < labelstorage.size())
@@ -13,19 +15,23 @@
 //                             Keyed by frame index and not by row, so that retraction needs no row lookup; rows (kflist
 //                             positions) enter only when a problem is assembled, through kf_row.
 //   ctl                       "a full solve has run" (!labelstorage.empty()), the size of the problem being assembled
-//   kf_row [n_rows]           kflist[r].keyFrameIndex; the dense inverse (frameIndexToKeyframeDB, MobileFusion.cpp:293-296)
-//                             stays on the host (TexMapState::kf_inv): it only checks the frames an update names
+// What grows is a Scratch grown by reserve() (TexMapState), which drains the stream before it frees a buffer in use:
+//   kf     [n_rows + 64]      kf_row = kflist[r].keyFrameIndex (device half; the pinned half stages its upload), 64 words
+//                             behind the rows for the tail's keyframes to update.  The dense inverse (frameIndexToKeyframeDB,
+//                             MobileFusion.cpp:293-296) stays on the host (kf_inv): it only checks the frames an update names
+//   pn, pz                    the problem assembled last, per node and per label (TmProb::take_nodes / take_labels)
 // Pool slots never move and hash entries are never removed, so a slot is a chunk id for the life of the
 // volume and per-slot state needs no relocation.  The reference's `statistic` vector is written and never read
 // (TexMap.cpp:71-75,95): it is not kept.
 //
-// Assembly (tf_texmap_view_selection): nodes are collected into a compact list (their numbering is free: the solver's
+// Assembly (tm_select): nodes are collected into a compact list (their numbering is free: the solver's
 // labels, rounds and f64 trace do not depend on it), one wave per node walks the keyframe rows in ascending order and
-// probes the cost table -- the ballot order of the lanes IS the ascending row order of std::map -- a single-workgroup scan
-// turns the column lengths into col_off, the host reads {n_nodes, nnz} once to size the solver's scratch, a second pass per
-// node writes labels (row + 1), costs 1.0f - q / column_max (IEEE divide, no contraction), the neighbour indices and the
-// warm start.  mrf_enqueue_start / mrf_enqueue_rounds solve it; k_tm_assign maps labels back to keyframe indices
-// (TexMap.cpp:227-246).
+// probes the cost table (tm_for_rows) -- the ballot order of the lanes IS the ascending row order of std::map -- a
+// single-workgroup scan turns the column lengths into col_off, the host reads {n_nodes, nnz} once to size the solver's
+// scratch, a second pass per node writes labels (row + 1), costs 1.0f - q / column_max (IEEE divide, no contraction), the
+// neighbour indices and the warm start.  mrf_begin / mrf_enqueue_rounds solve it; k_tm_assign maps labels back to keyframe
+// indices (TexMap.cpp:227-246).
+#include <stddef.h>
 #include <string.h>
 
 #include <algorithm>
@@ -37,6 +43,15 @@
 
 namespace tf {
 namespace {
+
+constexpr int kTmMaxRounds = 4096;
+
+// block `count` elements long out of the staging area L at base d (d == null: only L grows, by what the block needs)
+template <typename T>
+void tm_carve(T*& p, void* d, Layout& L, size_t count) {
+  const size_t at = L.take(count * sizeof(T));
+  p = d ? reinterpret_cast<T*>(static_cast<uint8_t*>(d) + at) : nullptr;
+}
 
 // the problem assembled last (device arrays; TexMapState::pn / pz)
 struct TmProb {
@@ -52,8 +67,15 @@ struct TmProb {
   double* energy;      // [kTmMaxRounds + 1]
   int32_t* labels;     // [nnz]
   float* costs;        // [nnz]
+  // the per-node arrays for c nodes out of d (TexMapState::pn), the per-label arrays for c labels (pz)
+  void take_nodes(Layout& L, void* d, size_t c) {
+    cap = (uint32_t)c;
+    tm_carve(slot, d, L, c); tm_carve(ids, d, L, 3 * c); tm_carve(nbr, d, L, 6 * c); tm_carve(col_off, d, L, c + 1);
+    tm_carve(cnt, d, L, c); tm_carve(init, d, L, c); tm_carve(off, d, L, c); tm_carve(rounds, d, L, 4);
+    tm_carve(energy, d, L, (size_t)kTmMaxRounds + 1);
+  }
+  void take_labels(Layout& L, void* d, size_t c) { tm_carve(labels, d, L, c); tm_carve(costs, d, L, c); }
 };
-constexpr int kTmMaxRounds = 4096;
 
 __device__ __forceinline__ uint32_t tm_slot_of(const VolumeDev& v, int x, int y, int z) {
   const uint32_t e = hash_find(v, pack_id(x, y, z));
@@ -90,6 +112,34 @@ __device__ __forceinline__ float tm_obs(const VolumeDev& v, uint32_t slot, int32
   return at == kInvalidSlot ? 0.0f : v.obs_q[at];
 }
 __device__ __forceinline__ bool tm_in_map(const VolumeDev& v, uint32_t slot) { return (v.mesh_rec[slot].state & kMsInMap) != 0; }
+__device__ __forceinline__ bool tm_is_node(const TmDev& v, uint32_t slot) { return (v.tm.node[slot] & kTmNode) != 0; }
+
+// The chunk-hash entry of this thread (one thread per entry, blocks of 256): false beyond the table, for an empty entry and
+// for one without a pool slot; the kernels over the hash start here.
+__device__ __forceinline__ bool tm_entry(const TmDev& v, HEntry* h) {
+  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+  if (e > v.hmask) return false;
+  *h = v.hent[e];
+  return h->key != kEmptyKey && h->slot < v.max_chunks;
+}
+
+// The column of a pool slot, walked by one wave: the keyframe rows in blocks of 64, lane = row within the block, every lane
+// probing the cost table.  Per block fn(r, frame, q, present, before): the lane's row, frame index and quality (0: none),
+// the ballot of the lanes with an entry (q > 0) and the entries of the blocks before -- before + popc(present & lanes
+// below) is the entry's position in the column, rows ascending (the order of std::map).  Returns the column's length.
+template <typename F>
+__device__ __forceinline__ uint32_t tm_for_rows(const TmDev& v, uint32_t slot, int lane, F fn) {
+  uint32_t before = 0;
+  for (int32_t r0 = 0; r0 < v.tm.n_rows; r0 += 64) {
+    const int32_t r = r0 + lane;
+    const int32_t f = r < v.tm.n_rows ? v.tm.kf_row[r] : 0;
+    const float q = r < v.tm.n_rows ? tm_cost(v, slot, f) : 0.0f;
+    const unsigned long long present = __ballot(q > 0.0f);
+    fn(r, f, q, present, before);
+    before += (uint32_t)__popcll(present);
+  }
+  return before;
+}
 
 // UniGraph::add_node for every listed chunk (TexMap.cpp:53-55); all nodes are there before any edge is looked at
 __global__ __launch_bounds__(256) void k_tm_add_nodes(TmDev v, const int4* __restrict__ ids, uint32_t n, const uint32_t* __restrict__ dn) {
@@ -152,13 +202,11 @@ __global__ __launch_bounds__(256) void k_tm_retract(TmDev v, int32_t kf_id, cons
 // MobileFusion.cpp:330-342 over the chunk hash: a mesh in the map whose patch has wrong_mapping loses the entry of the
 // keyframe its patch was cut from.  ctl->n_removed counts the entries that were there.
 __global__ __launch_bounds__(256) void k_tm_wrong_mapping(TmDev v) {
-  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-  if (e > v.hmask) return;
-  const HEntry h = v.hent[e];
-  if (h.key == kEmptyKey || !(h.alive & 1u) || h.slot >= v.max_chunks) return;
+  HEntry h;
+  if (!tm_entry(v, &h) || !(h.alive & 1u)) return;
   const MeshRec* r = &v.mesh_rec[h.slot];
   if (!(r->state & kMsInMap) || (r->pflags & (kPfHasPatch | kPfWrong)) != (kPfHasPatch | kPfWrong)) return;
-  if (!(v.tm.node[h.slot] & kTmNode)) return;  // (the reference dereferences chunks.find() unchecked here)
+  if (!tm_is_node(v, h.slot)) return;  // (the reference dereferences chunks.find() unchecked here)
   const uint32_t at = tm_find(v, obs_pack(h.slot, r->frameid), false);
   if (at != kInvalidSlot && v.tm.q[at] > 0.0f) {
     v.tm.q[at] = 0.0f;
@@ -169,10 +217,8 @@ __global__ __launch_bounds__(256) void k_tm_wrong_mapping(TmDev v) {
 // TexMap::check_graph (TexMap.cpp:107-118): UniGraph::remove_node for every node whose mesh has left allMeshes -- its
 // edges go on both ends, it stays a node (uni_graph.cpp:89-107) -- ...
 __global__ __launch_bounds__(256) void k_tm_check_nodes(TmDev v) {
-  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-  if (e > v.hmask) return;
-  const HEntry h = v.hent[e];
-  if (h.key == kEmptyKey || h.slot >= v.max_chunks) return;
+  HEntry h;
+  if (!tm_entry(v, &h)) return;
   const uint32_t w = v.tm.node[h.slot];
   if (!(w & kTmNode) || tm_in_map(v, h.slot)) return;
   atomicAdd(&v.tm.ctl->n_removed, 1u);
@@ -200,10 +246,8 @@ __global__ __launch_bounds__(256) void k_tm_check_costs(TmDev v) {
 // ---- the problem --------------------------------------------------------------------------------------------------
 // every node of the graph (TexMap.cpp:122), off the chunk hash: the hash entry holds the id the solver's checks want
 __global__ __launch_bounds__(256) void k_tm_collect_all(TmDev v, TmProb P) {
-  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-  if (e > v.hmask) return;
-  const HEntry h = v.hent[e];
-  if (h.key == kEmptyKey || h.slot >= v.max_chunks || !(v.tm.node[h.slot] & kTmNode)) return;
+  HEntry h;
+  if (!tm_entry(v, &h) || !tm_is_node(v, h.slot)) return;
   const uint32_t p = atomicAdd(&v.tm.ctl->n_nodes, 1u);
   if (p >= P.cap) return;
   const int4 id = unpack_id(h.key);
@@ -233,12 +277,7 @@ __global__ __launch_bounds__(256) void k_tm_count(TmDev v, TmProb P) {
   const int lane = (int)(threadIdx.x & 63u);
   for (uint32_t p = blockIdx.x * 4u + (threadIdx.x >> 6); p < n; p += gridDim.x * 4u) {
     const uint32_t slot = P.slot[p];
-    uint32_t K = 0;
-    for (int32_t r0 = 0; r0 < v.tm.n_rows; r0 += 64) {
-      const int32_t r = r0 + lane;
-      const float q = r < v.tm.n_rows ? tm_cost(v, slot, v.tm.kf_row[r]) : 0.0f;
-      K += (uint32_t)__popcll(__ballot(q > 0.0f));
-    }
+    const uint32_t K = tm_for_rows(v, slot, lane, [](int32_t, int32_t, float, unsigned long long, uint32_t) {});
     if (lane == 0) {
       P.cnt[p] = K;
       if (v.tm.node[slot] & kTmTmp) atomicAnd(&v.tm.node[slot], ~kTmTmp);
@@ -294,14 +333,11 @@ __global__ __launch_bounds__(256) void k_tm_fill(TmDev v, TmProb P, uint32_t n, 
       if (lane == 0) { P.labels[c0] = 0; P.costs[c0] = 1.0f; }
     } else {
       float mx = 0.0f;  // column_max (:168-170; qualities are > 0)
-      for (int32_t r0 = 0; r0 < v.tm.n_rows; r0 += 64) {
-        const int32_t r = r0 + lane;
-        const float q = r < v.tm.n_rows ? tm_cost(v, slot, v.tm.kf_row[r]) : 0.0f;
-        mx = fmaxf(mx, q);
-      }
+      tm_for_rows(v, slot, lane, [&](int32_t, int32_t, float q, unsigned long long, uint32_t) { mx = fmaxf(mx, q); });
 #pragma unroll
       for (int d = 32; d; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
       const int32_t want = (warm && (word & kTmHadLabel)) ? v.tm.stored[slot] : -1;
+      // tm_for_rows' walk written out and to be kept like it: in helper form this pass costs the kernel a 43rd VGPR
       uint32_t pos = 0;
       float cbest = INFINITY;
       uint32_t jbest = 0xFFFFFFFFu;
@@ -405,20 +441,14 @@ __global__ __launch_bounds__(256) void k_tm_download(TmDev v, const int4* __rest
     const uint32_t slot = tm_slot_of(v, id.x, id.y, id.z);
     const uint32_t word = slot == kInvalidSlot ? 0u : v.tm.node[slot];
     uint32_t pos = 0;
-    if (word & kTmNode) {
-      for (int32_t r0 = 0; r0 < v.tm.n_rows; r0 += 64) {
-        const int32_t r = r0 + lane;
-        const int32_t f = r < v.tm.n_rows ? v.tm.kf_row[r] : 0;
-        const float q = r < v.tm.n_rows ? tm_cost(v, slot, f) : 0.0f;
-        const unsigned long long m = __ballot(q > 0.0f);
+    if (word & kTmNode)
+      pos = tm_for_rows(v, slot, lane, [&](int32_t, int32_t f, float q, unsigned long long m, uint32_t before) {
         if (q > 0.0f) {
-          const size_t at = (size_t)i * (size_t)v.tm.n_rows + pos + (uint32_t)__popcll(m & lt);
+          const size_t at = (size_t)i * (size_t)v.tm.n_rows + before + (uint32_t)__popcll(m & lt);
           col_frame[at] = f;
           col_q[at] = q;
         }
-        pos += (uint32_t)__popcll(m);
-      }
-    }
+      });
     if (lane == 0) {
       info[4 * i] = (int32_t)(word & kTmNode ? word & (kTmNode | kTmEdges | kTmHadLabel) : 0u);
       info[4 * i + 1] = (word & kTmNode) ? v.tm.label[slot] : 0;
@@ -454,94 +484,62 @@ __global__ __launch_bounds__(256) void k_tm_work_cut(TmDev v, uint32_t n, const 
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-template <typename T>
-int tm_alloc(T** p, size_t count, int fill, hipStream_t s) {
-  TF_HIP(hipMalloc((void**)p, count * sizeof(T)));
-  TF_HIP(hipMemsetAsync(*p, fill, count * sizeof(T), s));
+// The map's device arrays in the order they lie in its one block (node first: the block's base) as fn(member, bytes, fill)
+template <typename F>
+void tm_arrays(TexMapDev& t, size_t max_chunks, F fn) {
+  const size_t mc = max_chunks, cap = (size_t)t.mask + 1;  // (the cost table is as large as the observation table it mirrors)
+  fn(t.node, 4 * mc, 0); fn(t.label, 4 * mc, 0); fn(t.stored, 4 * mc, 0); fn(t.idx, 4 * mc, 0xFF);
+  fn(t.key, 8 * cap, 0xFF); fn(t.q, 4 * cap, 0); fn(t.ctl, sizeof(TexMapCtl), 0);
+}
+
+int tm_fill(tf_volume* v) {
+  hipError_t e = hipSuccess;
+  tm_arrays(v->tm, v->dev.max_chunks, [&](auto* p, size_t bytes, int fill) {
+    if (e == hipSuccess) e = hipMemsetAsync(p, fill, bytes, v->stream);
+  });
+  TF_HIP(e);
   return TF_OK;
 }
 
-// first use: the per-slot state and the cost table (as large as the observation table it mirrors)
+// First use, all or nothing: one that fails gives back what it took, so node != null says that the whole map is there
 int tm_ensure(tf_volume* v) {
   TexMapDev& t = v->tm;
   if (t.node) return TF_OK;
-  const size_t mc = v->dev.max_chunks, cap = (size_t)v->dev.obs_mask + 1;
-  int rc;
-  if ((rc = tm_alloc(&t.node, mc, 0, v->stream)) || (rc = tm_alloc(&t.label, mc, 0, v->stream)) ||
-      (rc = tm_alloc(&t.stored, mc, 0, v->stream)) || (rc = tm_alloc(&t.idx, mc, 0xFF, v->stream)) ||
-      (rc = tm_alloc(&t.key, cap, 0xFF, v->stream)) || (rc = tm_alloc(&t.q, cap, 0, v->stream)) ||
-      (rc = tm_alloc(&t.ctl, 1, 0, v->stream)))
-    return rc;
   t.mask = v->dev.obs_mask;
-  TF_HIP(hipHostMalloc((void**)&v->tmx.h_ctl, sizeof(TexMapCtl), hipHostMallocDefault));
-  return TF_OK;
+  void* d = nullptr;
+  Layout L;
+  const auto carve = [&](auto*& p, size_t bytes, int) { tm_carve(p, d, L, bytes / sizeof(*p)); };
+  tm_arrays(t, v->dev.max_chunks, carve);  // (d == null: the block's size)
+  const int rc = [&]() -> int {
+    TF_HIP(hipMalloc(&d, L.size));
+    L = Layout{};
+    tm_arrays(t, v->dev.max_chunks, carve);
+    TF_HIP(hipHostMalloc((void**)&v->tmx.h_ctl, sizeof(TexMapCtl), hipHostMallocDefault));
+    return tm_fill(v);
+  }();
+  if (rc) texmap_release(v);
+  return rc;
 }
 
-int tm_clear(tf_volume* v) {
-  TexMapDev& t = v->tm;
-  if (!t.node) return TF_OK;
-  const size_t mc = v->dev.max_chunks, cap = (size_t)t.mask + 1;
-  hipStream_t s = v->stream;
-  TF_HIP(hipMemsetAsync(t.node, 0, mc * 4, s));
-  TF_HIP(hipMemsetAsync(t.label, 0, mc * 4, s));
-  TF_HIP(hipMemsetAsync(t.stored, 0, mc * 4, s));
-  TF_HIP(hipMemsetAsync(t.idx, 0xFF, mc * 4, s));
-  TF_HIP(hipMemsetAsync(t.key, 0xFF, cap * 8, s));
-  TF_HIP(hipMemsetAsync(t.q, 0, cap * 4, s));
-  TF_HIP(hipMemsetAsync(t.ctl, 0, sizeof(TexMapCtl), s));
-  v->tmx.nodes_bound = 0;
-  v->tmx.n = v->tmx.nnz = 0;
-  return TF_OK;
-}
-
-struct PnLayout {
-  size_t slot, ids, nbr, col_off, cnt, init, off, rounds, energy, size;
-  explicit PnLayout(size_t cap) {
-    Layout L;
-    slot = L.take(4 * cap); ids = L.take(12 * cap); nbr = L.take(24 * cap); col_off = L.take(8 * (cap + 1));
-    cnt = L.take(4 * cap); init = L.take(4 * cap); off = L.take(4 * cap); rounds = L.take(16);
-    energy = L.take(8 * (size_t)(kTmMaxRounds + 1));
-    size = L.size;
-  }
-};
-struct PzLayout {
-  size_t labels, costs, size;
-  explicit PzLayout(size_t cap) {
-    Layout L;
-    labels = L.take(4 * cap); costs = L.take(4 * cap);
-    size = L.size;
-  }
-};
-
-int tm_grow(tf_volume* v, void** p, size_t* cap, size_t want, bool per_node) {
-  if (want <= *cap && *p) return TF_OK;
-  size_t c = 1024;
+// room for `want` nodes in TexMapState::pn (per_node) or labels in pz: a power of two of at least 1024 that never shrinks
+int tm_room(tf_volume* v, bool per_node, size_t want) {
+  TexMapState& x = v->tmx;
+  size_t& cap = per_node ? x.pn_cap : x.pz_cap;
+  size_t c = std::max<size_t>(cap, 1024);
   while (c < want) c <<= 1;
-  if (*p) {
-    TF_HIP(hipStreamSynchronize(v->stream));
-    TF_HIP(hipFree(*p));
-    *p = nullptr; *cap = 0;
-  }
-  TF_HIP(hipMalloc(p, per_node ? PnLayout(c).size : PzLayout(c).size));
-  *cap = c;
-  return TF_OK;
+  TmProb P{};
+  Layout L;
+  if (per_node) P.take_nodes(L, nullptr, c); else P.take_labels(L, nullptr, c);
+  const int rc = reserve(v, per_node ? x.pn : x.pz, L.size, 0);
+  if (!rc) cap = c;
+  return rc;
 }
 
 TmProb tm_prob(const TexMapState& x) {
   TmProb P{};
-  uint8_t* a = reinterpret_cast<uint8_t*>(x.pn);
-  uint8_t* z = reinterpret_cast<uint8_t*>(x.pz);
-  const PnLayout N(x.pn_cap);
-  P.cap = (uint32_t)x.pn_cap;
-  P.slot = reinterpret_cast<uint32_t*>(a + N.slot); P.ids = reinterpret_cast<int32_t*>(a + N.ids);
-  P.nbr = reinterpret_cast<int32_t*>(a + N.nbr); P.col_off = reinterpret_cast<long long*>(a + N.col_off);
-  P.cnt = reinterpret_cast<uint32_t*>(a + N.cnt); P.init = reinterpret_cast<int32_t*>(a + N.init);
-  P.off = reinterpret_cast<int32_t*>(a + N.off); P.rounds = reinterpret_cast<int32_t*>(a + N.rounds);
-  P.energy = reinterpret_cast<double*>(a + N.energy);
-  if (z) {
-    const PzLayout Z(x.pz_cap);
-    P.labels = reinterpret_cast<int32_t*>(z + Z.labels); P.costs = reinterpret_cast<float*>(z + Z.costs);
-  }
+  Layout N, Z;
+  P.take_nodes(N, x.pn.d, x.pn_cap);
+  P.take_labels(Z, x.pz.d, x.pz_cap);
   return P;
 }
 
@@ -553,15 +551,13 @@ unsigned wave_blocks(size_t n) { return (unsigned)std::min<size_t>(std::max<size
 void texmap_release(tf_volume* v) {
   TexMapDev& t = v->tm;
   TexMapState& x = v->tmx;
-  if (t.node) { hipFree(t.node); hipFree(t.label); hipFree(t.stored); hipFree(t.idx); hipFree(t.key); hipFree(t.q); hipFree(t.ctl); }
-  if (x.d_kf_row) hipFree(x.d_kf_row);
-  if (x.h_kf) hipHostFree(x.h_kf);
-  if (x.kf_ev) hipEventDestroy(x.kf_ev);
-  if (x.pn) hipFree(x.pn);
-  if (x.pz) hipFree(x.pz);
+  if (t.node) hipFree(t.node);  // the block (tm_arrays)
   if (x.h_ctl) hipHostFree(x.h_ctl);
-  if (x.d_ctu_raw) hipFree(x.d_ctu_raw);
-  if (x.d_ctu) hipFree(x.d_ctu);
+  scratch_free(x.kf);
+  if (x.kf_ev) hipEventDestroy(x.kf_ev);
+  scratch_free(x.pn);
+  scratch_free(x.pz);
+  if (x.d_ctu_raw) hipFree(x.d_ctu_raw);  // (d_ctu lies behind it)
   t = TexMapDev{};
   x = TexMapState{};
 }
@@ -598,45 +594,38 @@ int tf_texmap_set_keyframes(tf_volume* v, const int32_t* key_frame_index, int32_
   TexMapState& x = v->tmx;
   if (!x.kf_ev) TF_HIP(hipEventCreateWithFlags(&x.kf_ev, hipEventDisableTiming));
   else TF_HIP(hipEventSynchronize(x.kf_ev));  // the previous upload has left the staging buffer
-  if ((size_t)n_rows + 64 > x.kf_cap) {  // (64 words behind the rows: the tail's keyframes to update)
-    size_t c = 256;
-    while (c < (size_t)n_rows + 64) c <<= 1;
-    TF_HIP(hipStreamSynchronize(v->stream));  // launches on the stream may still read the old table
-    if (x.d_kf_row) TF_HIP(hipFree(x.d_kf_row));
-    if (x.h_kf) TF_HIP(hipHostFree(x.h_kf));
-    x.d_kf_row = nullptr; x.h_kf = nullptr; x.kf_cap = 0;
-    TF_HIP(hipMalloc((void**)&x.d_kf_row, 4 * c));
-    TF_HIP(hipHostMalloc((void**)&x.h_kf, 4 * c, hipHostMallocDefault));
-    x.kf_cap = c;
-  }
-  memcpy(x.h_kf, key_frame_index, 4 * (size_t)n_rows);
-  TF_HIP(hipMemcpyAsync(x.d_kf_row, x.h_kf, 4 * (size_t)n_rows, hipMemcpyHostToDevice, v->stream));
+  const size_t bytes = 4 * std::max<size_t>((size_t)n_rows + 64, 256);  // (64 words behind the rows: the tail's keyframes to update)
+  if ((rc = reserve(v, x.kf, bytes, bytes))) { v->tm.kf_row = nullptr; v->tm.n_rows = 0; return rc; }
+  memcpy(x.kf.h, key_frame_index, 4 * (size_t)n_rows);
+  TF_HIP(hipMemcpyAsync(x.kf.d, x.kf.h, 4 * (size_t)n_rows, hipMemcpyHostToDevice, v->stream));
   TF_HIP(hipEventRecord(x.kf_ev, v->stream));
   x.kf_row.assign(key_frame_index, key_frame_index + n_rows);
   x.kf_inv.swap(inv);
-  v->tm.kf_row = x.d_kf_row;
+  v->tm.kf_row = static_cast<const int32_t*>(x.kf.d);
   v->tm.n_rows = n_rows;
   return TF_OK;
 }
 
-// the two device lists of chunksToUpdate (first use)
+// the two device lists of chunksToUpdate (first use): one allocation
 static int tm_list_buffers(tf_volume* v) {
   TexMapState& x = v->tmx;
   if (x.d_ctu) return TF_OK;
-  TF_HIP(hipMalloc((void**)&x.d_ctu_raw, (size_t)v->dev.max_chunks * 16));
-  TF_HIP(hipMalloc((void**)&x.d_ctu, (size_t)v->dev.max_chunks * 16));
+  const size_t mc = v->dev.max_chunks;
+  TF_HIP(hipMalloc((void**)&x.d_ctu_raw, 2 * mc * 16));
+  x.d_ctu = x.d_ctu_raw + mc;
   return TF_OK;
 }
-// frames_to_update of the tail: into the tail of the keyframe table's device buffer, through its pinned staging buffer
-static int tm_frames_upload(tf_volume* v, const int32_t* frames, int32_t n, int32_t** d_out) {
+// frames_to_update of the tail: into the tail of the keyframe table's device half, through its pinned half
+static int tm_frames_upload(tf_volume* v, const int32_t* frames, int32_t n, const int32_t** d_out) {
   TexMapState& x = v->tmx;
   const size_t rows = (size_t)v->tm.n_rows;
-  if (rows + (size_t)n > x.kf_cap) { set_error("texmap: more keyframes to update than the keyframe table has room behind its rows"); return TF_ERR_CAPACITY; }
+  if (rows + (size_t)n > x.kf.d_bytes / 4) { set_error("texmap: more keyframes to update than the keyframe table has room behind its rows"); return TF_ERR_CAPACITY; }
+  int32_t *h = static_cast<int32_t*>(x.kf.h) + rows, *d = static_cast<int32_t*>(x.kf.d) + rows;
   TF_HIP(hipEventSynchronize(x.kf_ev));
-  memcpy(x.h_kf + rows, frames, 4 * (size_t)n);
-  TF_HIP(hipMemcpyAsync(x.d_kf_row + rows, x.h_kf + rows, 4 * (size_t)n, hipMemcpyHostToDevice, v->stream));
+  memcpy(h, frames, 4 * (size_t)n);
+  TF_HIP(hipMemcpyAsync(d, h, 4 * (size_t)n, hipMemcpyHostToDevice, v->stream));
   TF_HIP(hipEventRecord(x.kf_ev, v->stream));
-  *d_out = x.d_kf_row + rows;
+  *d_out = d;
   return TF_OK;
 }
 
@@ -651,20 +640,23 @@ static int tm_update_enqueue(tf_volume* v, const int4* d_ids, uint32_t n, const 
   return TF_OK;
 }
 
-static int tm_frame_known(const tf_volume* v, int32_t f) {
+// the keyframe of an update and its n keyframes to update must be in the keyframe table
+static int tm_frames_known(const tf_volume* v, int32_t frame_index, const int32_t* frames, int32_t n) {
   const std::vector<int32_t>& inv = v->tmx.kf_inv;
-  if (f >= 0 && (size_t)f < inv.size() && inv[(size_t)f] >= 0) return TF_OK;
-  set_error("texmap: frame index " + std::to_string(f) + " is not in the keyframe table (tf_texmap_set_keyframes)");
-  return TF_ERR_INVALID;
+  for (int32_t j = -1; j < n; ++j) {
+    const int32_t f = j < 0 ? frame_index : frames[j];
+    if (f >= 0 && (size_t)f < inv.size() && inv[(size_t)f] >= 0) continue;
+    set_error("texmap: frame index " + std::to_string(f) + " is not in the keyframe table (tf_texmap_set_keyframes)");
+    return TF_ERR_INVALID;
+  }
+  return TF_OK;
 }
 
 int tf_texmap_update(tf_volume* v, const int32_t* ids, int64_t n, int32_t frame_index, const int32_t* frames_to_update,
                      int32_t n_frames) {
   if (!v || (n > 0 && !ids) || n_frames < 0 || (n_frames > 0 && !frames_to_update)) { set_error("invalid argument"); return TF_ERR_INVALID; }
-  int rc;
-  if ((rc = tm_frame_known(v, frame_index))) return rc;
-  for (int32_t j = 0; j < n_frames; ++j)
-    if ((rc = tm_frame_known(v, frames_to_update[j]))) return rc;
+  int rc = tm_frames_known(v, frame_index, frames_to_update, n_frames);
+  if (rc) return rc;
   if (n > (int64_t)v->dev.max_chunks) { set_error("chunk list longer than tf_config.max_chunks"); return TF_ERR_CAPACITY; }
   TF_DEV(v);
   if ((rc = tm_ensure(v))) return rc;
@@ -691,42 +683,51 @@ int tf_texmap_retract(tf_volume* v, int32_t keyframe_id, const int32_t* ids, int
   return TF_OK;
 }
 
-// n_removed != NULL: waits for the count
-static int tm_removed(tf_volume* v, int64_t* n_removed) {
-  if (!n_removed) return TF_OK;
+// MobileFusion.cpp:330-342 and TexMap::check_graph on the stream; TexMapCtl::n_removed counts what the pass removed
+static int tm_wrong_mapping_enqueue(tf_volume* v) {
+  TF_HIP(hipMemsetAsync(&v->tm.ctl->n_removed, 0, 4, v->stream));
+  hipLaunchKernelGGL(k_tm_wrong_mapping, dim3(blocks_of((size_t)v->dev.hmask + 1, 256)), dim3(256), 0, v->stream, tm_dev(v));
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+static int tm_check_graph_enqueue(tf_volume* v) {
+  TF_HIP(hipMemsetAsync(&v->tm.ctl->n_removed, 0, 4, v->stream));
+  hipLaunchKernelGGL(k_tm_check_nodes, dim3(blocks_of((size_t)v->dev.hmask + 1, 256)), dim3(256), 0, v->stream, tm_dev(v));
+  hipLaunchKernelGGL(k_tm_check_costs, dim3(blocks_of((size_t)v->tm.mask + 1, 256)), dim3(256), 0, v->stream, tm_dev(v));
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+
+// the entry point around one of the two passes; n_removed != NULL: waits for the count
+static int tm_removal(tf_volume* v, int (*enqueue)(tf_volume*), int64_t* n_removed) {
+  if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
+  TF_DEV(v);
+  if (n_removed) *n_removed = 0;
+  if (!v->tm.node) return TF_OK;
+  const int rc = enqueue(v);
+  if (rc || !n_removed) return rc;
   TF_HIP(hipMemcpyAsync(v->tmx.h_ctl, v->tm.ctl, sizeof(TexMapCtl), hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   *n_removed = v->tmx.h_ctl->n_removed;
   return TF_OK;
 }
 
-int tf_texmap_remove_wrong_mapping(tf_volume* v, int64_t* n_removed) {
-  if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
-  TF_DEV(v);
-  if (n_removed) *n_removed = 0;
-  if (!v->tm.node) return TF_OK;
-  TF_HIP(hipMemsetAsync(&v->tm.ctl->n_removed, 0, 4, v->stream));
-  hipLaunchKernelGGL(k_tm_wrong_mapping, dim3(blocks_of((size_t)v->dev.hmask + 1, 256)), dim3(256), 0, v->stream, tm_dev(v));
-  TF_HIP(hipGetLastError());
-  return tm_removed(v, n_removed);
-}
+int tf_texmap_remove_wrong_mapping(tf_volume* v, int64_t* n_removed) { return tm_removal(v, tm_wrong_mapping_enqueue, n_removed); }
+int tf_texmap_check_graph(tf_volume* v, int64_t* n_removed) { return tm_removal(v, tm_check_graph_enqueue, n_removed); }
 
-int tf_texmap_check_graph(tf_volume* v, int64_t* n_removed) {
-  if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
-  TF_DEV(v);
-  if (n_removed) *n_removed = 0;
-  if (!v->tm.node) return TF_OK;
-  TF_HIP(hipMemsetAsync(&v->tm.ctl->n_removed, 0, 4, v->stream));
-  hipLaunchKernelGGL(k_tm_check_nodes, dim3(blocks_of((size_t)v->dev.hmask + 1, 256)), dim3(256), 0, v->stream, tm_dev(v));
-  hipLaunchKernelGGL(k_tm_check_costs, dim3(blocks_of((size_t)v->tm.mask + 1, 256)), dim3(256), 0, v->stream, tm_dev(v));
-  TF_HIP(hipGetLastError());
-  return tm_removed(v, n_removed);
-}
+struct TmWant {  // what a caller of tm_select wants back (null: not wanted)
+  double* energy;    // the f64 trace [0 .. rounds]; needs rounds
+  int32_t* rounds;   // (waits for the solve)
+  int64_t* n_nodes;
+  uint32_t* list_n;  // TexMapCtl::n_list as the one wait read it
+};
+// n_nodes and nnz of the control block, the problem being assembled, are zeroed as one
+constexpr size_t kTmCtlProblem = offsetof(TexMapCtl, n_removed) - offsetof(TexMapCtl, n_nodes);
+static_assert(offsetof(TexMapCtl, nnz) == offsetof(TexMapCtl, n_nodes) + 4 && kTmCtlProblem == 12, "n_nodes and nnz are adjacent");
 
 // The assembly, the solve and the assignment.  d_ids == null: the full overload; else the sub-problem over a device list of
-// n entries (dn != null: at most n).  Contains the one wait; *list_n (may be null) receives TexMapCtl::n_list as read there.
-static int tm_select(tf_volume* v, const int4* d_ids, uint32_t n, const uint32_t* dn, int32_t max_rounds, double* out_energy,
-                     int32_t* out_rounds, int64_t* out_n_nodes, uint32_t* list_n) {
+// n entries (dn != null: at most n).  Contains the one wait.
+static int tm_select(tf_volume* v, const int4* d_ids, uint32_t n, const uint32_t* dn, int32_t max_rounds, const TmWant& want) {
   TexMapState& x = v->tmx;
   const bool full = d_ids == nullptr;
   const int64_t bound = full ? x.nodes_bound : (int64_t)n;
@@ -735,15 +736,15 @@ static int tm_select(tf_volume* v, const int4* d_ids, uint32_t n, const uint32_t
   TexMapCtl* ctl = v->tm.ctl;
   int rc;
   if (bound <= 0) {  // (tsdfFusion asks num_nodes() > 0 first; `concerns.empty()` returns)
-    if (list_n) {
+    if (want.list_n) {
       TF_HIP(hipMemcpyAsync(x.h_ctl, ctl, sizeof(TexMapCtl), hipMemcpyDeviceToHost, s));
       TF_HIP(hipStreamSynchronize(s));
-      *list_n = x.h_ctl->n_list;
+      *want.list_n = x.h_ctl->n_list;
     }
     return TF_OK;
   }
-  if ((rc = tm_grow(v, &x.pn, &x.pn_cap, (size_t)bound, true))) return rc;
-  TF_HIP(hipMemsetAsync(&ctl->n_nodes, 0, 12, s));  // n_nodes, nnz
+  if ((rc = tm_room(v, true, (size_t)bound))) return rc;
+  TF_HIP(hipMemsetAsync(&ctl->n_nodes, 0, kTmCtlProblem, s));
   TmProb P = tm_prob(x);
   if (full) hipLaunchKernelGGL(k_tm_collect_all, dim3(blocks_of((size_t)v->dev.hmask + 1, 256)), dim3(256), 0, s, tm_dev(v), P);
   else hipLaunchKernelGGL(k_tm_collect_ids, dim3(blocks_of((size_t)n, 256)), dim3(256), 0, s, tm_dev(v), P, d_ids, n, dn);
@@ -753,43 +754,30 @@ static int tm_select(tf_volume* v, const int4* d_ids, uint32_t n, const uint32_t
   // the one wait: {n_nodes, nnz} size the solver's scratch and the launch grids
   TF_HIP(hipMemcpyAsync(x.h_ctl, ctl, sizeof(TexMapCtl), hipMemcpyDeviceToHost, s));
   TF_HIP(hipStreamSynchronize(s));
-  if (list_n) *list_n = x.h_ctl->n_list;
+  if (want.list_n) *want.list_n = x.h_ctl->n_list;
   const int64_t nn = std::min<int64_t>(x.h_ctl->n_nodes, (int64_t)P.cap), nnz = (int64_t)x.h_ctl->nnz;
-  if (out_n_nodes) *out_n_nodes = nn;
+  if (want.n_nodes) *want.n_nodes = nn;
   if (nn == 0) return TF_OK;
-  if ((rc = tm_grow(v, &x.pz, &x.pz_cap, (size_t)nnz, false))) return rc;
+  if ((rc = tm_room(v, false, (size_t)nnz))) return rc;
   P = tm_prob(x);
   TF_HIP(hipMemsetAsync(P.rounds, 0xFF, 16, s));  // [0] = -1: the checking launch refused the problem; [1]: started warm (k_tm_fill)
   hipLaunchKernelGGL(k_tm_fill, dim3(wave_blocks((size_t)nn)), dim3(256), 0, s, tm_dev(v), P, (uint32_t)nn, full ? 1 : 0);
   const int R = max_rounds ? max_rounds : kMrfDefaultRounds;
-  Layout L;
-  MrfScratch sc;
-  sc.take(L, nn, nnz);
-  if ((rc = reserve(v, v->scratch, L.size, 0))) return rc;
   MrfArgs a{};
   a.n = (int32_t)nn; a.nnz = nnz; a.ids = P.ids; a.nbr = P.nbr; a.col_off = reinterpret_cast<const int64_t*>(P.col_off);
   a.labels = P.labels; a.costs = P.costs; a.init = P.init; a.w = 0.5f * 1.0f;  // adjacent_cost * pairwise_cost (TexMap.h:53-54)
   a.off = P.off; a.energy = P.energy; a.rounds = P.rounds;
-  sc.bind(a, reinterpret_cast<uint8_t*>(v->scratch.d));
-  if ((rc = mrf_enqueue_start(v, a)) || (rc = mrf_enqueue_rounds(v, a, 1, R))) return rc;
+  if ((rc = mrf_begin(v, a, 0)) || (rc = mrf_enqueue_rounds(v, a, 1, R))) return rc;
   hipLaunchKernelGGL(k_tm_assign, dim3(blocks_of((size_t)nn, 256)), dim3(256), 0, s, tm_dev(v), P, (uint32_t)nn, full ? 1 : 0, a.ctl);
   TF_HIP(hipGetLastError());
   x.n = nn; x.nnz = nnz;
-  if (!out_rounds) return TF_OK;
-  // the caller wants the trace: wait for it
-  Layout H;
-  const size_t o_r = H.take(16), o_c = H.take(sizeof(MrfCtl)), o_e = H.take(8 * (size_t)(R + 1));
-  if ((rc = reserve(v, v->scratch, 0, H.size))) return rc;
-  uint8_t* h = reinterpret_cast<uint8_t*>(v->scratch.h);
-  TF_HIP(hipMemcpyAsync(h + o_r, P.rounds, 16, hipMemcpyDeviceToHost, s));
-  TF_HIP(hipMemcpyAsync(h + o_c, a.ctl, sizeof(MrfCtl), hipMemcpyDeviceToHost, s));
-  TF_HIP(hipMemcpyAsync(h + o_e, P.energy, 8 * (size_t)(R + 1), hipMemcpyDeviceToHost, s));
-  TF_HIP(hipStreamSynchronize(s));
-  const MrfCtl* mc = reinterpret_cast<const MrfCtl*>(h + o_c);
-  if (mc->bad != ~0ull) return mrf_bad_to_error(mc->bad);  // (k_tm_assign wrote nothing: labels and the solved flag are as before)
-  const int32_t rounds = *reinterpret_cast<const int32_t*>(h + o_r);
-  *out_rounds = rounds;
-  if (out_energy && rounds >= 0) memcpy(out_energy, h + o_e, 8 * (size_t)(rounds + 1));
+  if (!want.rounds) return TF_OK;
+  // the caller wants the trace: wait for it.  (A refused problem: k_tm_assign wrote nothing, labels and the solved flag are as before.)
+  if ((rc = reserve(v, v->scratch, 0, MrfResult::bytes(R)))) return rc;
+  const MrfResult* res = static_cast<const MrfResult*>(v->scratch.h);
+  if ((rc = mrf_read_back(v, a, R, static_cast<MrfResult*>(v->scratch.h)))) return rc;
+  *want.rounds = res->rounds[0];
+  if (want.energy && res->rounds[0] >= 0) memcpy(want.energy, res->energy, 8 * (size_t)(res->rounds[0] + 1));
   return TF_OK;
 }
 
@@ -802,7 +790,8 @@ int tf_texmap_view_selection(tf_volume* v, const int32_t* ids, int64_t n, int32_
   if (out_n_nodes) *out_n_nodes = 0;
   if (out_rounds) *out_rounds = 0;
   if (!v->tm.node || !v->tm.n_rows) { set_error("texmap: no keyframe table (tf_texmap_set_keyframes)"); return TF_ERR_INVALID; }
-  if (!ids) return tm_select(v, nullptr, 0, nullptr, max_rounds, out_energy, out_rounds, out_n_nodes, nullptr);
+  const TmWant want{out_energy, out_rounds, out_n_nodes, nullptr};
+  if (!ids) return tm_select(v, nullptr, 0, nullptr, max_rounds, want);
   if (n > (int64_t)v->dev.max_chunks) { set_error("chunk list longer than tf_config.max_chunks"); return TF_ERR_CAPACITY; }
   v->tmx.n = v->tmx.nnz = 0;
   if (n == 0) return TF_OK;
@@ -812,7 +801,7 @@ int tf_texmap_view_selection(tf_volume* v, const int32_t* ids, int64_t n, int32_
   Stage sg;
   if ((rc = stage_ids(v, v->scratch, (size_t)n * 16, ids, n, &sg))) return rc;
   TF_HIP(hipMemcpyAsync(v->tmx.d_ctu_raw, sg.d, (size_t)n * 16, hipMemcpyDeviceToDevice, v->stream));
-  return tm_select(v, v->tmx.d_ctu_raw, (uint32_t)n, nullptr, max_rounds, out_energy, out_rounds, out_n_nodes, nullptr);
+  return tm_select(v, v->tmx.d_ctu_raw, (uint32_t)n, nullptr, max_rounds, want);
 }
 
 // MobileFusion::tsdfFusion's tail (GCFusion/MobileFusion.cpp:330-382 without CompensateColor) in one call
@@ -820,45 +809,32 @@ int tf_texture_tail_device(tf_volume* v, int32_t frame_index, const int32_t* fra
                            int32_t max_rounds) {
   if (!v || n_frames < 0 || (n_frames > 0 && !frames_to_update) || (flags & ~7u)) { set_error("invalid argument"); return TF_ERR_INVALID; }
   if (max_rounds < 0 || max_rounds > kTmMaxRounds) { set_error("view selection: max_rounds must be 0 .. 4096"); return TF_ERR_INVALID; }
-  int rc;
-  if ((rc = tm_frame_known(v, frame_index))) return rc;
-  for (int32_t j = 0; j < n_frames; ++j)
-    if ((rc = tm_frame_known(v, frames_to_update[j]))) return rc;
+  int rc = tm_frames_known(v, frame_index, frames_to_update, n_frames);
+  if (rc) return rc;
   TF_DEV(v);
   if ((rc = tm_ensure(v)) || (rc = tm_list_buffers(v))) return rc;
   TexMapState& x = v->tmx;
   hipStream_t s = v->stream;
   x.ctu_n = 0;
-  if (flags & TF_TAIL_WRONG_MAPPING) {  // :330-342
-    TF_HIP(hipMemsetAsync(&v->tm.ctl->n_removed, 0, 4, s));
-    hipLaunchKernelGGL(k_tm_wrong_mapping, dim3(blocks_of((size_t)v->dev.hmask + 1, 256)), dim3(256), 0, s, tm_dev(v));
-  }
+  if ((flags & TF_TAIL_WRONG_MAPPING) && (rc = tm_wrong_mapping_enqueue(v))) return rc;  // :330-342
   // :345-355 chunksToUpdate + CompressMeshes; the list sorted on the device
   uint32_t bound = 0;
-  uint32_t* d_count = &v->tm.ctl->pad;
+  uint32_t* d_count = &v->tm.ctl->n_raw;
   if ((rc = compress_device_list(v, x.d_ctu_raw, v->dev.max_chunks, d_count, &bound))) return rc;
   const uint32_t rank_grid = (uint32_t)std::min<size_t>(std::max<size_t>(blocks_of(bound, 256), 1), 2048);
   hipLaunchKernelGGL(k_tm_rank, dim3(rank_grid), dim3(256), 0, s, tm_dev(v), x.d_ctu_raw, d_count, v->dev.max_chunks, x.d_ctu);
   const uint32_t* d_n = &v->tm.ctl->n_list;
-  // :356-361 (the keyframes to update travel through the pinned control block's neighbour: n_frames <= 12 in the reference)
+  // :356-361 (the keyframes to update travel through the words behind the keyframe table's rows: n_frames <= 12 in the reference)
   const int32_t* d_frames = nullptr;
-  if (n_frames) {
-    int32_t* df = nullptr;
-    if ((rc = tm_frames_upload(v, frames_to_update, n_frames, &df))) return rc;
-    d_frames = df;
-  }
+  if (n_frames && (rc = tm_frames_upload(v, frames_to_update, n_frames, &d_frames))) return rc;
   if (bound && (rc = tm_update_enqueue(v, x.d_ctu, bound, d_n, frame_index, d_frames, n_frames))) return rc;
-  if (flags & TF_TAIL_CHECK_GRAPH) {
-    TF_HIP(hipMemsetAsync(&v->tm.ctl->n_removed, 0, 4, s));
-    hipLaunchKernelGGL(k_tm_check_nodes, dim3(blocks_of((size_t)v->dev.hmask + 1, 256)), dim3(256), 0, s, tm_dev(v));
-    hipLaunchKernelGGL(k_tm_check_costs, dim3(blocks_of((size_t)v->tm.mask + 1, 256)), dim3(256), 0, s, tm_dev(v));
-  }
+  if ((flags & TF_TAIL_CHECK_GRAPH) && (rc = tm_check_graph_enqueue(v))) return rc;
   TF_HIP(hipGetLastError());
   // :362-369; its control-block read is the call's one wait and brings the list's length along
   uint32_t list_n = 0;
-  if (flags & TF_TAIL_SUB_PROBLEM) rc = tm_select(v, x.d_ctu, bound, d_n, max_rounds, nullptr, nullptr, nullptr, &list_n);
-  else rc = tm_select(v, nullptr, 0, nullptr, max_rounds, nullptr, nullptr, nullptr, &list_n);
-  if (rc) return rc;
+  const TmWant want{nullptr, nullptr, nullptr, &list_n};
+  const bool sub = (flags & TF_TAIL_SUB_PROBLEM) != 0;
+  if ((rc = tm_select(v, sub ? x.d_ctu : nullptr, sub ? bound : 0, sub ? d_n : nullptr, max_rounds, want))) return rc;
   x.ctu_n = list_n;
   // :374-382 GeneratePatches with the labels just assigned, UpdateAtlas
   return patch_stage_device(v, x.d_ctu, list_n, &v->tm.ctl->first_fail);
@@ -958,7 +934,10 @@ int tf_texmap_download_problem(tf_volume* v, int64_t cap_nodes, int64_t cap_nnz,
 int tf_texmap_clear(tf_volume* v) {
   if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
   TF_DEV(v);
-  return tm_clear(v);
+  if (!v->tm.node) return TF_OK;
+  v->tmx.nodes_bound = 0;
+  v->tmx.n = v->tmx.nnz = 0;
+  return tm_fill(v);
 }
 
 }  // extern "C"

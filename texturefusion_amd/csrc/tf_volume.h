@@ -156,18 +156,17 @@ struct AtlasState {
 struct TexMapState {
   std::vector<int32_t> kf_row;       // kflist[r].keyFrameIndex of the last tf_texmap_set_keyframes
   std::vector<int32_t> kf_inv;       // frame index -> row, -1 = none (frameIndexToKeyframeDB, MobileFusion.cpp:293-296)
-  int32_t* d_kf_row = nullptr;       // device copy of kf_row
-  size_t kf_cap = 0;
-  int32_t* h_kf = nullptr;           // pinned staging of the upload, and the event behind it
+  // device copy of kf_row + 64 spare words (the tail's keyframes to update), pinned staging of the uploads and their event
+  Scratch kf;
   hipEvent_t kf_ev = nullptr;
   int64_t nodes_bound = 0;           // chunks ever handed to tf_texmap_update: an upper bound of the node count
-  // the problem assembled last: per-node arrays (pn, room for pn_cap nodes) and per-label arrays (pz, room for pz_cap labels)
-  void* pn = nullptr;
-  void* pz = nullptr;
+  TexMapCtl* h_ctl = nullptr;        // pinned: the control block as read back; there whenever the map's device block is
+  // the problem assembled last: per-node arrays (pn, room for pn_cap nodes), per-label arrays (pz, pz_cap labels); device halves
+  Scratch pn, pz;
   size_t pn_cap = 0, pz_cap = 0;
   int64_t n = 0, nnz = 0;            // its size
-  TexMapCtl* h_ctl = nullptr;        // pinned: the control block as read back
-  // tf_texture_tail_device: chunksToUpdate as a device list (raw = as the dirty set gave it, ctu = ascending chunk id)
+  // tf_texture_tail_device: chunksToUpdate as a device list (raw = as the dirty set gave it, ctu = ascending chunk id);
+  // one allocation, d_ctu behind d_ctu_raw
   int4* d_ctu_raw = nullptr;
   int4* d_ctu = nullptr;
   int64_t ctu_n = 0;                 // its length, known since the tail's one wait

@@ -45,6 +45,12 @@ struct ChunkID {  // Eigen::Vector3i in the reference (geometry/Geometry.h)
   bool operator==(const ChunkID& o) const { return v[0] == o.v[0] && v[1] == o.v[1] && v[2] == o.v[2]; }
 };
 typedef std::vector<ChunkID> ChunkIDList;
+inline std::vector<int32_t> flat_ids(const ChunkIDList& l, std::size_t pad = 0) {  // int32[3 n + pad]: a chunk list for the C ABI
+  std::vector<int32_t> ids(l.size() * 3 + pad);
+  for (std::size_t i = 0; i < l.size(); ++i)
+    for (int a = 0; a < 3; ++a) ids[3 * i + a] = l[i](a);
+  return ids;
+}
 
 struct ChunkHasher {  // Structure/ChunkManager.h:44-53
   std::size_t operator()(const ChunkID& k) const {
@@ -1008,9 +1014,8 @@ class Chisel {
     ProjectionIntegrator dummy;
     Configure(dummy, cameraModel, false);
     const size_t n = chunksToUpdate.size();
-    std::vector<int32_t> ids(n * 3 + 3), labels(n + 1);
+    std::vector<int32_t> ids = flat_ids(chunksToUpdate, 3), labels(n + 1);
     for (size_t i = 0; i < n; ++i) {
-      for (int a = 0; a < 3; ++a) ids[3 * i + a] = chunksToUpdate[i](a);
       const int frameid = labelset.get_label(labelset.chunks.find(chunksToUpdate[i])->second);
       labels[i] = frameid;
       Frame& f = frame_list[(size_t)frameid];
@@ -1041,10 +1046,8 @@ class Chisel {
     ProjectionIntegrator dummy;
     Configure(dummy, cameraModel, false);
     const size_t n = chunksToUpdate.size();
-    std::vector<int32_t> ids(n * 3 + 3), labels(n + 1);
+    std::vector<int32_t> ids = flat_ids(chunksToUpdate, 3), labels(n + 1);
     std::vector<uint8_t> is_node(n + 1);
-    for (size_t i = 0; i < n; ++i)
-      for (int a = 0; a < 3; ++a) ids[3 * i + a] = chunksToUpdate[i](a);
     tf_check(tf_texmap_download(vol, ids.data(), (int64_t)n, is_node.data(), nullptr, labels.data(), nullptr, nullptr, nullptr,
                                 nullptr, 0), "GeneratePatches: labels");
     for (size_t i = 0; i < n; ++i) {
@@ -1083,9 +1086,7 @@ class Chisel {
   // Structure/Chisel.cpp:191-196
   void UpdateAtlas(ChunkIDList& chunksToUpdate) {
     const size_t n = chunksToUpdate.size();
-    std::vector<int32_t> ids(n * 3 + 3);
-    for (size_t i = 0; i < n; ++i)
-      for (int a = 0; a < 3; ++a) ids[3 * i + a] = chunksToUpdate[i](a);
+    const std::vector<int32_t> ids = flat_ids(chunksToUpdate, 3);
     tf_check(tf_update_atlas(vol, ids.data(), (int64_t)n), "UpdateAtlas");
     RefreshPatches(ids, n);  // Patch::ratio is written by Atlas::UpdateBuffer
     atlas.RefreshHotRows();  // Atlas::texture_buffer: what the GUI thread uploads next (MobileFusion.h:404-421)
@@ -1301,8 +1302,7 @@ class TexMap {
     for (const ChunkID& id : chunksToUpdate) chunkGraph.add_node(id);
     const int64_t n = (int64_t)chunksToUpdate.size();
     if (!n) return TF_OK;
-    std::vector<int32_t> ids((std::size_t)n * 3), edges((std::size_t)n * 6 * 4);
-    for (int64_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) ids[(std::size_t)(3 * i + a)] = chunksToUpdate[(std::size_t)i](a);
+    std::vector<int32_t> ids = flat_ids(chunksToUpdate), edges((std::size_t)n * 6 * 4);
     int64_t ne = 0;
     const int rc = tf_export_adjacency(vol, ids.data(), n, edges.data(), n * 6, &ne);
     if (rc) return rc;
@@ -1320,8 +1320,7 @@ class TexMap {
     const int64_t n = (int64_t)chunksToUpdate.size();
     if (!n) return TF_OK;
     const std::size_t m = framesToUpdate.size();
-    std::vector<int32_t> ids((std::size_t)n * 3), fr(framesToUpdate.begin(), framesToUpdate.end());
-    for (int64_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) ids[(std::size_t)(3 * i + a)] = chunksToUpdate[(std::size_t)i](a);
+    std::vector<int32_t> ids = flat_ids(chunksToUpdate), fr(framesToUpdate.begin(), framesToUpdate.end());
     std::vector<float> tab((std::size_t)n * (1 + m));
     const int rc = tf_export_datacost(vol, ids.data(), n, frameindex, fr.empty() ? nullptr : fr.data(), (int32_t)m, tab.data());
     if (rc) return rc;
@@ -1364,8 +1363,7 @@ class TexMap {
   int update_datacost_resident(ChunkIDList& chunksToUpdate, tf_volume* vol, int frameindex, std::vector<int>& framesToUpdate) {
     this->vol = vol;
     const int64_t n = (int64_t)chunksToUpdate.size();
-    std::vector<int32_t> ids((std::size_t)n * 3), fr(framesToUpdate.begin(), framesToUpdate.end());
-    for (int64_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) ids[(std::size_t)(3 * i + a)] = chunksToUpdate[(std::size_t)i](a);
+    std::vector<int32_t> ids = flat_ids(chunksToUpdate), fr(framesToUpdate.begin(), framesToUpdate.end());
     return tf_texmap_update(vol, ids.data(), n, frameindex, fr.empty() ? nullptr : fr.data(), (int32_t)fr.size());
   }
   int check_graph_resident(int64_t* n_removed = nullptr) { return tf_texmap_check_graph(vol, n_removed); }
@@ -1373,16 +1371,13 @@ class TexMap {
   int view_selection_resident() { return select_resident(nullptr, 0); }
   // the chunksToUpdate overload (:257-406)
   int view_selection_resident(ChunkIDList& chunksToUpdate) {
-    const int64_t n = (int64_t)chunksToUpdate.size();
-    std::vector<int32_t> ids((std::size_t)n * 3 + 3);
-    for (int64_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) ids[(std::size_t)(3 * i + a)] = chunksToUpdate[(std::size_t)i](a);
-    return select_resident(ids.data(), n);
+    const std::vector<int32_t> ids = flat_ids(chunksToUpdate, 3);
+    return select_resident(ids.data(), (int64_t)chunksToUpdate.size());
   }
   // UniGraph::get_label of listed chunks, from the device (0 for a chunk that is no node)
   int labels_resident(ChunkIDList& chunks, std::vector<int32_t>& out) {
     const int64_t n = (int64_t)chunks.size();
-    std::vector<int32_t> ids((std::size_t)n * 3 + 3);
-    for (int64_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) ids[(std::size_t)(3 * i + a)] = chunks[(std::size_t)i](a);
+    const std::vector<int32_t> ids = flat_ids(chunks, 3);
     out.assign((std::size_t)n, 0);
     return tf_texmap_download(vol, ids.data(), n, nullptr, nullptr, out.data(), nullptr, nullptr, nullptr, nullptr, 0);
   }
