@@ -372,15 +372,18 @@ TF_API int tf_texmap_clear(tf_volume* v);
  *   (the order the path defines for Atlas::AddPatch) and every stage reads that list.  The host waits ONCE, for the control
  *   block of the solve (which also brings the list's length); nothing else is read back -- an atlas overflow or a label
  *   without a cached keyframe stays in the status word and is reported by the next synchronising call (TF_ERR_ATLAS_FULL /
- *   TF_ERR_INVALID).  Chisel::CompensateColor (:380) is NOT part of the tail: it waits for the host's eigen-solves; it reads
- *   what GeneratePatches wrote and nothing UpdateAtlas writes, so tf_compensate_color behind the tail equals the reference's
- *   order.  Chunk ids must lie within +-2^20 per axis (the range of the chunk hash's packed key).
+ *   TF_ERR_INVALID).  Chisel::CompensateColor (:380) is part of the tail with TF_TAIL_COMPENSATE_COLOR: the device path
+ *   (tf_compensate_color_device) is enqueued behind UpdateAtlas, the tail still waits once.  CompensateColor reads what
+ *   GeneratePatches wrote and nothing UpdateAtlas writes, so that position -- and tf_compensate_color behind a tail without
+ *   the flag -- equals the reference's order.  Without the flag CompensateColor is not enqueued.
+ *   Chunk ids must lie within +-2^20 per axis (the range of the chunk hash's packed key).
  * tf_texture_tail_list   chunksToUpdate of the last tail, for the caller's DrawMeshes bookkeeping: *n = its length (known
  *   since the tail's wait: out_ids == NULL asks for nothing else and does not synchronise), out_ids = the list in
  *   ascending chunk id (synchronises). */
 #define TF_TAIL_WRONG_MAPPING 1u
 #define TF_TAIL_CHECK_GRAPH 2u
 #define TF_TAIL_SUB_PROBLEM 4u
+#define TF_TAIL_COMPENSATE_COLOR 8u
 TF_API int tf_texture_tail_device(tf_volume* v, int32_t frame_index, const int32_t* frames_to_update, int32_t n_frames,
                                   uint32_t flags, int32_t max_rounds);
 TF_API int tf_texture_tail_list(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n);
@@ -783,6 +786,21 @@ TF_API int tf_generate_patches_selected(tf_volume* v, const int32_t* ids, int64_
  *   Reductions and the per-vertex transfer run on the device, the 3x3 eigen-decompositions on the host (f64
  *   Jacobi; Eigen's own iteration is not restated, the result agrees to float rounding). */
 TF_API int tf_compensate_color(tf_volume* v, int64_t* out_n_clusters);
+/* Chisel::CompensateColor (Structure/Chisel.cpp:198-286) with nothing crossing to the host: asynchronous on the
+ * handle's stream.  d_n_clusters (device memory, may be NULL) receives the cluster count.
+ *   The semantics are tf_compensate_color's: every mesh of the map that has a patch takes part, patches with has_adjusted
+ *   are skipped, the rest is clustered by frame id; a cluster whose patches all map wrongly learns nothing (has_adjusted
+ *   stays clear) and still counts; wrongly mapped patches of a learnt cluster get has_adjusted and no labs.  The list of
+ *   patches, the clusters, both reductions, the two 3x3 eigen-decompositions per cluster (the same f64 Jacobi text as the
+ *   host path's, tf_cc_solve.h) and the transfer run as kernels; the call returns when they are enqueued.  Sums are
+ *   accumulated in f64 in an order that depends on the set of patches only (ascending chunk key, vertex index): two runs
+ *   over the same map give the same bits; against tf_compensate_color (f32 trees) labs agree to float rounding.
+ *   Its buffers (about 230 B per tf_config.max_chunks) are allocated by the first call and freed by tf_volume_reset /
+ *   tf_volume_destroy; a handle that never calls it (or the tail with TF_TAIL_COMPENSATE_COLOR) holds none. */
+TF_API int tf_compensate_color_device(tf_volume* v, uint32_t* d_n_clusters);
+/* tf_compensate_color_device with a device word of the handle's own as d_n_clusters, then tf_sync and that word read
+ *   back into *out_n_clusters: for callers (and tests) that want the count on the host and accept the wait. */
+TF_API int tf_compensate_color_device_count(tf_volume* v, int64_t* out_n_clusters);
 /* Chisel::UpdateAtlas(chunksToUpdate)  Structure/Chisel.cpp:191-196 -> Atlas::UpdateBuffer (Atlas.cpp:71-91):
  *   the keyframe ROI of every listed complete() patch is copied -- or cv::resize'd when it exceeds the slot --
  *   into the atlas. */

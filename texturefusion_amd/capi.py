@@ -38,7 +38,7 @@ SYMBOLS = (
     "tf_get_stats", "tf_profile_enable", "tf_profile_get", "tf_profile_calibrate", "tf_keyframe_unit_device", "tf_keyframe_unit_release", "tf_keyframe_unit_stats", "tf_keyframe_unit_stats_ex", "tf_observations_record", "tf_observations_retract", "tf_export_datacost", "tf_export_adjacency", "tf_debug_phase_raw", "tf_set_partition", "tf_set_partition_key", "tf_boundary_pack", "tf_boundary_pack_async",
     "tf_boundary_unpack", "tf_keyframe_cache", "tf_keyframe_cache_device", "tf_keyframe_set_pose",
     "tf_keyframe_release", "tf_atlas_patch_size", "tf_atlas_loc_next", "tf_atlas_size", "tf_meshes_upload",
-    "tf_generate_patches", "tf_compensate_color", "tf_update_atlas", "tf_draw_meshes", "tf_draw_meshes_device",
+    "tf_generate_patches", "tf_compensate_color", "tf_compensate_color_device", "tf_compensate_color_device_count", "tf_update_atlas", "tf_draw_meshes", "tf_draw_meshes_device",
     "tf_patches_download", "tf_atlas_download_rows", "tf_atlas_snapshot_rows", "tf_stream_frames_device",
     "tf_stream_frames_textured_device", "tf_get_texture_stats", "tf_integrate_frame_host", "tf_integrate_frame_host_rgb", "tf_host_frame_times", "tf_host_register", "tf_host_unregister",
     "tf_host_frame_buffers", "tf_host_frame_deferral", "tf_host_frame_set_deferral", "tf_host_frame_set_async", "tf_host_frame_fence", "tf_texture_frame_device_phase", "tf_comm_exchange_overlap", "tf_texture_frame_device", "tf_boundary_block_bytes", "tf_boundary_pack_block", "tf_boundary_pack_bands", "tf_boundary_band_bounds", "tf_boundary_pack_bands2", "tf_boundary_unpack_pair", "tf_comm_exchange_mode", "tf_comm_stats", "tf_comm_stats_ex",
@@ -175,6 +175,8 @@ def lib():
     L.tf_meshes_upload.argtypes = [vp, i32p, C.c_int64, i64p, i64p, fp, fp, fp, C.POINTER(C.c_uint32)]
     L.tf_generate_patches.argtypes = [vp, i32p, C.c_int64, i32p, u64p]
     L.tf_compensate_color.argtypes = [vp, i64p]
+    L.tf_compensate_color_device.argtypes = [vp, vp]
+    L.tf_compensate_color_device_count.argtypes = [vp, i64p]
     L.tf_update_atlas.argtypes = [vp, i32p, C.c_int64]
     L.tf_draw_meshes.argtypes = [vp, fp, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, i64p, i64p]
     L.tf_draw_meshes_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, i64p, i64p]
@@ -293,10 +295,10 @@ class Volume:
 
     def __init__(self, res, cam=None, max_chunks=1 << 17, max_list=1 << 18, max_coarse=1 << 20,
                  atlas_w=0, atlas_h=0, device=0, use_color=True, stream=None, mesh_max_vertices=0,
-                 mesh_max_triangles=0, mesh_overflow_blocks=0, mesh_blocks=0):
+                 mesh_max_triangles=0, mesh_overflow_blocks=0, mesh_blocks=0, max_keyframes=0):
         self.L = lib()
         self.h = C.c_void_p()
-        cfg = Config(device, max_chunks, max_list, max_coarse, atlas_w, atlas_h, 0, mesh_overflow_blocks, mesh_max_vertices,
+        cfg = Config(device, max_chunks, max_list, max_coarse, atlas_w, atlas_h, max_keyframes, mesh_overflow_blocks, mesh_max_vertices,
                      mesh_max_triangles, mesh_blocks)
         dims = (C.c_int32 * 3)(8, 8, 8)
         rc = self.L.tf_volume_create(dims, np.float32(res), int(use_color), C.byref(cfg), C.byref(self.h))
@@ -899,10 +901,11 @@ class Volume:
         return rc, (int(hot[0]), int(hot[1]))
 
     def texture_tail(self, frame_index, frames_to_update=(), wrong_mapping=True, check_graph=False, sub_problem=False,
-                     max_rounds=0):
-        """tf_texture_tail_device: tsdfFusion's tail in one call (one host wait)"""
+                     max_rounds=0, compensate_color=False):
+        """tf_texture_tail_device: tsdfFusion's tail in one call (one host wait); compensate_color: Chisel::CompensateColor
+        enqueued behind UpdateAtlas (TF_TAIL_COMPENSATE_COLOR)"""
         fr = np.ascontiguousarray(frames_to_update, np.int32).reshape(-1)
-        flags = (1 if wrong_mapping else 0) | (2 if check_graph else 0) | (4 if sub_problem else 0)
+        flags = (1 if wrong_mapping else 0) | (2 if check_graph else 0) | (4 if sub_problem else 0) | (8 if compensate_color else 0)
         self._ck(self.L.tf_texture_tail_device(self.h, int(frame_index), _p(fr, C.c_int32) if len(fr) else None, len(fr), flags,
                                                int(max_rounds)))
 
@@ -1125,6 +1128,13 @@ class Volume:
     def compensate_color(self):
         n = C.c_int64(0)
         self._ck(self.L.tf_compensate_color(self.h, C.byref(n)))
+        return n.value
+
+    def compensate_color_device(self):
+        """tf_compensate_color_device_count: the device path, then tf_sync and the cluster count read back through a device
+        word of the handle (for tests: tf_compensate_color_device itself waits for nothing)"""
+        n = C.c_int64(0)
+        self._ck(self.L.tf_compensate_color_device_count(self.h, C.byref(n)))
         return n.value
 
     def update_atlas(self, ids):

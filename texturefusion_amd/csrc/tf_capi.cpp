@@ -523,6 +523,7 @@ int tf_volume_destroy(tf_volume* v) {
   prof_collect(v);
   for (hipEvent_t e : v->prof_pool) hipEventDestroy(e);
   texmap_release(v);
+  cc_release(v);
   atlas_destroy(v);
   comm_destroy(v);
   for (void* p : v->allocs) hipFree(p);
@@ -571,6 +572,7 @@ int tf_volume_reset(tf_volume* v) {
   if (rc) return rc;
   TF_HIP(hipStreamSynchronize(v->stream));
   texmap_release(v);  // TexMap::clear, and its storage given back
+  cc_release(v);
   rc = init_device_state(v);
   if (rc) return rc;
   return atlas_reset(v);

@@ -804,10 +804,10 @@ int tf_texmap_view_selection(tf_volume* v, const int32_t* ids, int64_t n, int32_
   return tm_select(v, v->tmx.d_ctu_raw, (uint32_t)n, nullptr, max_rounds, want);
 }
 
-// MobileFusion::tsdfFusion's tail (GCFusion/MobileFusion.cpp:330-382 without CompensateColor) in one call
+// MobileFusion::tsdfFusion's tail (GCFusion/MobileFusion.cpp:330-382; CompensateColor with TF_TAIL_COMPENSATE_COLOR) in one call
 int tf_texture_tail_device(tf_volume* v, int32_t frame_index, const int32_t* frames_to_update, int32_t n_frames, uint32_t flags,
                            int32_t max_rounds) {
-  if (!v || n_frames < 0 || (n_frames > 0 && !frames_to_update) || (flags & ~7u)) { set_error("invalid argument"); return TF_ERR_INVALID; }
+  if (!v || n_frames < 0 || (n_frames > 0 && !frames_to_update) || (flags & ~15u)) { set_error("invalid argument"); return TF_ERR_INVALID; }
   if (max_rounds < 0 || max_rounds > kTmMaxRounds) { set_error("view selection: max_rounds must be 0 .. 4096"); return TF_ERR_INVALID; }
   int rc = tm_frames_known(v, frame_index, frames_to_update, n_frames);
   if (rc) return rc;
@@ -837,7 +837,10 @@ int tf_texture_tail_device(tf_volume* v, int32_t frame_index, const int32_t* fra
   if ((rc = tm_select(v, sub ? x.d_ctu : nullptr, sub ? bound : 0, sub ? d_n : nullptr, max_rounds, want))) return rc;
   x.ctu_n = list_n;
   // :374-382 GeneratePatches with the labels just assigned, UpdateAtlas
-  return patch_stage_device(v, x.d_ctu, list_n, &v->tm.ctl->first_fail);
+  rc = patch_stage_device(v, x.d_ctu, list_n, &v->tm.ctl->first_fail);
+  // :380 CompensateColor, enqueued: it reads what GeneratePatches wrote and nothing UpdateAtlas writes
+  if (!rc && (flags & TF_TAIL_COMPENSATE_COLOR)) rc = cc_enqueue(v, nullptr);
+  return rc;
 }
 
 int tf_texture_tail_list(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n) {

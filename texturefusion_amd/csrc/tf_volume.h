@@ -172,6 +172,11 @@ struct TexMapState {
   int64_t ctu_n = 0;                 // its length, known since the tail's one wait
 };
 
+// Device-resident CompensateColor (tf_cc.hip): its list, cluster table and partial sums in one block, null until first use
+struct CcState {
+  void* block = nullptr;
+};
+
 // RCCL communicator of the handle (tf_comm_init) and the exchange buffers
 struct CommState {
   void* comm = nullptr;  // ncclComm_t
@@ -303,6 +308,7 @@ struct tf_volume {
   tf::CommState comm;
   tf::TexMapDev tm{};   // TexMap resident on the device: null pointers until the first tf_texmap_* call
   tf::TexMapState tmx;
+  tf::CcState cc;
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
   // band counts of a frame's selection as the host sees them: pinned words [0] tag (frame epoch + 1), [1..4] FrameCtl::band_cnt
   uint32_t* h_xchg = nullptr;
@@ -392,6 +398,9 @@ void launch_tm_work_labels(tf_volume* v, uint32_t n, uint32_t* d_first_fail);
 // and UpdateAtlas over a device list of n entries, nothing read back.
 int compress_device_list(tf_volume* v, int4* d_out, uint32_t cap_out, uint32_t* d_count, uint32_t* bound);
 int patch_stage_device(tf_volume* v, const int4* d_list, uint32_t n, uint32_t* d_first_fail);
+// Chisel::CompensateColor enqueued on the handle's stream, nothing read back (tf_cc.hip); cc_release frees its buffers
+int cc_enqueue(tf_volume* v, uint32_t* d_n_clusters);
+void cc_release(tf_volume* v);
 void launch_patch_fused(tf_volume* v, const VolumeDev& d, int par, const KfDev& kf, hipStream_t s);
 inline uint64_t host_pack_id(const int32_t id[3]) {
   return ((uint64_t)((uint32_t)(id[0] + (1 << 20)) & 0x1FFFFFu) << 42) |

@@ -1082,6 +1082,16 @@ class Chisel {
       if (kv.second->m_patch) { ids.push_back(kv.first(0)); ids.push_back(kv.first(1)); ids.push_back(kv.first(2)); }
     RefreshPatches(ids, ids.size() / 3);
   }
+  // The same with nothing crossing to the host (tf_compensate_color_device): enqueued on the handle's stream; the mirror's
+  // patches are refreshed behind it (that download is this function's only wait -- a caller that renders from the device,
+  // tf_draw_meshes_device, can call tf_compensate_color_device itself and skip it).
+  void CompensateColorDevice() {
+    tf_check(tf_compensate_color_device(vol, nullptr), "CompensateColorDevice");
+    std::vector<int32_t> ids;
+    for (const auto& kv : chunkManager.GetAllMeshes())
+      if (kv.second->m_patch) { ids.push_back(kv.first(0)); ids.push_back(kv.first(1)); ids.push_back(kv.first(2)); }
+    RefreshPatches(ids, ids.size() / 3);
+  }
 
   // Structure/Chisel.cpp:191-196
   void UpdateAtlas(ChunkIDList& chunksToUpdate) {
@@ -1382,14 +1392,18 @@ class TexMap {
     return tf_texmap_download(vol, ids.data(), n, nullptr, nullptr, out.data(), nullptr, nullptr, nullptr, nullptr, 0);
   }
   int clear_resident() { return vol ? tf_texmap_clear(vol) : TF_OK; }
-  // MobileFusion.cpp:330-382 without CompensateColor as ONE device call with one host wait (tf_texture_tail_device): the
-  // wrong-mapping removal when integrateKeyframeIndex > 3, chunksToUpdate, CompressMeshes, the two updates, check_graph when
-  // keyframes moved, view_selection, GeneratePatches, UpdateAtlas.  chunksToUpdate comes back for DrawMeshes' bookkeeping.
+  // MobileFusion.cpp:330-382 as ONE device call with one host wait (tf_texture_tail_device): the wrong-mapping removal when
+  // integrateKeyframeIndex > 3, chunksToUpdate, CompressMeshes, the two updates, check_graph when keyframes moved,
+  // view_selection, GeneratePatches, UpdateAtlas and -- with compensate_color -- CompensateColor (:380) enqueued behind
+  // them (TF_TAIL_COMPENSATE_COLOR; without it the caller's Chisel::CompensateColor follows).  chunksToUpdate comes back
+  // for DrawMeshes' bookkeeping.
   // The keyframes the labels can name must be cached (tf_keyframe_cache_device / tf_keyframe_set_pose) before the call.
-  int texture_tail_resident(tf_volume* vol, int integrateKeyframeIndex, std::vector<int>& keyframesToUpdate, ChunkIDList& chunksToUpdate) {
+  int texture_tail_resident(tf_volume* vol, int integrateKeyframeIndex, std::vector<int>& keyframesToUpdate, ChunkIDList& chunksToUpdate,
+                            bool compensate_color = false) {
     this->vol = vol;
     std::vector<int32_t> fr(keyframesToUpdate.begin(), keyframesToUpdate.end());
-    const uint32_t flags = (integrateKeyframeIndex > 3 ? TF_TAIL_WRONG_MAPPING : 0u) | (fr.empty() ? 0u : TF_TAIL_CHECK_GRAPH);
+    const uint32_t flags = (integrateKeyframeIndex > 3 ? TF_TAIL_WRONG_MAPPING : 0u) | (fr.empty() ? 0u : TF_TAIL_CHECK_GRAPH) |
+                           (compensate_color ? TF_TAIL_COMPENSATE_COLOR : 0u);
     int rc = tf_texture_tail_device(vol, integrateKeyframeIndex, fr.empty() ? nullptr : fr.data(), (int32_t)fr.size(), flags, 0);
     if (rc) return rc;
     int64_t n = 0;
