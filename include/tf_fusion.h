@@ -812,7 +812,10 @@ TF_API int tf_update_atlas(tf_volume* v, const int32_t* ids, int64_t n);
  *   adj = has_adjusted && !labs.empty() ? (float)(3 x 9 bit of int((labs - texcolor) * 255) + 255) : 0, plus
  *   the index stream rebased by the running vertex count, over every mesh whose patch is complete()
  *   (Patch.cpp:191-196), in ascending chunk-id order.  _device leaves both streams in HBM (e.g. a mapped GL
- *   buffer, MobileFusion.h:404-446). */
+ *   buffer, MobileFusion.h:404-446).
+ *   Undefined in the reference, defined here: a colour delta labs - texcolor that is not a number -- the labs of
+ *   a cluster of one vertex, whose covariance is 0 / (N - 1) = 0 / 0 while has_adjusted is set all the same --
+ *   packs as a zero delta, 255 in its 9-bit field; the other fields of the vertex keep their values. */
 TF_API int tf_draw_meshes(tf_volume* v, float* vertices, uint32_t* indices, int64_t cap_vertices,
                           int64_t cap_indices, int64_t* n_vertices, int64_t* n_indices);
 TF_API int tf_draw_meshes_device(tf_volume* v, float* d_vertices, uint32_t* d_indices, int64_t cap_vertices,

@@ -1371,6 +1371,10 @@ int64_t tfo_color_compensate(int64_t n_patches, const int32_t* frame_ids, const 
 /* ===================================================================================== */
 /* f-2  Chisel::DrawMeshes (Structure/Chisel.cpp:288-355)                                 */
 /* ===================================================================================== */
+/* one 9-bit field of the colour delta (:331-336).  Undefined in the reference, defined here: a delta that is not a
+ * number -- labs of a one-vertex cluster, whose covariance is 0 / (N - 1) = 0 / 0 -- packs as a zero delta, 255;
+ * (int)(NaN * 255.0f) is an undefined conversion in C (INT_MIN on x86, 0 on gfx950). */
+static int pack_delta(float a) { return a != a ? 255 : (int)(a * 255.0f) + 255; }
 int64_t tfo_pack_vertices(int64_t n_patches, const uint8_t* complete, const uint8_t* wrong_mapping,
                           const uint8_t* labs_valid, const uint64_t* texloc, const float* ratio,
                           int atlas_w, int atlas_h, const int64_t* voff, const float* verts,
@@ -1398,9 +1402,9 @@ int64_t tfo_pack_vertices(int64_t n_patches, const uint8_t* complete, const uint
       if (labs_valid[p]) {                                   /* :330-337 */
         const float a0 = labs[3 * k] - texcolor[3 * k], a1 = labs[3 * k + 1] - texcolor[3 * k + 1],
                     a2 = labs[3 * k + 2] - texcolor[3 * k + 2];
-        int ad = (int)(a0 * 255.0f) + 255;
-        ad = (ad << 9) + (int)(a1 * 255.0f) + 255;
-        ad = (ad << 9) + (int)(a2 * 255.0f) + 255;
+        int ad = pack_delta(a0);
+        ad = (ad << 9) + pack_delta(a1);
+        ad = (ad << 9) + pack_delta(a2);
         o[5] = (float)ad;
       } else {
         o[5] = 0.0f;

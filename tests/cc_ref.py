@@ -10,8 +10,54 @@ import numpy as np
 from oracle import api as O
 
 
-def labs_exact_sums(frameid, wrong, adjusted, voff, texcolor, meshcolor):
-    """labs of every patch that is not adjusted yet (NaN where the reference writes none), has_adjusted afterwards"""
+def _eigh(A):
+    w, V = np.linalg.eigh(np.asarray(A, np.float64))
+    return np.maximum(w, 0.0), V
+
+
+def transfer_f64(cov_src, cov_tar):
+    """The transfer matrix of Chisel.cpp:247-266 as the matrix function it is,
+
+        T = f(Cs) . (Cs^1/2 Ct Cs^1/2)^1/2 . f(Cs),    f(x) = 1 / (sqrt(max(x, 0)) + 1e-2),
+
+    by numpy.linalg.eigh (LAPACK's tridiagonal QR) in f64: no line of the Jacobi text that tf_cc_solve.h and the oracle
+    share.  With Cs = U diag(w) U^T: f(Cs) = U Di U^T, Cs^1/2 Ct Cs^1/2 = U media U^T with media = D U^T Ct U D, and its
+    root is U Um Dm Um^T U^T from media = Um diag(wm) Um^T.  The four f32 roundings of tf_cc_solve.h are applied where it
+    applies them: D = f32(sqrt(w)), media rounded entry by entry and its upper triangle mirrored, Dm = f32(sqrt(wm)),
+    Di = f32(1 / (D + 1e-2)).  Where Cs has a repeated eigenvalue (Cs = 0, a grey keyframe's rank-1 Cs) eigh's U is
+    another basis of that eigenspace than Jacobi's, so media is rounded in another basis: a relative 2^-24 of entries that
+    T depends on continuously; tests/test_cc_inputs_cpu.py measures it against the Jacobi text on every cluster.
+
+    Compare labs, never T.  On a rank-deficient Cs the components of T on the null space of Cs are ill-conditioned: an
+    eigenvalue of 1e-9 where 0 is meant makes D 3e-5, media's entry there 1e-9 |Ct|, and T's component
+    Di^2 sqrt(1e-9 |Ct|) -- about 1e4 * 1e-5 = 0.1.  The vertices that receive labs = T (texcolor - mean_src) + mean_tar
+    are exactly the vertices the covariance was taken over: texcolor - mean_src has no component on the null space of
+    Cs (up to the rounding of the mean), so labs do not feel what T does TO a null-space input.  They do feel the
+    block of T that maps the range of Cs ONTO the null direction, Di_null * sqrt(eps) * Di_range: two solves fed the
+    same covariance bits agree on it (0 to 6e-8 in labs over the clusters of tests/cc_inputs.py, rank 0, 1 and 3), but
+    two summations that differ in the covariance's last bits do not where the zero eigenvalue is made of rounding
+    alone -- see the note on cluster L in tests/cc_inputs.py.
+
+    A covariance that is not finite (a one-vertex cluster: 0 / 0) gives a T of NaN, as the Jacobi text does."""
+    cs = np.asarray(cov_src, np.float32).reshape(3, 3).astype(np.float64)
+    ct = np.asarray(cov_tar, np.float32).reshape(3, 3).astype(np.float64)
+    if not (np.isfinite(cs).all() and np.isfinite(ct).all()):
+        return np.full((3, 3), np.nan, np.float32)
+    w, U = _eigh((cs + cs.T) / 2)
+    D = np.sqrt(w).astype(np.float32).astype(np.float64)
+    media = (D[:, None] * (U.T @ ct @ U) * D[None, :]).astype(np.float32)
+    media = (np.triu(media) + np.triu(media, 1).T).astype(np.float64)
+    wm, Um = _eigh(media)
+    Dm = np.sqrt(wm).astype(np.float32).astype(np.float64)
+    Di = (1.0 / (D + 1e-2)).astype(np.float32).astype(np.float64)
+    f_cs = (U * Di) @ U.T
+    root = U @ ((Um * Dm) @ Um.T) @ U.T
+    return (f_cs @ root @ f_cs).astype(np.float32)
+
+
+def labs_exact_sums(frameid, wrong, adjusted, voff, texcolor, meshcolor, solve=O.color_transfer):
+    """labs of every patch that is not adjusted yet (NaN where the reference writes none), has_adjusted afterwards;
+    solve(cov_src, cov_tar) -> T is the oracle's Jacobi text or transfer_f64"""
     tex = np.ascontiguousarray(texcolor, np.float32)
     mesh = np.ascontiguousarray(meshcolor, np.float32)
     labs = np.full_like(tex, np.nan)
@@ -30,12 +76,13 @@ def labs_exact_sums(frameid, wrong, adjusted, voff, texcolor, meshcolor):
             m = (x.astype(np.float64).sum(0) / n).astype(np.float32)
             d = x - m
             c = np.zeros((3, 3), np.float32)
-            for i in range(3):
-                for j in range(3):
-                    c[i, j] = np.float32((d[:, i] * d[:, j]).astype(np.float64).sum() / nm1)
+            with np.errstate(invalid="ignore", divide="ignore"):  # (one vertex: 0 / (N - 1) = 0 / 0, Patch.cpp:347)
+                for i in range(3):
+                    for j in range(3):
+                        c[i, j] = np.float32((d[:, i] * d[:, j]).astype(np.float64).sum() / nm1)
             mean.append(m)
             cov.append(c)
-        T = O.color_transfer(cov[0], cov[1])
+        T = np.asarray(solve(cov[0], cov[1]), np.float32).reshape(3, 3)
         for p in members:
             adj[p] = True
             if wrong[p]:

@@ -129,6 +129,12 @@ def _positions(theme, n, cam, slot, rng):
     return u, v, z
 
 
+def interior_positions(n, cam, slot, rng, z=1.1):
+    """-> f64[n, 3] (u, v, z): the "interior" theme's n image positions, all at the distance z"""
+    u, v, _ = _positions("interior", n, cam, slot, rng)
+    return np.stack([u, v, np.full(n, float(z))], -1)
+
+
 def _plane_z0(n, rng):
     """Vertices in the plane z == 0 of the axis-aligned keyframe (v_l.z == 0 exactly, v_l.x and v_l.y != 0): the
     projection is +-inf in both coordinates and clamps to a corner."""

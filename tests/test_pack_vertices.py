@@ -49,6 +49,25 @@ def test_oracle_known_answer():
     assert np.array_equal(i, [0, 0, 0])
 
 
+def test_oracle_delta_that_is_not_a_number_packs_as_a_zero_delta():
+    """labs of a one-vertex cluster are NaN (its covariance is 0 / (N - 1) = 0 / 0) and has_adjusted is set, so the
+    packer meets labs - texcolor = NaN: (int)(NaN * 255.0f) is undefined in the reference (INT_MIN on x86, 0 on
+    gfx950).  Defined here: a field whose delta is not a number packs as a zero delta, 255; the
+    fields beside it keep their values."""
+    nan = np.nan
+    tl = np.array([36 * AW + 48], np.uint64)
+    labs = [[nan, nan, nan], [0.5, nan, 0.5], [nan, 0.4, 0.6]]
+    v, i = O.pack_vertices([1], [0], [1], tl, [[1.0, 1.0]], AW, AH, [0, 3], np.ones((3, 3)), np.full((3, 3), 0.5),
+                           np.zeros((3, 3)), np.zeros((3, 2)), [[0.4, 0.5, 0.5]] * 3, labs, [0, 0], [])
+    f = lambda lab, tex: int(np.float32(np.float32(lab) - np.float32(tex)) * np.float32(255)) + 255
+    want = [(255 << 18) + (255 << 9) + 255,
+            (f(0.5, 0.4) << 18) + (255 << 9) + f(0.5, 0.5),
+            (255 << 18) + (f(0.4, 0.5) << 9) + f(0.6, 0.5)]
+    assert np.array_equal(v[:, 5], np.array(want, np.float32))
+    assert f(0.5, 0.4) == 280 and f(0.4, 0.5) == 230 and f(0.6, 0.5) == 280  # (the finite fields are not all 255)
+    assert np.isfinite(v).all() and len(i) == 0
+
+
 def test_oracle_skips_incomplete_and_rebases_indices():
     b = _batch(3, n_patches=12)
     v, i = O.pack_vertices(atlas_w=AW, atlas_h=AH, **b)

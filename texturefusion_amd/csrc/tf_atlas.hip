@@ -278,6 +278,9 @@ struct DrawPatch {
   uint32_t slot, nv, nt, flags;  // flags: bit1 wrong_mapping, bit2 labs valid
   unsigned long long vout, iout;  // output positions (running counts over the patches before this one)
 };
+// one 9-bit field of the colour delta.  A delta that is not a number (labs of a one-vertex cluster: 0 / (N - 1) = 0 / 0)
+// packs as a zero delta, 255: stated here, as in the oracle, not left to what the hardware conversion makes of a NaN
+__device__ __forceinline__ int pack_delta(const float a) { return a != a ? 255 : (int)(a * 255.0f) + 255; }
 __global__ __launch_bounds__(256) void k_draw(VolumeDev v, const DrawPatch* __restrict__ pt, float* __restrict__ out_v,
                                               uint32_t* __restrict__ out_i) {
   const DrawPatch P = pt[blockIdx.x];
@@ -306,9 +309,9 @@ __global__ __launch_bounds__(256) void k_draw(VolumeDev v, const DrawPatch* __re
       const float a0 = mesh_plane(v, rec.block, kMpLabs)[k] - mesh_plane(v, rec.block, kMpTcol)[k],
                   a1 = mesh_plane(v, rec.block, kMpLabs + 1)[k] - mesh_plane(v, rec.block, kMpTcol + 1)[k],
                   a2 = mesh_plane(v, rec.block, kMpLabs + 2)[k] - mesh_plane(v, rec.block, kMpTcol + 2)[k];
-      int ad = (int)(a0 * 255.0f) + 255;
-      ad = (ad << 9) + (int)(a1 * 255.0f) + 255;
-      ad = (ad << 9) + (int)(a2 * 255.0f) + 255;
+      int ad = pack_delta(a0);
+      ad = (ad << 9) + pack_delta(a1);
+      ad = (ad << 9) + pack_delta(a2);
       adj = (float)ad;
     }
     const float4 q0 = make_float4(mesh_plane(v, rec.block, kMpPos)[k], mesh_plane(v, rec.block, kMpPos + 1)[k],
