@@ -859,7 +859,14 @@ TF_API int tf_atlas_snapshot_rows(tf_volume* v, int64_t row0, int64_t row1, uint
  *                                T = f32 of (pose_ref^-1 * pose_new).matrix()[3x4], row-major)
  *   tf_pre_refine_keyframe       BasicAPI::refineKeyframesSIMD       BasicAPI.cpp:506-636   (depth_ref, weight_ref in
  *                                place with the reference's sequential in-place semantics; T = f32 of
- *                                (pose_new^-1 * pose_ref).matrix()[3x4]; synchronises; *rounds = passes it took) */
+ *                                (pose_new^-1 * pose_ref).matrix()[3x4]; synchronises)
+ * The two refinement passes return TF_ERR_INVALID when the width is not a multiple of 8: the reference's 8-pixel
+ *   groups run over the row end there and have no result to match (tf_set_camera takes no such width either).
+ * tf_pre_refine_keyframe reaches the sequential in-place result as a fixed point, one link of the dependency chain
+ *   per round, for any chain the image can hold: a keyframe fresh from the loader (weight 0) can take one round per
+ *   image row, and no image takes more than W * H / 8 + 1.  Rounds are queued in growing batches and the iteration
+ *   stops at the first batch whose last round changed nothing, so *rounds (may be NULL) = ROUNDS RUN, which can
+ *   exceed the chain length.  On every error return d_depth_ref and d_weight_ref are untouched. */
 /* DatasetWrapper::framePreprocess (Tools/DatasetWrapper.hpp:186-263, the loader's depth pass ahead of all of the
  *   above): raw u16 depth (device, updated in place like Frame::depth) -> readings above maximum_depth * depth_scale
  *   dropped -> metres -> cv::bilateralFilter(refined_depth, ., d = 9 (7 on MobileCPU builds), sigma_color = 0.03,

@@ -676,6 +676,8 @@ def pre_color_quality(depth, normal, rgb, cam):
     d, n = f32(depth), f32(normal)
     rgb = np.ascontiguousarray(rgb, np.uint8)
     H, W = d.shape
+    if W < 2 or H < 2:
+        raise ValueError("the 3x3 derivative reflects about the border: %dx%d has no neighbour to fold onto" % (W, H))
     q = np.zeros((H, W), np.float32)
     lib().tfo_pre_color_quality(_p(d, C.c_float), _p(n, C.c_float), _p(rgb, C.c_uint8), W, H, *_k4(cam), _p(q, C.c_float))
     return q
@@ -690,10 +692,13 @@ def pre_refine_newframe(depth_ref, depth_new, cam, T12):
 
 
 def pre_refine_keyframe(depth_ref, weight_ref, depth_new, cam, T12):
-    """-> (depth_ref, weight_ref) refined copies"""
+    """-> (depth_ref, weight_ref) refined copies.  The pass loads and stores 8 pixels at a time: the width must be a
+    multiple of 8, or the last group of a row runs into the next one and, in the last row, past the arrays"""
     r, w, d = f32(depth_ref).copy(), f32(weight_ref).copy(), f32(depth_new)
     T = f32(T12).reshape(12)
     H, W = r.shape
+    if W % 8:
+        raise ValueError("refineKeyframesSIMD steps 8 pixels at a time: width %d has no defined result" % W)
     lib().tfo_pre_refine_keyframe(_p(r, C.c_float), _p(w, C.c_float), _p(d, C.c_float), W, H, *_k4(cam), _p(T, C.c_float))
     return r, w
 

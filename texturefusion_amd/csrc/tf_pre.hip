@@ -14,7 +14,8 @@
 // 8 pixels at a time in row-major order, and its nearest-neighbour fallback reads that same map: a pixel may see
 // values earlier groups have already rewritten.  The device reproduces the sequential result as the fixed point
 // of "evaluate every pixel against the current estimate of the earlier groups' results" (dependencies only
-// point to earlier groups, so the iteration is exact after chain-depth + 1 rounds; 2-3 in practice).
+// point to earlier groups, so the iteration is exact after chain-depth + 1 rounds: 2-3 on smooth frames, up to one
+// per image row on the loader's weight 0, never more than one per group plus one).
 #include <stdlib.h>
 #include <string.h>
 
@@ -360,6 +361,7 @@ int tf_pre_refine_newframe(tf_volume* v, const float* d_depth_ref, float* d_dept
   if (!v || !d_depth_ref || !d_depth_new || !T_new_to_ref) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   const PreCam c = pre_cam(v);
+  if (c.W & 7) { set_error("tf_pre_refine_newframe: the reference's 8-pixel groups need a width that is a multiple of 8"); return TF_ERR_INVALID; }
   PreT T;
   memcpy(T.t, T_new_to_ref, sizeof(T.t));
   hipLaunchKernelGGL(k_pre_refine_newframe, pre_grid(c), dim3(256), 0, v->stream, d_depth_ref, d_depth_new, c, T);
@@ -372,6 +374,7 @@ int tf_pre_refine_keyframe(tf_volume* v, float* d_depth_ref, float* d_weight_ref
   if (!v || !d_depth_ref || !d_weight_ref || !d_depth_new || !T_ref_to_new) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   const PreCam c = pre_cam(v);
+  if (c.W & 7) { set_error("tf_pre_refine_keyframe: the reference's 8-pixel groups need a width that is a multiple of 8"); return TF_ERR_INVALID; }
   const size_t np = (size_t)c.W * c.H, bytes = np * sizeof(float);
   // scratch: original depth | estimate A | estimate B | new weight | flag
   int rc = reserve(v, v->scratch, 4 * bytes + 64, 0);
@@ -384,25 +387,32 @@ int tf_pre_refine_keyframe(tf_volume* v, float* d_depth_ref, float* d_weight_ref
   memcpy(T.t, T_ref_to_new, sizeof(T.t));
   TF_HIP(hipMemcpyAsync(orig, d_depth_ref, bytes, hipMemcpyDeviceToDevice, v->stream));
   const float* in = orig;  // round 0: nothing rewritten yet
-  int k = 0;
-  for (;; ++k) {
-    if (k >= 256) { set_error("tf_pre_refine_keyframe: the in-place dependency chain did not settle in 256 rounds"); return TF_ERR_INVALID; }
-    TF_HIP(hipMemsetAsync(flag, 0, 4, v->stream));
-    float* out = est[k & 1];
-    hipLaunchKernelGGL(k_pre_refine_keyframe, pre_grid(c), dim3(256), 0, v->stream, orig, d_weight_ref, d_depth_new, in,
-                       out, wout, c, T, flag);
-    TF_HIP(hipGetLastError());
+  // Group g reads only groups before it, so it is final after round g, and the round after the last group's
+  // compares equal: no chain the image can hold needs more than this many rounds.
+  const int64_t max_rounds = (int64_t)(np / 8) + 1;
+  // A round whose input is the fixed point rewrites the same bits, so rounds may be queued past it: batches of
+  // 1, 2, 4, ... 16 rounds, and only the LAST round of a batch reports whether it still changed anything.
+  int64_t k = 0;
+  for (int batch = 1;; batch = batch < 16 ? 2 * batch : batch) {
+    for (int b = 0; b < batch; ++b, ++k) {
+      if (b == batch - 1) TF_HIP(hipMemsetAsync(flag, 0, 4, v->stream));
+      float* out = est[k & 1];
+      hipLaunchKernelGGL(k_pre_refine_keyframe, pre_grid(c), dim3(256), 0, v->stream, orig, d_weight_ref, d_depth_new, in,
+                         out, wout, c, T, flag);
+      TF_HIP(hipGetLastError());
+      in = out;
+    }
     uint32_t h = 0;
     TF_HIP(hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, v->stream));
     TF_HIP(hipStreamSynchronize(v->stream));
-    in = out;
-    // round k compared its output with its input estimate: equal everywhere = the fixed point (round 0 compares
+    // a round compares its output with its input estimate: equal everywhere = the fixed point (round 0 compares
     // with the original depth, so a frame that changes nothing ends at once)
     if (!h) break;
+    if (k >= max_rounds) { set_error("tf_pre_refine_keyframe: no fixed point after one round per 8-pixel group"); return TF_ERR_INVALID; }
   }
   TF_HIP(hipMemcpyAsync(d_depth_ref, in, bytes, hipMemcpyDeviceToDevice, v->stream));
   TF_HIP(hipMemcpyAsync(d_weight_ref, wout, bytes, hipMemcpyDeviceToDevice, v->stream));
-  if (rounds) *rounds = k + 1;
+  if (rounds) *rounds = (int32_t)k;
   return TF_OK;
 }
 
