@@ -462,75 +462,51 @@ int atlas_init(tf_volume* v) {
   a.pw = (uint64_t)floor((double)(4800.0f * v->res));  // Atlas::SetResolution, Atlas.h:62-65
   a.ph = (uint64_t)floor((double)(3600.0f * v->res));
   if (a.pw < 1 || a.ph < 1) { set_error("voxel resolution too small for an atlas patch"); return TF_ERR_INVALID; }
-  const size_t bytes = (size_t)a.aw * a.ah * 3;
-  hipError_t e = hipMalloc((void**)&a.buf, bytes);  // Atlas.cpp:34: 13824 x 13824 x RGB8 = 573 MB
-  if (e != hipSuccess) { set_error("atlas hipMalloc failed"); return TF_ERR_HIP; }
   a.kf_cap = v->cfg.max_keyframes;
-  TF_HIP(hipMalloc((void**)&a.d_kf, sizeof(KfDev) * (size_t)a.kf_cap));
-  TF_HIP(hipMalloc((void**)&a.d_actl, sizeof(AtlasCtl)));
+  // the atlas (Atlas.cpp:34: 13824 x 13824 x RGB8 = 573 MB) and, in one block, everything else: all or nothing
+  const size_t rows = (size_t)2 * kMeshShards * mesh_shard_rows(d.max_chunks), cnt_bytes = sizeof(uint32_t) * 2 * kMeshShards * 16;
+  Layout L;
+  // (every part starts on a 256-byte boundary, as the separate allocations this block replaces did: the control block's
+  // atomics and the per-line counters share no cache line with a neighbour's data, the int4 lists stay line-aligned)
+  const auto part = [&L](size_t bytes) { return L.take((bytes + 255) & ~(size_t)255); };
+  const size_t o_kf = part(sizeof(KfDev) * (size_t)a.kf_cap), o_actl = part(sizeof(AtlasCtl));
   // two work lists: the fused flow builds the list of frame f + 1 while the patches of frame f still read theirs
-  TF_HIP(hipMalloc((void**)&a.d_work_ids, sizeof(int4) * (size_t)d.max_chunks * 2));
-  TF_HIP(hipMalloc((void**)&a.d_work_slot, sizeof(uint32_t) * (size_t)d.max_chunks * 2));
-  TF_HIP(hipMalloc((void**)&a.d_patch_list, sizeof(int4) * (size_t)2 * kMeshShards * mesh_shard_rows(d.max_chunks)));
-  TF_HIP(hipMalloc((void**)&a.d_wl_ids, sizeof(int4) * (size_t)2 * kMeshShards * mesh_shard_rows(d.max_chunks)));
-  TF_HIP(hipMalloc((void**)&a.d_wl_slot, sizeof(uint32_t) * (size_t)2 * kMeshShards * mesh_shard_rows(d.max_chunks)));
-  TF_HIP(hipMalloc((void**)&a.d_wl_cnt, sizeof(uint32_t) * 2 * kMeshShards * 16));
-  TF_HIP(hipMemset(a.d_wl_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16));
-  TF_HIP(hipMalloc((void**)&a.d_patch_cnt, sizeof(uint32_t) * 2 * kMeshShards * 16));
-  TF_HIP(hipMemset(a.d_patch_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16));
-  TF_HIP(hipHostMalloc((void**)&a.h_dirty_len, 64, hipHostMallocDefault));
-  *a.h_dirty_len = 0u;
-  TF_HIP(hipMalloc((void**)&a.d_cand, sizeof(unsigned long long) * (size_t)d.max_chunks));
+  const size_t o_work_ids = part(sizeof(int4) * (size_t)d.max_chunks * 2), o_work_slot = part(sizeof(uint32_t) * (size_t)d.max_chunks * 2);
+  const size_t o_patch_list = part(sizeof(int4) * rows), o_wl_ids = part(sizeof(int4) * rows), o_wl_slot = part(sizeof(uint32_t) * rows);
+  const size_t o_wl_cnt = part(cnt_bytes), o_patch_cnt = part(cnt_bytes), o_cand = part(sizeof(unsigned long long) * (size_t)d.max_chunks);
+  int rc;
+  if ((rc = a.buf.alloc((size_t)a.aw * a.ah * 3)) || (rc = a.block.alloc(L.size)) || (rc = a.h_dirty_len.alloc(64))) {
+    a.buf.release(); a.block.release(); a.h_dirty_len.release();
+    return rc;
+  }
+  *a.h_dirty_len.as<uint32_t>() = 0u;
+  d.atlas = a.buf.as<uint8_t>(); d.atlas_w = a.aw; d.atlas_h = a.ah; d.patch_w = (int32_t)a.pw; d.patch_h = (int32_t)a.ph;
+  d.kf_tab = a.block.as<KfDev>(o_kf); d.actl = a.block.as<AtlasCtl>(o_actl);
+  d.work_ids = a.block.as<int4>(o_work_ids); d.work_slot = a.block.as<uint32_t>(o_work_slot);
+  d.patch_list = a.block.as<int4>(o_patch_list); d.patch_cnt = a.block.as<uint32_t>(o_patch_cnt);
+  d.wl_ids = a.block.as<int4>(o_wl_ids); d.wl_slot = a.block.as<uint32_t>(o_wl_slot); d.wl_cnt = a.block.as<uint32_t>(o_wl_cnt);
+  d.cand = a.block.as<unsigned long long>(o_cand);
   KfDev blank;
   memset(&blank, 0, sizeof(blank));
   blank.kf_id = -1; blank.stride = 3;
   a.h_kf.assign((size_t)a.kf_cap, blank);
   a.kf_used.assign((size_t)a.kf_cap, 0);
-  TF_HIP(hipMemcpy(a.d_kf, a.h_kf.data(), sizeof(KfDev) * (size_t)a.kf_cap, hipMemcpyHostToDevice));
-  d.atlas = a.buf; d.atlas_w = a.aw; d.atlas_h = a.ah; d.patch_w = (int32_t)a.pw; d.patch_h = (int32_t)a.ph;
-  d.actl = a.d_actl; d.kf_tab = a.d_kf; d.work_ids = a.d_work_ids; d.work_slot = a.d_work_slot; d.patch_list = a.d_patch_list; d.patch_cnt = a.d_patch_cnt; d.cand = a.d_cand;
-  d.wl_ids = a.d_wl_ids; d.wl_slot = a.d_wl_slot; d.wl_cnt = a.d_wl_cnt;
-  return atlas_reset(v);
-}
-
-void atlas_destroy(tf_volume* v) {
-  AtlasState& a = v->atlas;
-  for (auto& kv : a.keyframes) {
-    KeyframeSlot& ks = kv.second;
-    if (ks.owned) { hipFree(ks.rgb); hipFree(ks.depth); }
-  }
-  a.keyframes.clear();
-  if (a.buf) hipFree(a.buf);
-  if (a.d_kf) hipFree(a.d_kf);
-  if (a.d_actl) hipFree(a.d_actl);
-  if (a.d_work_ids) hipFree(a.d_work_ids);
-  if (a.d_work_slot) hipFree(a.d_work_slot);
-  if (a.d_wl_ids) hipFree(a.d_wl_ids);
-  if (a.d_wl_slot) hipFree(a.d_wl_slot);
-  if (a.d_wl_cnt) hipFree(a.d_wl_cnt);
-  a.d_wl_ids = nullptr; a.d_wl_slot = nullptr; a.d_wl_cnt = nullptr;
-  if (a.d_patch_list) hipFree(a.d_patch_list);
-  if (a.d_patch_cnt) hipFree(a.d_patch_cnt);
-  if (a.h_dirty_len) hipHostFree(a.h_dirty_len);
-  a.h_dirty_len = nullptr;
-  if (a.d_cand) hipFree(a.d_cand);
-  scratch_free(a.stage);
-  a.buf = nullptr; a.d_kf = nullptr; a.d_actl = nullptr;
-  a.d_work_ids = nullptr; a.d_work_slot = nullptr; a.d_patch_list = nullptr; a.d_patch_cnt = nullptr; a.d_cand = nullptr;
+  TF_HIP(hipMemcpy(d.kf_tab, a.h_kf.data(), sizeof(KfDev) * (size_t)a.kf_cap, hipMemcpyHostToDevice));
+  return atlas_reset(v);  // (zeroes the counters)
 }
 
 int atlas_reset(tf_volume* v) {
   AtlasState& a = v->atlas;
   {
     AtlasWriteScope aw(v, -1);
-    TF_HIP(hipMemsetAsync(a.buf, 0, (size_t)a.aw * a.ah * 3, v->stream));  // Atlas.cpp:35-36
+    TF_HIP(hipMemsetAsync(v->dev.atlas, 0, (size_t)a.aw * a.ah * 3, v->stream));  // Atlas.cpp:35-36
   }
   AtlasCtl c;
   memset(&c, 0, sizeof(c));
   c.loc_min = ~0ull;
-  TF_HIP(hipMemcpyAsync(a.d_actl, &c, sizeof(c), hipMemcpyHostToDevice, v->stream));
-  TF_HIP(hipMemsetAsync(a.d_patch_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
-  TF_HIP(hipMemsetAsync(a.d_wl_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
+  TF_HIP(hipMemcpyAsync(v->dev.actl, &c, sizeof(c), hipMemcpyHostToDevice, v->stream));
+  TF_HIP(hipMemsetAsync(v->dev.patch_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
+  TF_HIP(hipMemsetAsync(v->dev.wl_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   a.fused_par = 0;
   a.fused_armed = true;
@@ -546,7 +522,7 @@ __global__ void k_kf_set(KfDev* dst, KfDev val) {
 }
 int kf_push(tf_volume* v, int slot) {
   AtlasState& a = v->atlas;
-  hipLaunchKernelGGL(k_kf_set, dim3(1), dim3(64), 0, v->stream, a.d_kf + slot, a.h_kf[(size_t)slot]);
+  hipLaunchKernelGGL(k_kf_set, dim3(1), dim3(64), 0, v->stream, v->dev.kf_tab + slot, a.h_kf[(size_t)slot]);
   TF_HIP(hipGetLastError());
   return TF_OK;
 }
@@ -562,9 +538,7 @@ static int kf_slot_for(tf_volume* v, int32_t kf_id, bool create, int* out) {
   for (int s = 0; s < v->cfg.max_keyframes; ++s)
     if (!a.kf_used[(size_t)s]) { slot = s; break; }
   if (slot < 0) { set_error("keyframe cache full (tf_config.max_keyframes)"); return TF_ERR_CAPACITY; }
-  KeyframeSlot ks;
-  ks.slot = slot;
-  a.keyframes[kf_id] = ks;
+  a.keyframes[kf_id].slot = slot;
   a.kf_used[(size_t)slot] = 1;
   KfDev& k = a.h_kf[(size_t)slot];
   memset(&k, 0, sizeof(k));
@@ -588,16 +562,16 @@ static int list_patches(tf_volume* v, std::vector<PatchRow>* rows) {
   if (rc) return rc;
   TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
   hipLaunchKernelGGL(k_list_patches, dim3(1024), dim3(256), 0, v->stream, v->dev,
-                     reinterpret_cast<PatchRow*>(a.stage.d), (uint32_t)cap);
+                     a.stage.d.as<PatchRow>(), (uint32_t)cap);
   TF_HIP(hipGetLastError());
   uint32_t n = 0;
   TF_HIP(hipMemcpyAsync(&n, &v->dev.vctl->n_tmp, 4, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   rows->resize(n);
   if (n) {
-    TF_HIP(hipMemcpyAsync(a.stage.h, a.stage.d, (size_t)n * sizeof(PatchRow), hipMemcpyDeviceToHost, v->stream));
+    TF_HIP(hipMemcpyAsync(a.stage.h.p, a.stage.d.p, (size_t)n * sizeof(PatchRow), hipMemcpyDeviceToHost, v->stream));
     TF_HIP(hipStreamSynchronize(v->stream));
-    memcpy(rows->data(), a.stage.h, (size_t)n * sizeof(PatchRow));
+    memcpy(rows->data(), a.stage.h.p, (size_t)n * sizeof(PatchRow));
     std::sort(rows->begin(), rows->end(), row_less);
   }
   return TF_OK;
@@ -614,8 +588,8 @@ static int upload_work(tf_volume* v, const int32_t* ids, const int* kfslot, int6
   int32_t* h = sg.hp<int32_t>(0);
   pack_ids(ids, n, h, kfslot);
   h[4 * n] = (int32_t)n;
-  TF_HIP(hipMemcpyAsync(a.d_work_ids, h, (size_t)n * 16, hipMemcpyHostToDevice, v->stream));
-  TF_HIP(hipMemcpyAsync(&a.d_actl->set[0].n_work, h + 4 * n, 4, hipMemcpyHostToDevice, v->stream));
+  TF_HIP(hipMemcpyAsync(v->dev.work_ids, h, (size_t)n * 16, hipMemcpyHostToDevice, v->stream));
+  TF_HIP(hipMemcpyAsync(&v->dev.actl->set[0].n_work, h + 4 * n, 4, hipMemcpyHostToDevice, v->stream));
   return TF_OK;
 }
 
@@ -641,22 +615,18 @@ int tf_keyframe_cache(tf_volume* v, int32_t kf_id, const uint8_t* rgb, const flo
   int rc = kf_slot_for(v, kf_id, true, &slot);
   if (rc) return rc;
   KeyframeSlot& ks = a.keyframes[kf_id];
-  if (!ks.owned) {
-    ks.rgb = nullptr; ks.depth = nullptr;
-    TF_HIP(hipMalloc((void**)&ks.rgb, npix * 3));
-    TF_HIP(hipMalloc((void**)&ks.depth, npix * 4));
-    ks.owned = true;
-  }
+  // the handle's copies follow the camera: a keyframe cached again after tf_set_camera gets images of the new size
+  if ((rc = fit(ks.rgb, npix * 3, v->stream)) || (rc = fit(ks.depth, npix * 4, v->stream))) return rc;
   Stage sg;
   rc = stage_begin(v, a.stage, npix * 7, npix * 7, &sg);
   if (rc) return rc;
   uint8_t* hs = sg.h;
   memcpy(hs, rgb, npix * 3);
   memcpy(hs + npix * 3, depth, npix * 4);
-  TF_HIP(hipMemcpyAsync(ks.rgb, hs, npix * 3, hipMemcpyHostToDevice, v->stream));
-  TF_HIP(hipMemcpyAsync(ks.depth, hs + npix * 3, npix * 4, hipMemcpyHostToDevice, v->stream));
-  a.h_kf[(size_t)slot].rgb = ks.rgb;
-  a.h_kf[(size_t)slot].depth = ks.depth;
+  TF_HIP(hipMemcpyAsync(ks.rgb.p, hs, npix * 3, hipMemcpyHostToDevice, v->stream));
+  TF_HIP(hipMemcpyAsync(ks.depth.p, hs + npix * 3, npix * 4, hipMemcpyHostToDevice, v->stream));
+  a.h_kf[(size_t)slot].rgb = ks.rgb.as<uint8_t>();
+  a.h_kf[(size_t)slot].depth = ks.depth.as<float>();
   a.h_kf[(size_t)slot].stride = 3;
   return kf_push(v, slot);
 }
@@ -671,9 +641,7 @@ int tf_keyframe_cache_device(tf_volume* v, int32_t kf_id, const uint8_t* d_rgb, 
   int rc = kf_slot_for(v, kf_id, true, &slot);
   if (rc) return rc;
   KeyframeSlot& ks = a.keyframes[kf_id];
-  if (ks.owned) { TF_HIP(hipStreamSynchronize(v->stream)); hipFree(ks.rgb); hipFree(ks.depth); ks.owned = false; }
-  ks.rgb = const_cast<uint8_t*>(d_rgb);
-  ks.depth = const_cast<float*>(d_depth);
+  if (ks.rgb) { TF_HIP(hipStreamSynchronize(v->stream)); ks.rgb.release(); ks.depth.release(); }  // the caller's images from here on
   a.h_kf[(size_t)slot].rgb = d_rgb;
   a.h_kf[(size_t)slot].depth = d_depth;
   a.h_kf[(size_t)slot].stride = rgb_pixel_stride;
@@ -697,7 +665,6 @@ int tf_keyframe_release(tf_volume* v, int32_t kf_id) {
   auto it = a.keyframes.find(kf_id);
   if (it == a.keyframes.end()) return TF_OK;
   TF_HIP(hipStreamSynchronize(v->stream));
-  if (it->second.owned) { hipFree(it->second.rgb); hipFree(it->second.depth); }
   const int slot = it->second.slot;
   a.keyframes.erase(it);
   a.kf_used[(size_t)slot] = 0;
@@ -726,7 +693,7 @@ int tf_atlas_loc_next(tf_volume* v, uint64_t* loc_next) {
   TF_DEV(v);
   AtlasState& a = v->atlas;
   AtlasCtl c;
-  TF_HIP(hipMemcpyAsync(&c, a.d_actl, sizeof(c), hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(&c, v->dev.actl, sizeof(c), hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   unsigned long long tl = 0;
   slot_texloc(a.aw, a.ah, (int)a.pw, (int)a.ph, c.n_slots, &tl);
@@ -802,8 +769,8 @@ int tf_generate_patches(tf_volume* v, const int32_t* ids, int64_t n, const int32
   hipLaunchKernelGGL((k_patch<true, false, false>), dim3(1024), dim3(256), 0, v->stream, v->dev, v->cam, 0, KfDev{});
   prof_end(v);
   TF_HIP(hipGetLastError());
-  AtlasCtl* hc = reinterpret_cast<AtlasCtl*>(reinterpret_cast<uint8_t*>(a.stage.h) + o_ctl);
-  TF_HIP(hipMemcpyAsync(hc, a.d_actl, sizeof(AtlasCtl), hipMemcpyDeviceToHost, v->stream));
+  AtlasCtl* hc = a.stage.h.as<AtlasCtl>(o_ctl);
+  TF_HIP(hipMemcpyAsync(hc, v->dev.actl, sizeof(AtlasCtl), hipMemcpyDeviceToHost, v->stream));
   rc = sync_status(v, nullptr);
   const AtlasCtl c = *hc;
   if (out_hot && c.n_done > 0) {  // Chisel.cpp:184-186
@@ -834,14 +801,14 @@ int tf_generate_patches_selected(tf_volume* v, const int32_t* ids, int64_t n, ui
   if (rc) return rc;
   a.fused_armed = false;
   hipLaunchKernelGGL(k_work_lookup, dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, v->stream, v->dev, (uint32_t)n);
-  launch_tm_work_labels(v, (uint32_t)n, reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(a.stage.d) + o_ff));
+  launch_tm_work_labels(v, (uint32_t)n, a.stage.d.as<uint32_t>(o_ff));
   hipLaunchKernelGGL(k_patch_assign, dim3(1), dim3(1024), 0, v->stream, v->dev, (uint32_t)n);
   prof_begin(v, TF_PROF_PATCH_PROJECT);
   hipLaunchKernelGGL((k_patch<true, false, false>), dim3(1024), dim3(256), 0, v->stream, v->dev, v->cam, 0, KfDev{});
   prof_end(v);
   TF_HIP(hipGetLastError());
-  AtlasCtl* hc = reinterpret_cast<AtlasCtl*>(reinterpret_cast<uint8_t*>(a.stage.h) + o_ctl);
-  TF_HIP(hipMemcpyAsync(hc, a.d_actl, sizeof(AtlasCtl), hipMemcpyDeviceToHost, v->stream));
+  AtlasCtl* hc = a.stage.h.as<AtlasCtl>(o_ctl);
+  TF_HIP(hipMemcpyAsync(hc, v->dev.actl, sizeof(AtlasCtl), hipMemcpyDeviceToHost, v->stream));
   rc = sync_status(v, nullptr);
   const AtlasCtl c = *hc;
   if (out_hot && c.n_done > 0) {  // Chisel.cpp:184-186
@@ -859,7 +826,7 @@ int tf::patch_stage_device(tf_volume* v, const int4* d_list, uint32_t n, uint32_
   AtlasState& a = v->atlas;
   if (!n) return TF_OK;
   if (n > v->dev.max_chunks) { set_error("chunk list longer than tf_config.max_chunks"); return TF_ERR_CAPACITY; }
-  TF_HIP(hipMemcpyAsync(a.d_work_ids, d_list, (size_t)n * 16, hipMemcpyDeviceToDevice, v->stream));
+  TF_HIP(hipMemcpyAsync(v->dev.work_ids, d_list, (size_t)n * 16, hipMemcpyDeviceToDevice, v->stream));
   a.fused_armed = false;
   hipLaunchKernelGGL(k_work_lookup, dim3((n + 255u) / 256u), dim3(256), 0, v->stream, v->dev, n);
   launch_tm_work_labels(v, n, d_first_fail);
@@ -1104,24 +1071,21 @@ int tf_atlas_snapshot_rows(tf_volume* v, int64_t row0, int64_t row1, uint8_t* ds
     TF_HIP(hipStreamCreateWithFlags(&v->read_stream, hipStreamNonBlocking));
     TF_HIP(hipEventCreateWithFlags(&v->read_ev, hipEventDisableTiming));
   }
-  if (bytes > v->d_snap_bytes) {  // (grows by doubling; the free waits for the device once per growth)
-    size_t want = std::max<size_t>(64 * step, 1);
-    while (want < bytes) want <<= 1;
-    if (v->d_snap) { TF_HIP(hipStreamSynchronize(v->read_stream)); TF_HIP(hipFree(v->d_snap)); v->d_snap = nullptr; v->d_snap_bytes = 0; }
-    TF_HIP(hipMalloc((void**)&v->d_snap, want));
-    v->d_snap_bytes = want;
-  }
+  size_t want = std::max<size_t>(64 * step, 1);  // (grows by doubling; the free waits for the reader's stream once per growth)
+  while (want < bytes) want <<= 1;
+  const int rc = fit(v->snap, want, v->read_stream);
+  if (rc) return rc;
   uint64_t seq = 0;
   int32_t fid = -1;
   {
     std::lock_guard<std::mutex> lk(v->atlas_mu);
-    if (bytes) TF_HIP(hipMemcpyAsync(v->d_snap, a.buf + (size_t)row0 * step, bytes, hipMemcpyDeviceToDevice, v->stream));
+    if (bytes) TF_HIP(hipMemcpyAsync(v->snap.p, v->dev.atlas + (size_t)row0 * step, bytes, hipMemcpyDeviceToDevice, v->stream));
     TF_HIP(hipEventRecord(v->read_ev, v->stream));
     seq = v->atlas_seq.load(std::memory_order_acquire);
     fid = v->atlas_frame.load(std::memory_order_relaxed);
   }
   TF_HIP(hipStreamWaitEvent(v->read_stream, v->read_ev, 0));
-  if (bytes) TF_HIP(hipMemcpyAsync(dst, v->d_snap, bytes, hipMemcpyDeviceToHost, v->read_stream));
+  if (bytes) TF_HIP(hipMemcpyAsync(dst, v->snap.p, bytes, hipMemcpyDeviceToHost, v->read_stream));
   TF_HIP(hipStreamSynchronize(v->read_stream));
   if (write_seq) *write_seq = (int64_t)seq;
   if (frame_id) *frame_id = fid;
@@ -1135,7 +1099,7 @@ int tf_atlas_download_rows(tf_volume* v, int64_t row0, int64_t row1, uint8_t* ds
   if (row0 < 0 || row1 > a.ah || row0 > row1) { set_error("row range outside the atlas"); return TF_ERR_INVALID; }
   const size_t step = (size_t)a.aw * 3;
   if (row1 == row0) return TF_OK;
-  TF_HIP(hipMemcpyAsync(dst, a.buf + (size_t)row0 * step, (size_t)(row1 - row0) * step,
+  TF_HIP(hipMemcpyAsync(dst, v->dev.atlas + (size_t)row0 * step, (size_t)(row1 - row0) * step,
                         hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   return TF_OK;

@@ -49,47 +49,25 @@ static size_t pow2_at_least(size_t x) {
 
 template <typename T>
 static int dev_alloc(tf_volume* v, T** p, size_t count) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, count * sizeof(T));
-  if (e != hipSuccess) {
-    set_error(std::string("hipMalloc(") + std::to_string(count * sizeof(T)) + " B): " + hipGetErrorString(e));
-    return TF_ERR_HIP;
-  }
-  v->allocs.push_back(q);
-  *p = reinterpret_cast<T*>(q);
+  DevMem m;
+  const int rc = m.alloc(count * sizeof(T));
+  if (rc) return rc;
+  *p = m.as<T>();
+  v->allocs.push_back(std::move(m));
   return TF_OK;
 }
 
 int reserve(tf_volume* v, Scratch& s, size_t dev_bytes, size_t host_bytes) {
-  const bool grow_d = dev_bytes > s.d_bytes, grow_h = host_bytes > s.h_bytes;
-  if ((grow_d && s.d) || (grow_h && s.h)) TF_HIP(hipStreamSynchronize(v->stream));
-  if (grow_d) {
-    if (s.d) TF_HIP(hipFree(s.d));
-    s.d = nullptr; s.d_bytes = 0;
-    TF_HIP(hipMalloc(&s.d, pow2_at_least(dev_bytes)));
-    s.d_bytes = pow2_at_least(dev_bytes);
-  }
-  if (grow_h) {
-    if (s.h) TF_HIP(hipHostFree(s.h));
-    s.h = nullptr; s.h_bytes = 0;
-    TF_HIP(hipHostMalloc(&s.h, pow2_at_least(host_bytes), hipHostMallocDefault));
-    s.h_bytes = pow2_at_least(host_bytes);
-  }
-  return TF_OK;
-}
-
-void scratch_free(Scratch& s) {
-  if (s.d) hipFree(s.d);
-  if (s.h) hipHostFree(s.h);
-  s = Scratch{};
+  const int rc = dev_bytes ? fit(s.d, pow2_at_least(dev_bytes), v->stream) : TF_OK;  // (0 bytes: that half is not asked for)
+  return rc || !host_bytes ? rc : fit(s.h, pow2_at_least(host_bytes), v->stream);
 }
 
 int stage_begin(tf_volume* v, Scratch& s, size_t dev_bytes, size_t host_bytes, Stage* st) {
   int rc = reserve(v, s, dev_bytes, host_bytes);
   if (rc) return rc;
   TF_HIP(hipStreamSynchronize(v->stream));
-  st->h = reinterpret_cast<uint8_t*>(s.h);
-  st->d = reinterpret_cast<uint8_t*>(s.d);
+  st->h = s.h.as<uint8_t>();
+  st->d = s.d.as<uint8_t>();
   return TF_OK;
 }
 
@@ -108,9 +86,9 @@ int stage_ids(tf_volume* v, Scratch& s, size_t bytes, const int32_t* ids, int64_
 }
 
 int download_ids(tf_volume* v, const Scratch& s, int64_t m, int32_t* out) {
-  TF_HIP(hipMemcpyAsync(s.h, s.d, (size_t)m * 16, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(s.h.p, s.d.p, (size_t)m * 16, hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  unpack_ids(reinterpret_cast<const int32_t*>(s.h), m, out);
+  unpack_ids(s.h.as<int32_t>(), m, out);
   return TF_OK;
 }
 
@@ -201,12 +179,13 @@ struct CtlSnap {
   VolCtl vc;
 };
 static int fetch_ctl(tf_volume* v, CtlSnap* out) {
-  if (!v->h_ctl) TF_HIP(hipHostMalloc((void**)&v->h_ctl, sizeof(FrameCtl) + sizeof(VolCtl), hipHostMallocDefault));
-  launch_export_ctl(v->dev.sel.ctl, v->dev.vctl, v->h_ctl, v->stream);
+  const int rc = fit(v->h_ctl, sizeof(FrameCtl) + sizeof(VolCtl), v->stream);
+  if (rc) return rc;
+  launch_export_ctl(v->dev.sel.ctl, v->dev.vctl, v->h_ctl.as<uint32_t>(), v->stream);
   TF_HIP(hipGetLastError());
   TF_HIP(hipStreamSynchronize(v->stream));
-  memcpy(&out->f, v->h_ctl, sizeof(FrameCtl));  // (without the pull counters)
-  memcpy(&out->vc, reinterpret_cast<const uint8_t*>(v->h_ctl) + sizeof(FrameCtl), sizeof(VolCtl));
+  memcpy(&out->f, v->h_ctl.p, sizeof(FrameCtl));  // (without the pull counters)
+  memcpy(&out->vc, v->h_ctl.as<uint8_t>(sizeof(FrameCtl)), sizeof(VolCtl));
   if (out->vc.status) {
     TF_HIP(hipMemsetAsync(&v->dev.vctl->status, 0, sizeof(uint32_t), v->stream));
     return status_to_error(out->vc.status);
@@ -269,24 +248,28 @@ static void discard_primed(tf_volume* v) {
 }
 
 }  // namespace tf (the two functions below are shared with tf_unit.hip: declared in tf_volume.h)
+int tf::xchg_words(tf_volume* v) {
+  if (v->h_xchg) return TF_OK;
+  const int rc = v->h_xchg.alloc(64);
+  if (!rc) memset(v->h_xchg.p, 0, 64);
+  return rc;
+}
 int tf::xchg_band_counts(tf_volume* v, const tf::FrameCtl* ctl, uint32_t tag, uint32_t cnt[4], hipStream_t s) {
   using namespace tf;
   if (!s) s = v->stream;
-  if (!v->h_xchg) {
-    TF_HIP(hipHostMalloc((void**)&v->h_xchg, 64, hipHostMallocDefault));
-    memset(v->h_xchg, 0, 64);
-  }
+  const int rc = xchg_words(v);
+  if (rc) return rc;
   if (v->xchg_pub_enq != tag) {  // nobody published this frame's counts behind an earlier exchange: do it now
     // (the word the host waits for is a publish SEQUENCE number, never reused: a frame that replaces a discarded selection
     // has the same epoch tag as the frame it replaces, and the old publish may still sit in the pinned word)
     const uint32_t seq = ++v->xchg_seq;
-    launch_xchg_publish(ctl, v->h_xchg, seq, s);
+    launch_xchg_publish(ctl, v->h_xchg.as<uint32_t>(), seq, s);
     TF_HIP(hipGetLastError());
     v->xchg_pub_enq = tag;
     v->xchg_pub_seq = seq;
   }
   // the publishing launch sits behind the selection on the stream; the words arrive with a system-scope release
-  volatile uint32_t* w = v->h_xchg;
+  volatile uint32_t* w = v->h_xchg.as<uint32_t>();
   const uint32_t want = v->xchg_pub_seq;
   const auto t0 = std::chrono::steady_clock::now();
   for (uint64_t spin = 0; __atomic_load_n(&w[0], __ATOMIC_ACQUIRE) != want; ++spin) {
@@ -522,47 +505,27 @@ int tf_volume_destroy(tf_volume* v) {
   tf_keyframe_unit_release(v);
   prof_collect(v);
   for (hipEvent_t e : v->prof_pool) hipEventDestroy(e);
-  texmap_release(v);
-  cc_release(v);
-  render_release(v);
-  atlas_destroy(v);
+  texmap_release(v);  // (its event)
   comm_destroy(v);
-  for (void* p : v->allocs) hipFree(p);
-  if (v->d_depth) hipFree(v->d_depth);
-  if (v->d_rgba) hipFree(v->d_rgba);
-  if (v->d_quality) hipFree(v->d_quality);
-  scratch_free(v->scratch);
-  if (v->d_group) hipFree(v->d_group);
-  if (v->h_ctl) hipHostFree(v->h_ctl);
-  if (v->h_progress) hipHostFree(v->h_progress);
-  v->h_progress = nullptr;
-  if (v->h_xchg) hipHostFree(v->h_xchg);
-  v->h_xchg = nullptr;
-  if (v->xstream) { hipStreamSynchronize(v->xstream); hipStreamDestroy(v->xstream); v->xstream = nullptr; }
-  if (v->read_stream) { hipStreamSynchronize(v->read_stream); hipStreamDestroy(v->read_stream); v->read_stream = nullptr; }
-  if (v->read_ev) { hipEventDestroy(v->read_ev); v->read_ev = nullptr; }
-  if (v->d_snap) { hipFree(v->d_snap); v->d_snap = nullptr; }
-  if (v->ev_fork) { hipEventDestroy(v->ev_fork); v->ev_fork = nullptr; }
-  if (v->ev_join) { hipEventDestroy(v->ev_join); v->ev_join = nullptr; }
+  if (v->xstream) { hipStreamSynchronize(v->xstream); hipStreamDestroy(v->xstream); }
+  if (v->read_stream) { hipStreamSynchronize(v->read_stream); hipStreamDestroy(v->read_stream); }
+  if (v->read_ev) hipEventDestroy(v->read_ev);
+  if (v->ev_fork) hipEventDestroy(v->ev_fork);
+  if (v->ev_join) hipEventDestroy(v->ev_join);
   for (const tf_volume::HostRange& r : v->host_ranges) (void)host_range_release(r.locked);
-  v->host_ranges.clear();
-  for (int k = 0; k < tf_volume::kHostRing; ++k) {
-    if (v->hslot[k].h) hipHostFree(v->hslot[k].h);
-    if (v->hslot[k].d) hipFree(v->hslot[k].d);
+  for (int k = 0; k < tf_volume::kHostRing; ++k)
     if (v->hslot[k].copied) hipEventDestroy(v->hslot[k].copied);
-  }
   if (v->host_trace[5] > 0 && getenv("TF_HOST_TRACE") && atoi(getenv("TF_HOST_TRACE")))
     fprintf(stderr, "tf host frames: %.0f calls; per call us: wait kernels %.1f, wait upload %.1f, staging copy %.1f, "
                     "upload enqueue %.1f, launches %.1f; copies a launch waited for in the stream: %ld\n", v->host_trace[5],
             v->host_trace[0] / v->host_trace[5], v->host_trace[1] / v->host_trace[5], v->host_trace[2] / v->host_trace[5],
             v->host_trace[3] / v->host_trace[5], v->host_trace[4] / v->host_trace[5], v->host_waits);
   delete v->copy_pool;
-  v->copy_pool = nullptr;
   if (v->copy_stream) hipStreamDestroy(v->copy_stream);
   if (v->copy_stream2) hipStreamDestroy(v->copy_stream2);
   if (v->copy_join) hipEventDestroy(v->copy_join);
   if (v->own_stream && v->stream) hipStreamDestroy(v->stream);
-  delete v;
+  delete v;  // every device and pinned allocation of the handle is a member that frees itself (tf_mem.h)
   return TF_OK;
 }
 
@@ -632,34 +595,28 @@ int tf_frame_upload(tf_volume* v, const float* depth, const uint8_t* rgba, const
   if (!v || !depth) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
   const size_t npix = (size_t)v->cam.W * v->cam.H;
-  if (v->img_pixels != npix) {
-    TF_HIP(hipStreamSynchronize(v->stream));
-    if (v->d_depth) hipFree(v->d_depth);
-    if (v->d_rgba) hipFree(v->d_rgba);
-    if (v->d_quality) hipFree(v->d_quality);
-    v->d_depth = nullptr; v->d_rgba = nullptr; v->d_quality = nullptr;
-    TF_HIP(hipMalloc((void**)&v->d_depth, npix * 4));
-    TF_HIP(hipMalloc((void**)&v->d_rgba, npix * 4));
-    TF_HIP(hipMalloc((void**)&v->d_quality, npix * 4));
-    v->img_pixels = npix;
-  }
-  const FrameStaging fs(npix);
+  const FrameStaging fs(npix);  // (the device images lie as the staging does; npix * 4 is a multiple of 16: the width is one of 8)
+  int rc = fit(v->images, fs.size, v->stream);
+  if (rc) return rc;
+  float* const d_depth = v->images.as<float>(fs.depth);
+  uint8_t* const d_rgba = v->images.as<uint8_t>(fs.rgba);
+  float* const d_quality = v->images.as<float>(fs.quality);
   Stage sg;
-  int rc = stage_begin(v, v->scratch, 0, fs.size, &sg);
+  rc = stage_begin(v, v->scratch, 0, fs.size, &sg);
   if (rc) return rc;
   memcpy(sg.h + fs.depth, depth, npix * 4);
-  TF_HIP(hipMemcpyAsync(v->d_depth, sg.h + fs.depth, npix * 4, hipMemcpyHostToDevice, v->stream));
+  TF_HIP(hipMemcpyAsync(d_depth, sg.h + fs.depth, npix * 4, hipMemcpyHostToDevice, v->stream));
   if (rgba) {
     memcpy(sg.h + fs.rgba, rgba, npix * 4);
-    TF_HIP(hipMemcpyAsync(v->d_rgba, sg.h + fs.rgba, npix * 4, hipMemcpyHostToDevice, v->stream));
+    TF_HIP(hipMemcpyAsync(d_rgba, sg.h + fs.rgba, npix * 4, hipMemcpyHostToDevice, v->stream));
   }
   if (quality) {
     memcpy(sg.h + fs.quality, quality, npix * 4);
-    TF_HIP(hipMemcpyAsync(v->d_quality, sg.h + fs.quality, npix * 4, hipMemcpyHostToDevice, v->stream));
+    TF_HIP(hipMemcpyAsync(d_quality, sg.h + fs.quality, npix * 4, hipMemcpyHostToDevice, v->stream));
   }
-  v->frame.depth = v->d_depth;
-  v->frame.rgba = rgba ? reinterpret_cast<const uchar4*>(v->d_rgba) : nullptr;
-  v->frame.quality = quality ? v->d_quality : nullptr;
+  v->frame.depth = d_depth;
+  v->frame.rgba = rgba ? reinterpret_cast<const uchar4*>(d_rgba) : nullptr;
+  v->frame.quality = quality ? d_quality : nullptr;
   v->frame_bound = true;
   return TF_OK;
 }
@@ -678,14 +635,15 @@ int tf_frame_upload_rgb(tf_volume* v, const float* depth, const uint8_t* rgb, co
   rc = reserve(v, v->scratch, npix * 4, 0);
   if (rc) return rc;
   // (tf_frame_upload synchronised before its copies, none of which reads the rgba block)
-  uint8_t* st = reinterpret_cast<uint8_t*>(v->scratch.h) + fs.rgba;
+  uint8_t* st = v->scratch.h.as<uint8_t>() + fs.rgba;
   memcpy(st, rgb, npix * 3);
   memcpy(st + npix * 3, color_valid, npix);
-  uint8_t* dt = reinterpret_cast<uint8_t*>(v->scratch.d);
+  uint8_t* dt = v->scratch.d.as<uint8_t>();
   TF_HIP(hipMemcpyAsync(dt, st, npix * 4, hipMemcpyHostToDevice, v->stream));
-  launch_pack_rgba(dt, dt + npix * 3, reinterpret_cast<uchar4*>(v->d_rgba), (uint32_t)npix, v->stream);
+  uchar4* const d_rgba = v->images.as<uchar4>(fs.rgba);
+  launch_pack_rgba(dt, dt + npix * 3, d_rgba, (uint32_t)npix, v->stream);
   TF_HIP(hipGetLastError());
-  v->frame.rgba = reinterpret_cast<const uchar4*>(v->d_rgba);
+  v->frame.rgba = d_rgba;
   return TF_OK;
 }
 
@@ -720,7 +678,7 @@ int tf_prepare(tf_volume* v, const float pose[12], int32_t* out_ids, uint8_t* ou
   rc = launch_prepare(v, P, true);
   if (rc) return rc;
   TF_HIP(hipGetLastError());
-  int32_t* st = reinterpret_cast<int32_t*>(v->scratch.h);
+  int32_t* st = v->scratch.h.as<int32_t>();
   uint8_t* stn = reinterpret_cast<uint8_t*>(st + 4 * cap_list);
   launch_export_list(v->dev, reinterpret_cast<int4*>(st), stn, (uint32_t)cap_list, v->stream);
   TF_HIP(hipGetLastError());
@@ -837,17 +795,13 @@ int tf_integrate_depth_group_host(tf_volume* v, int32_t n_frames, const float* c
   if (n_frames < 1 || n_frames > 6) { set_error("a keyframe group holds 1..6 local frames"); return TF_ERR_INVALID; }
   TF_DEV(v);
   const size_t npix = (size_t)v->cam.W * v->cam.H;
-  if (v->d_group_pixels != npix) {
-    if (v->d_group) hipFree(v->d_group);
-    v->d_group = nullptr;
-    TF_HIP(hipMalloc((void**)&v->d_group, 6 * npix * sizeof(float)));
-    v->d_group_pixels = npix;
-  }
-  const float* dd[6];
+  const int rc = fit(v->group, 6 * npix * sizeof(float), v->stream);
+  if (rc) return rc;
+  float* dd[6];
   for (int f = 0; f < n_frames; ++f) {
     if (!depth[f]) { set_error("null depth image"); return TF_ERR_INVALID; }
-    dd[f] = v->d_group + (size_t)f * npix;
-    TF_HIP(hipMemcpyAsync(v->d_group + (size_t)f * npix, depth[f], npix * sizeof(float), hipMemcpyHostToDevice, v->stream));
+    dd[f] = v->group.as<float>() + (size_t)f * npix;
+    TF_HIP(hipMemcpyAsync(dd[f], depth[f], npix * sizeof(float), hipMemcpyHostToDevice, v->stream));
   }
   return tf_integrate_depth_group(v, n_frames, dd, poses12, ids, n, integrate_flag, inout_needs_update);
 }
@@ -908,9 +862,9 @@ int tf::fused_arm(tf_volume* v) {
   // first textured frame after a reset / a call-by-call atlas call: empty work lists
   AtlasCtl::Set z[2];
   memset(z, 0, sizeof(z));
-  TF_HIP(hipMemcpyAsync(&a.d_actl->set[0], z, sizeof(z), hipMemcpyHostToDevice, v->stream));
-  TF_HIP(hipMemsetAsync(a.d_patch_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
-  TF_HIP(hipMemsetAsync(a.d_wl_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
+  TF_HIP(hipMemcpyAsync(&v->dev.actl->set[0], z, sizeof(z), hipMemcpyHostToDevice, v->stream));
+  TF_HIP(hipMemsetAsync(v->dev.patch_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
+  TF_HIP(hipMemsetAsync(v->dev.wl_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   a.fused_par = 0;
   a.fused_armed = true;
@@ -963,8 +917,8 @@ int tf::texture_stage(tf_volume* v, const SelBuf& sel, const FrameImages& img, u
     a.fused_par ^= 1;
     VolumeDev d = v->dev;
     d.sel = sel;
-    d.work_ids = a.d_work_ids + (size_t)par * d.max_chunks;
-    d.work_slot = a.d_work_slot + (size_t)par * d.max_chunks;
+    d.work_ids = v->dev.work_ids + (size_t)par * d.max_chunks;
+    d.work_slot = v->dev.work_slot + (size_t)par * d.max_chunks;
     prof_begin(v, TF_PROF_MESH);
     d.seq = nbr_next_seq(v);
     launch_mesh(d, v->mesh_par, d.work_ids, &d.actl->set[par].n_work, d.max_chunks, ++v->mesh_epoch, v->res, true, par ^ 1, 0u, nullptr, par,
@@ -988,8 +942,8 @@ int tf::texture_stage(tf_volume* v, const SelBuf& sel, const FrameImages& img, u
   if (phase != 1) a.fused_par ^= 1;  // (phase 1: the caller's unpack still appends to this parity's list)
   VolumeDev d = v->dev;
   d.sel = sel;
-  d.work_ids = a.d_work_ids + (size_t)par * d.max_chunks;
-  d.work_slot = a.d_work_slot + (size_t)par * d.max_chunks;
+  d.work_ids = v->dev.work_ids + (size_t)par * d.max_chunks;
+  d.work_slot = v->dev.work_slot + (size_t)par * d.max_chunks;
   prof_begin(v, TF_PROF_DIRTY);
   // meshesToUpdate = everything marked since CompressMeshes last cleared it (Chisel.h:192-208, Chisel.cpp:146).  In a
   // textured stream that is this frame's chunks (stamps <= frame_epoch are cleared); after frames integrated without
@@ -1000,7 +954,7 @@ int tf::texture_stage(tf_volume* v, const SelBuf& sel, const FrameImages& img, u
   prof_end(v);
   // (the filter's form follows the dirty-list length of an earlier frame: the kernel leaves it in host-visible memory,
   // read here without any synchronisation -- whatever value is there is good enough)
-  const uint32_t len_guess = a.h_dirty_len ? *reinterpret_cast<volatile uint32_t*>(a.h_dirty_len) : 0u;
+  const uint32_t len_guess = a.h_dirty_len ? *a.h_dirty_len.as<volatile uint32_t>() : 0u;
   const PatchStage prev = a.pend_patch.st;  // (copied: the pending record is overwritten below)
   // one filter + mesher pass over the frame's dirty set (cls: every chunk / interior chunks only / boundary chunks only);
   // the shard lists of this parity are walked in any case: empty when K-A did not claim -- the previous frame's mesher
@@ -1013,7 +967,7 @@ int tf::texture_stage(tf_volume* v, const SelBuf& sel, const FrameImages& img, u
     std::unique_ptr<AtlasWriteScope> aw;  // (a patch stage riding on the filter launch writes atlas texels)
     if (with_ride) aw.reset(new AtlasWriteScope(v, prev.kf.kf_id));
     const bool rode = launch_mesh(d, v->mesh_par, d.work_ids, flat_count, d.max_chunks, ++v->mesh_epoch, v->res, true, par ^ 1,
-                                  len_guess, with_hint ? a.h_dirty_len : nullptr, par, v->stream, with_ride ? &prev : nullptr,
+                                  len_guess, with_hint ? a.h_dirty_len.as<uint32_t>() : nullptr, par, v->stream, with_ride ? &prev : nullptr,
                                   &v->cam, cls, store);
     aw.reset();
     store = nullptr;  // (once)
@@ -1182,7 +1136,7 @@ static int enqueue_frames(tf_volume* v, int64_t n, int64_t n_ahead, const float*
     // wave walks ten chunks and the claim's dependent hops add up behind each of them (hall: k_frame 250 -> 296 us for
     // 26 us of k_dirty_frame, profiles/r3): decided by the length of an earlier frame's dirty list, which the mesher's
     // filter leaves in host-visible memory (no synchronisation; any value gives correct results).
-    const uint32_t dirty_hint = v->atlas.h_dirty_len ? *reinterpret_cast<volatile uint32_t*>(v->atlas.h_dirty_len) : 0u;
+    const uint32_t dirty_hint = v->atlas.h_dirty_len ? *v->atlas.h_dirty_len.as<volatile uint32_t>() : 0u;
     static const uint32_t small_max = getenv("TF_SMALL_FRAME") ? (uint32_t)atoi(getenv("TF_SMALL_FRAME")) : 20000u;
     const bool small_frame = dirty_hint <= small_max;
     if (hc) cur.small_frame = small_frame;
@@ -1199,11 +1153,11 @@ static int enqueue_frames(tf_volume* v, int64_t n, int64_t n_ahead, const float*
     if (hc) prof_begin(v, TF_PROF_INTEGRATE);
     if (carry) {  // (the launch writes atlas texels: ordered against tf_atlas_snapshot_rows)
       AtlasWriteScope aw(v, pp.st.kf.kf_id);
-      launch_frame(v->dev, &cur, hn ? &nxt : nullptr, h2 ? &nx2 : nullptr, &pp.st, v->cam, v->ig, v->res, v->stream, v->h_progress,
+      launch_frame(v->dev, &cur, hn ? &nxt : nullptr, h2 ? &nx2 : nullptr, &pp.st, v->cam, v->ig, v->res, v->stream, v->h_progress.as<uint32_t>(),
                    &v->progress_seq);
     } else {
       launch_frame(v->dev, hc ? &cur : nullptr, hn ? &nxt : nullptr, h2 ? &nx2 : nullptr, nullptr, v->cam, v->ig, v->res, v->stream,
-                   v->h_progress, &v->progress_seq);
+                   v->h_progress.as<uint32_t>(), &v->progress_seq);
     }
     if (hc) prof_end(v);
     if (carry) { int rc = patch_launched(v); if (rc) return rc; }
@@ -1259,7 +1213,7 @@ static int host_slot_done(tf_volume* v, int slot) {
 // stream is drained instead.
 static int host_slot_wait(tf_volume* v, tf_volume::HostSlot& s) {
   if (!s.free_when) return TF_OK;
-  volatile uint32_t* p = v->h_progress;
+  volatile uint32_t* p = v->h_progress.as<uint32_t>();
   if ((int32_t)(v->progress_seq - s.free_when) < 0) {  // no launch that would stamp it is on the stream
     TF_HIP(hipStreamSynchronize(v->stream));
     s.free_when = 0;
@@ -1351,22 +1305,20 @@ int tf_stream_frames_textured_device(tf_volume* v, int64_t n_frames, int64_t n_a
 static int host_ring_prepare(tf_volume* v) {
   const size_t npix = (size_t)v->cam.W * v->cam.H;
   if (v->hslot_pixels == npix && v->copy_stream) return TF_OK;
+  v->hslot_pixels = 0;  // not ready until every slot below fits
   TF_HIP(hipStreamSynchronize(v->stream));
   if (!v->copy_stream) TF_HIP(hipStreamCreateWithFlags(&v->copy_stream, hipStreamNonBlocking));
   TF_HIP(hipStreamSynchronize(v->copy_stream));
+  int rc;
   for (int k = 0; k < tf_volume::kHostRing; ++k) {
     tf_volume::HostSlot& s = v->hslot[k];
-    if (s.h) hipHostFree(s.h);
-    if (s.d) hipFree(s.d);
-    s.h = nullptr; s.d = nullptr;
-    TF_HIP(hipHostMalloc((void**)&s.h, npix * 8, hipHostMallocDefault));
-    TF_HIP(hipMalloc((void**)&s.d, npix * 12));  // depth | colour as uploaded (RGBA, or RGB + valid flags) | RGBA packed from an RGB upload
+    if ((rc = fit(s.h, npix * 8, v->stream)) || (rc = fit(s.d, npix * 12, v->stream))) return rc;
     if (!s.copied) TF_HIP(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
     s.free_when = 0;  // (both streams were drained above)
   }
   if (!v->h_progress) {
-    TF_HIP(hipHostMalloc((void**)&v->h_progress, 64, hipHostMallocDefault));
-    *v->h_progress = v->progress_seq;
+    if ((rc = v->h_progress.alloc(64))) return rc;
+    *v->h_progress.as<uint32_t>() = v->progress_seq;
   }
   v->hslot_pixels = npix;
   v->hslot_next = 0;
@@ -1469,8 +1421,8 @@ int tf_host_frame_buffers(tf_volume* v, float** depth, uint8_t** rgba) {
   if (rc) return rc;
   tf_volume::HostSlot& s = v->hslot[v->hslot_next];
   TF_HIP(hipEventSynchronize(s.copied));  // the previous upload out of this slot has left the host buffer
-  *depth = reinterpret_cast<float*>(s.h);
-  *rgba = s.h + v->hslot_pixels * 4;
+  *depth = s.h.as<float>();
+  *rgba = s.h.as<uint8_t>(v->hslot_pixels * 4);
   return TF_OK;
 }
 
@@ -1552,8 +1504,9 @@ static int integrate_frame_host_impl(tf_volume* v, const float* depth, const uin
   lap(0, t);
   TF_HIP(hipEventSynchronize(s.copied));
   lap(1, t);
-  float* hd = reinterpret_cast<float*>(s.h);
-  uint8_t* hc = s.h + npix * 4;
+  uint8_t* const sd = s.d.as<uint8_t>();
+  float* hd = s.h.as<float>();
+  uint8_t* hc = s.h.as<uint8_t>(npix * 4);
   // images inside registered caller buffers (tf_host_register) go up straight from there
   auto registered = [&](const void* q, size_t n) {
     const uint8_t* b = static_cast<const uint8_t*>(q);
@@ -1600,7 +1553,7 @@ static int integrate_frame_host_impl(tf_volume* v, const float* depth, const uin
   // frames on a shared one; profiles/r4/README.md, run s13)
   if (direct) {
     // (depth and colour are two caller arrays = two copies.  The link moves 2.46 MB as ONE copy in 53 us -- 46 GB/s,
-    // page-locked by hipHostMalloc or in place alike, tools/h2d_probe.py --; as two copies of 1.2 MB it takes 60 us when
+    // allocated page-locked or page-locked in place alike, tools/h2d_probe.py --; as two copies of 1.2 MB it takes 60 us when
     // they travel side by side on two copy queues and 66 us one behind the other on one queue (profiles/r5/README.md).  A
     // kernel that fetches the images itself -- 16-byte loads out of the mapped pages -- was no faster than the DMA
     // transfers and slowed the step kernels it ran next to: 100 -> 125 us per frame, profiles/r4/README.md)
@@ -1609,27 +1562,27 @@ static int integrate_frame_host_impl(tf_volume* v, const float* depth, const uin
         TF_HIP(hipStreamCreateWithFlags(&v->copy_stream2, hipStreamNonBlocking));
         TF_HIP(hipEventCreateWithFlags(&v->copy_join, hipEventDisableTiming));
       }
-      TF_HIP(hipMemcpyAsync(s.d + npix * 4, rgba, npix * 4, hipMemcpyHostToDevice, v->copy_stream2));
+      TF_HIP(hipMemcpyAsync(sd + npix * 4, rgba, npix * 4, hipMemcpyHostToDevice, v->copy_stream2));
       TF_HIP(hipEventRecord(v->copy_join, v->copy_stream2));
-      TF_HIP(hipMemcpyAsync(s.d, depth, npix * 4, hipMemcpyHostToDevice, v->copy_stream));
+      TF_HIP(hipMemcpyAsync(sd, depth, npix * 4, hipMemcpyHostToDevice, v->copy_stream));
       TF_HIP(hipStreamWaitEvent(v->copy_stream, v->copy_join, 0));
     } else {
-      TF_HIP(hipMemcpyAsync(s.d, depth, npix * 4, hipMemcpyHostToDevice, v->copy_stream));
+      TF_HIP(hipMemcpyAsync(sd, depth, npix * 4, hipMemcpyHostToDevice, v->copy_stream));
     }
     if (rgb) {
-      TF_HIP(hipMemcpyAsync(s.d + npix * 4, rgb, npix * 3, hipMemcpyHostToDevice, v->copy_stream));
-      if (color_valid) TF_HIP(hipMemcpyAsync(s.d + npix * 7, color_valid, npix, hipMemcpyHostToDevice, v->copy_stream));
-      launch_pack_rgba(s.d + npix * 4, color_valid ? s.d + npix * 7 : nullptr, reinterpret_cast<uchar4*>(s.d + npix * 8), (uint32_t)npix,
+      TF_HIP(hipMemcpyAsync(sd + npix * 4, rgb, npix * 3, hipMemcpyHostToDevice, v->copy_stream));
+      if (color_valid) TF_HIP(hipMemcpyAsync(sd + npix * 7, color_valid, npix, hipMemcpyHostToDevice, v->copy_stream));
+      launch_pack_rgba(sd + npix * 4, color_valid ? sd + npix * 7 : nullptr, reinterpret_cast<uchar4*>(sd + npix * 8), (uint32_t)npix,
                        v->copy_stream);
       TF_HIP(hipGetLastError());
     }
   } else {
     {
       const size_t up = rgba ? npix * 8 : (rgb ? (color_valid ? npix * 8 : npix * 7) : npix * 4);
-      TF_HIP(hipMemcpyAsync(s.d, s.h, up, hipMemcpyHostToDevice, v->copy_stream));
+      TF_HIP(hipMemcpyAsync(sd, s.h.p, up, hipMemcpyHostToDevice, v->copy_stream));
     }
     if (rgb) {  // rgba = valid ? (r, g, b, 1) : 0, behind the upload on the copy stream (null flags: every pixel valid)
-      launch_pack_rgba(s.d + npix * 4, color_valid ? s.d + npix * 7 : nullptr, reinterpret_cast<uchar4*>(s.d + npix * 8), (uint32_t)npix,
+      launch_pack_rgba(sd + npix * 4, color_valid ? sd + npix * 7 : nullptr, reinterpret_cast<uchar4*>(sd + npix * 8), (uint32_t)npix,
                        v->copy_stream);
       TF_HIP(hipGetLastError());
     }
@@ -1637,8 +1590,8 @@ static int integrate_frame_host_impl(tf_volume* v, const float* depth, const uin
   TF_HIP(hipEventRecord(s.copied, v->copy_stream));
   lap(3, t);
   tf_volume::Pending cur;
-  cur.d = reinterpret_cast<const float*>(s.d);
-  cur.c = rgba ? s.d + npix * 4 : (rgb ? s.d + npix * 8 : nullptr);
+  cur.d = reinterpret_cast<const float*>(sd);
+  cur.c = rgba ? sd + npix * 4 : (rgb ? sd + npix * 8 : nullptr);
   memcpy(cur.pose, pose, sizeof(cur.pose));
   cur.tex = pose_inv16 != nullptr;
   if (pose_inv16) memcpy(cur.pinv, pose_inv16, sizeof(cur.pinv));
@@ -1751,17 +1704,17 @@ int tf_get_texture_stats(tf_volume* v, tf_texture_stats* out) {
   memset(out, 0, sizeof(*out));
   int rc = reserve(v, v->scratch, 64, 0);
   if (rc) return rc;
-  TF_HIP(hipMemsetAsync(v->scratch.d, 0, 48, v->stream));
+  TF_HIP(hipMemsetAsync(v->scratch.d.p, 0, 48, v->stream));
   {
     const int par = v->atlas.fused_par ^ 1;
     VolumeDev d = v->dev;
-    d.work_ids = v->atlas.d_work_ids + (size_t)par * d.max_chunks;
-    d.work_slot = v->atlas.d_work_slot + (size_t)par * d.max_chunks;
-    launch_texture_stats(d, par, reinterpret_cast<unsigned long long*>(v->scratch.d), v->stream);
+    d.work_ids = v->dev.work_ids + (size_t)par * d.max_chunks;
+    d.work_slot = v->dev.work_slot + (size_t)par * d.max_chunks;
+    launch_texture_stats(d, par, v->scratch.d.as<unsigned long long>(), v->stream);
   }
   TF_HIP(hipGetLastError());
   unsigned long long r[6];
-  TF_HIP(hipMemcpyAsync(r, v->scratch.d, 48, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(r, v->scratch.d.p, 48, hipMemcpyDeviceToHost, v->stream));
   AtlasCtl c;
   TF_HIP(hipMemcpyAsync(&c, v->dev.actl, sizeof(c), hipMemcpyDeviceToHost, v->stream));
   uint32_t mc[kMeshCntWords];  // the counters of the last mesher launch: rows per shard | {exact tests, rows with a surface cell} per shard
@@ -1851,7 +1804,7 @@ static int list_common(tf_volume* v, bool dirty, int32_t* out_ids, int64_t cap, 
   if (cap < 0) cap = 0;
   int rc = reserve(v, v->scratch, (size_t)cap * 16 + 16, (size_t)cap * 16 + 16);
   if (rc) return rc;
-  int4* list = reinterpret_cast<int4*>(v->scratch.d);
+  int4* list = v->scratch.d.as<int4>();
   TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
   if (dirty) launch_list_dirty(v->dev, list, (uint32_t)cap, v->clear_floor, v->stream);
   else launch_list_chunks(v->dev, list, (uint32_t)cap, v->stream);
@@ -1888,11 +1841,11 @@ int tf_get_stats(tf_volume* v, tf_stats* out) {
   memset(out, 0, sizeof(*out));
   int rc = reserve(v, v->scratch, 64, 0);
   if (rc) return rc;
-  TF_HIP(hipMemsetAsync(v->scratch.d, 0, 32, v->stream));
-  launch_rowstats(v->dev, reinterpret_cast<unsigned long long*>(v->scratch.d), v->stream);
+  TF_HIP(hipMemsetAsync(v->scratch.d.p, 0, 32, v->stream));
+  launch_rowstats(v->dev, v->scratch.d.as<unsigned long long>(), v->stream);
   TF_HIP(hipGetLastError());
   unsigned long long r3[4];
-  TF_HIP(hipMemcpyAsync(r3, v->scratch.d, 32, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(r3, v->scratch.d.p, 32, hipMemcpyDeviceToHost, v->stream));
   CtlSnap ctl;
   rc = fetch_ctl(v, &ctl);
   if (rc) return rc;
@@ -2124,8 +2077,8 @@ static int unpack_blocks(tf_volume* v, const void* d_blocks, int32_t n_blocks, i
     int rc = fused_arm(v);
     if (rc) return rc;
     par = v->atlas.fused_par;
-    d.work_ids = v->atlas.d_work_ids + (size_t)par * d.max_chunks;
-    d.work_slot = v->atlas.d_work_slot + (size_t)par * d.max_chunks;
+    d.work_ids = v->dev.work_ids + (size_t)par * d.max_chunks;
+    d.work_slot = v->dev.work_slot + (size_t)par * d.max_chunks;
   }
   launch_boundary_unpack_blocks(d, reinterpret_cast<const uint8_t*>(d_blocks), n_blocks, own_block,
                                 (uint32_t)cap_records, par, v->epoch, v->stream, reinterpret_cast<const uint8_t*>(d_block_b),

@@ -299,23 +299,19 @@ int cc_ensure(tf_volume* v) {
   if (v->cc.block) return TF_OK;
   size_t bytes = 0;
   cc_carve(nullptr, v->dev.max_chunks, &bytes);
-  TF_HIP(hipMalloc(&v->cc.block, bytes));
-  return TF_OK;
+  return v->cc.block.alloc(bytes);
 }
 
 }  // namespace
 
-void cc_release(tf_volume* v) {
-  if (v->cc.block) hipFree(v->cc.block);
-  v->cc = CcState{};
-}
+void cc_release(tf_volume* v) { v->cc = CcState{}; }
 
 // Chisel::CompensateColor enqueued on the handle's stream: no wait, nothing read back
 int cc_enqueue(tf_volume* v, uint32_t* d_n_clusters) {
   const size_t mc = v->dev.max_chunks;
   const int rc = cc_ensure(v);
   if (rc) return rc;
-  const CcdDev c = cc_carve(v->cc.block, mc, nullptr);
+  const CcdDev c = cc_carve(v->cc.block.p, mc, nullptr);
   hipStream_t s = v->stream;
   const unsigned per_thread = (unsigned)std::min<size_t>(std::max<size_t>((mc + 255) / 256, 1), kCcdGrid);
   TF_HIP(hipMemsetAsync(c.ctl, 0, 16, s));  // n_raw, n, n_clusters, tmask
@@ -350,7 +346,7 @@ int tf_compensate_color_device_count(tf_volume* v, int64_t* out_n_clusters) {
   TF_DEV(v);
   int rc = cc_ensure(v);
   if (rc) return rc;
-  uint32_t* d_word = &cc_carve(v->cc.block, v->dev.max_chunks, nullptr).ctl->n_out;
+  uint32_t* d_word = &cc_carve(v->cc.block.p, v->dev.max_chunks, nullptr).ctl->n_out;
   if ((rc = cc_enqueue(v, d_word)) || (rc = tf_sync(v))) return rc;
   uint32_t n = 0;
   TF_HIP(hipMemcpy(&n, d_word, 4, hipMemcpyDeviceToHost));

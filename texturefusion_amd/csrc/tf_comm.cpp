@@ -84,9 +84,10 @@ static int comm_check_partition(tf_volume* v) {
   ncclComm_t comm = reinterpret_cast<ncclComm_t>(c.comm);
   const int n = c.nranks;
   int32_t mine[8] = {v->dev.part_lo, v->dev.part_hi, v->dev.part_a, v->dev.part_b, v->dev.part_c, 0, 0, 0};
-  int32_t* d_buf = nullptr;
-  TF_HIP(hipMalloc((void**)&d_buf, sizeof(mine) * (size_t)(n + 1)));
-  struct Free { int32_t* p; ~Free() { if (p) hipFree(p); } } guard{d_buf};  // (also on the error returns below)
+  DevMem buf;  // (freed on the error returns below too)
+  const int rc = buf.alloc(sizeof(mine) * (size_t)(n + 1));
+  if (rc) return rc;
+  int32_t* d_buf = buf.as<int32_t>();
   TF_HIP(hipMemcpyAsync(d_buf, mine, sizeof(mine), hipMemcpyHostToDevice, v->stream));
   TF_NCCL(g_rccl.AllGather(d_buf, d_buf + 8, sizeof(mine), ncclUint8, comm, v->stream));
   std::vector<int32_t> all((size_t)8 * n);
@@ -109,15 +110,13 @@ static int comm_check_partition(tf_volume* v) {
 static int comm_buffers(tf_volume* v, int64_t cap_records) {
   CommState& c = v->comm;
   const size_t block = tf_boundary_block_bytes(cap_records);
-  if (c.cap_records >= cap_records && c.d_send) return TF_OK;
-  TF_HIP(hipStreamSynchronize(v->stream));
-  if (c.d_send) hipFree(c.d_send);
-  if (c.d_recv) hipFree(c.d_recv);
-  c.d_send = c.d_recv = nullptr;
-  TF_HIP(hipMalloc(&c.d_send, block * 2));  // all-gather: one block; neighbours: the down block, then the up block
-  TF_HIP(hipMalloc(&c.d_recv, block * (size_t)(c.nranks > 2 ? c.nranks : 2)));
+  if (c.cap_records >= cap_records && c.send) return TF_OK;
+  c.cap_records = 0;  // (the blocks are laid out for cap_records: not usable until both buffers fit)
+  const size_t recv_bytes = block * (size_t)(c.nranks > 2 ? c.nranks : 2);
+  int rc;  // send: one block for the all-gather; for neighbours the down block, then the up block
+  if ((rc = fit(c.send, block * 2, v->stream)) || (rc = fit(c.recv, recv_bytes, v->stream))) return rc;
   // (a receive slot without a neighbour is never written: its count stays zero, no memset per exchange)
-  TF_HIP(hipMemset(c.d_recv, 0, block * (size_t)(c.nranks > 2 ? c.nranks : 2)));
+  TF_HIP(hipMemset(c.recv.p, 0, recv_bytes));
   c.cap_records = cap_records;
   return TF_OK;
 }
@@ -140,8 +139,8 @@ int comm_exchange(tf_volume* v, int64_t cap_records, int dirty_par, uint32_t sta
   if (rc) return rc;
   const size_t block = tf_boundary_block_bytes(c.cap_records);
   ncclComm_t comm = reinterpret_cast<ncclComm_t>(c.comm);
-  uint8_t* send = reinterpret_cast<uint8_t*>(c.d_send);
-  uint8_t* recv = reinterpret_cast<uint8_t*>(c.d_recv);
+  uint8_t* send = c.send.as<uint8_t>();
+  uint8_t* recv = c.recv.as<uint8_t>();
   int nblocks = c.nranks, skip = c.rank;
   bool neighbours = c.mode == TF_XCHG_NEIGHBOURS && g_rccl.Send && g_rccl.Recv && g_rccl.GroupStart && g_rccl.GroupEnd;
   if (neighbours && !c.checked) {  // slabs wide enough and in rank order?  (one tiny all-gather, once per partition)
@@ -151,8 +150,8 @@ int comm_exchange(tf_volume* v, int64_t cap_records, int dirty_par, uint32_t sta
   neighbours = neighbours && c.neighbours_ok;
   VolumeDev d = v->dev;
   if (dirty_par >= 0) {
-    d.work_ids = v->atlas.d_work_ids + (size_t)dirty_par * d.max_chunks;
-    d.work_slot = v->atlas.d_work_slot + (size_t)dirty_par * d.max_chunks;
+    d.work_ids = v->dev.work_ids + (size_t)dirty_par * d.max_chunks;
+    d.work_slot = v->dev.work_slot + (size_t)dirty_par * d.max_chunks;
   }
   struct ProfScope {  // HIP events around the whole exchange when tf_profile_enable asked for TF_PROF_XCHG
     tf_volume* v;
@@ -195,13 +194,10 @@ int comm_exchange(tf_volume* v, int64_t cap_records, int dirty_par, uint32_t sta
     // (the launch that stores the ghosts also tells the host the NEXT frame's band counts: that frame's selection ran
     // next to this frame's voxel update, so the next exchange finds its sizes waiting)
     const bool pub = ctl && next_ctl;
-    if (pub && !v->h_xchg) {
-      TF_HIP(hipHostMalloc((void**)&v->h_xchg, 64, hipHostMallocDefault));
-      memset(v->h_xchg, 0, 64);
-    }
+    if (pub && (rc = xchg_words(v))) return rc;
     const uint32_t pub_seq = pub ? ++v->xchg_seq : 0u;  // (a sequence number of its own: see xchg_band_counts)
     launch_boundary_unpack_blocks(d, recv, 2, -1, cap_lo, dirty_par, stamp, s, recv + block, cap_hi,
-                                  pub ? next_ctl : nullptr, pub ? v->h_xchg : nullptr, pub_seq);
+                                  pub ? next_ctl : nullptr, pub ? v->h_xchg.as<uint32_t>() : nullptr, pub_seq);
     if (pub) { v->xchg_pub_enq = tag + 1u; v->xchg_pub_seq = pub_seq; }
   } else {
     rc = boundary_pack_block_on(v, send, c.cap_records, s);
@@ -221,8 +217,6 @@ int comm_exchange(tf_volume* v, int64_t cap_records, int dirty_par, uint32_t sta
 void comm_destroy(tf_volume* v) {
   CommState& c = v->comm;
   if (c.comm && g_rccl.CommDestroy) g_rccl.CommDestroy(reinterpret_cast<ncclComm_t>(c.comm));
-  if (c.d_send) hipFree(c.d_send);
-  if (c.d_recv) hipFree(c.d_recv);
   c = CommState();
 }
 

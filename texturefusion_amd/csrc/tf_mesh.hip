@@ -1331,7 +1331,7 @@ int dirty_list_enqueue(tf_volume* v) {
   const size_t cap = (size_t)v->dev.max_chunks;
   int rc = reserve(v, v->scratch, cap * 16 + 16, 0);
   if (rc) return rc;
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->scratch.d);
+  uint8_t* db = v->scratch.d.as<uint8_t>();
   TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
   launch_list_dirty(v->dev, reinterpret_cast<int4*>(db + 16), (uint32_t)cap, v->clear_floor, v->stream);
   TF_HIP(hipGetLastError());
@@ -1403,7 +1403,7 @@ int tf_update_meshes(tf_volume* v, int64_t* n_meshed) {
   if (rc) return rc;
   // (the launches take the list's length from the device word: no synchronisation between the scan and the mesher; an
   // empty list costs two empty launches)
-  const uint8_t* db = reinterpret_cast<const uint8_t*>(v->scratch.d);
+  const uint8_t* db = v->scratch.d.as<const uint8_t>();
   prof_begin(v, TF_PROF_MESH);
   (void)nbr_next_seq(v);
   launch_mesh(v->dev, v->mesh_par, reinterpret_cast<const int4*>(db + 16), reinterpret_cast<const uint32_t*>(db), v->dev.max_chunks,
@@ -1428,7 +1428,7 @@ int tf_list_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n) {
   int rc = reserve(v, v->scratch, (size_t)cap * 16 + 16, (size_t)cap * 16 + 16);
   if (rc) return rc;
   TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
-  hipLaunchKernelGGL(k_list_meshes, dim3(1024), dim3(256), 0, v->stream, v->dev, reinterpret_cast<int4*>(v->scratch.d),
+  hipLaunchKernelGGL(k_list_meshes, dim3(1024), dim3(256), 0, v->stream, v->dev, v->scratch.d.as<int4>(),
                      (uint32_t)cap);
   TF_HIP(hipGetLastError());
   uint32_t cnt = 0;
@@ -1522,7 +1522,7 @@ int tf_compress_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n_o
   int rc = TF_OK;
   // (the call before this one was tf_update_meshes -- or a keyframe unit without its texture stage, which leaves the list in the
   // same place but, being asynchronous, not its length on the host: dirty_list_n == ~0u)
-  const bool have_list = v->dirty_list_seq + 1 == v->call_seq && v->scratch.d;
+  const bool have_list = v->dirty_list_seq + 1 == v->call_seq && v->scratch.d.p;
   if (!have_list) { rc = dirty_list_enqueue(v); if (rc) return rc; }
   const bool known_n = have_list && v->dirty_list_n != ~0u;
   const uint32_t cap_list = v->dev.max_chunks;
@@ -1532,7 +1532,7 @@ int tf_compress_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n_o
   if (cap_host) {
     rc = reserve(v, v->scratch, 0, cap_host * 16);  // (the host half only: the device half holds the list)
     if (rc) return rc;
-    uint8_t* db = reinterpret_cast<uint8_t*>(v->scratch.d);
+    uint8_t* db = v->scratch.d.as<uint8_t>();
     const int4* list = reinterpret_cast<const int4*>(db + 16);
     const uint32_t* cnt = reinterpret_cast<const uint32_t*>(db);
     launch_compress(v->dev, list, cnt, cap_list, true, v->stream);
@@ -1540,14 +1540,14 @@ int tf_compress_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n_o
     TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, v->stream));
     const uint32_t grid = known_n ? (v->dirty_list_n + 255u) / 256u : 1024u;
     hipLaunchKernelGGL(k_dirty_with_mesh, dim3(grid ? grid : 1u), dim3(256), 0, v->stream, v->dev, list, cnt, cap_list,
-                       reinterpret_cast<int4*>(v->scratch.h), (uint32_t)cap_host);
+                       v->scratch.h.as<int4>(), (uint32_t)cap_host);
     TF_HIP(hipGetLastError());
     uint32_t got = 0;
     rc = sync_status(v, &got);
     if (rc) return rc;
     m = got < cap_host ? got : (int64_t)cap_host;
     // ascending id (std::set<ChunkID> order): one 64-bit key per id, x most significant
-    const int32_t* hid = reinterpret_cast<const int32_t*>(v->scratch.h);
+    const int32_t* hid = v->scratch.h.as<const int32_t>();
     std::vector<unsigned long long> keys((size_t)m);
     bool wide = false;
     for (int64_t i = 0; i < m; ++i) {
@@ -1590,12 +1590,12 @@ int tf_compress_meshes(tf_volume* v, int32_t* out_ids, int64_t cap, int64_t* n_o
 // tf_compress_meshes without its host half (tf_texture_tail_device): the list stays on the device, unsorted
 int tf::compress_device_list(tf_volume* v, int4* d_out, uint32_t cap_out, uint32_t* d_count, uint32_t* bound) {
   int rc = TF_OK;
-  const bool have_list = v->dirty_list_seq + 1 == v->call_seq && v->scratch.d;
+  const bool have_list = v->dirty_list_seq + 1 == v->call_seq && v->scratch.d.p;
   if (!have_list) { rc = dirty_list_enqueue(v); if (rc) return rc; }
   const bool known_n = have_list && v->dirty_list_n != ~0u;
   const uint32_t cap_list = v->dev.max_chunks;
   *bound = known_n ? v->dirty_list_n : cap_list;
-  uint8_t* db = reinterpret_cast<uint8_t*>(v->scratch.d);
+  uint8_t* db = v->scratch.d.as<uint8_t>();
   const int4* list = reinterpret_cast<const int4*>(db + 16);
   const uint32_t* cnt = reinterpret_cast<const uint32_t*>(db);
   launch_compress(v->dev, list, cnt, cap_list, true, v->stream);
@@ -1616,11 +1616,11 @@ int tf_check_summaries(tf_volume* v, int64_t* n_chunks, int64_t* n_missing, int6
   TF_DEV(v);
   int rc = reserve(v, v->scratch, 32, 0);
   if (rc) return rc;
-  TF_HIP(hipMemsetAsync(v->scratch.d, 0, 32, v->stream));
-  hipLaunchKernelGGL(k_check_summaries, dim3(1024), dim3(256), 0, v->stream, v->dev, reinterpret_cast<unsigned long long*>(v->scratch.d));
+  TF_HIP(hipMemsetAsync(v->scratch.d.p, 0, 32, v->stream));
+  hipLaunchKernelGGL(k_check_summaries, dim3(1024), dim3(256), 0, v->stream, v->dev, v->scratch.d.as<unsigned long long>());
   TF_HIP(hipGetLastError());
   unsigned long long h[3] = {0, 0, 0};
-  TF_HIP(hipMemcpyAsync(h, v->scratch.d, sizeof(h), hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(h, v->scratch.d.p, sizeof(h), hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   if (n_chunks) *n_chunks = (int64_t)h[0];
   if (n_missing) *n_missing = (int64_t)h[1];
@@ -1633,11 +1633,11 @@ int tf_check_neighbours(tf_volume* v, int64_t out6[6]) {
   TF_DEV(v);
   int rc = reserve(v, v->scratch, 64, 0);
   if (rc) return rc;
-  TF_HIP(hipMemsetAsync(v->scratch.d, 0, 64, v->stream));
-  hipLaunchKernelGGL(k_check_neighbours, dim3(1024), dim3(256), 0, v->stream, v->dev, reinterpret_cast<unsigned long long*>(v->scratch.d));
+  TF_HIP(hipMemsetAsync(v->scratch.d.p, 0, 64, v->stream));
+  hipLaunchKernelGGL(k_check_neighbours, dim3(1024), dim3(256), 0, v->stream, v->dev, v->scratch.d.as<unsigned long long>());
   TF_HIP(hipGetLastError());
   unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-  TF_HIP(hipMemcpyAsync(h, v->scratch.d, sizeof(h), hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(h, v->scratch.d.p, sizeof(h), hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   for (int k = 0; k < 6; ++k) out6[k] = (int64_t)h[k];
   return TF_OK;

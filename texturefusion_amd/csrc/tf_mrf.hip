@@ -397,7 +397,7 @@ int mrf_begin(tf_volume* v, MrfArgs& a, size_t at) {
   MrfScratch sc;
   sc.take(L, a.n, a.nnz);
   if (int rc = reserve(v, v->scratch, L.size, 0)) return rc;
-  sc.bind(a, reinterpret_cast<uint8_t*>(v->scratch.d));
+  sc.bind(a, v->scratch.d.as<uint8_t>());
   return mrf_enqueue_start(v, a);
 }
 

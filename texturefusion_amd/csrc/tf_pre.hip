@@ -379,7 +379,7 @@ int tf_pre_refine_keyframe(tf_volume* v, float* d_depth_ref, float* d_weight_ref
   // scratch: original depth | estimate A | estimate B | new weight | flag
   int rc = reserve(v, v->scratch, 4 * bytes + 64, 0);
   if (rc) return rc;
-  float* orig = reinterpret_cast<float*>(v->scratch.d);
+  float* orig = v->scratch.d.as<float>();
   float* est[2] = {orig + np, orig + 2 * np};
   float* wout = orig + 3 * np;
   uint32_t* flag = reinterpret_cast<uint32_t*>(orig + 4 * np);
@@ -444,7 +444,7 @@ int tf_pre_frame_depth(tf_volume* v, uint16_t* d_depth, float* d_refined, float 
   const size_t lut_at = 64, img_at = lut_at + ((kBfBins + 2) * sizeof(float) + 63) / 64 * 64;
   int rc = reserve(v, v->scratch, img_at + np * sizeof(float), 0);
   if (rc) return rc;
-  uint8_t* base = reinterpret_cast<uint8_t*>(v->scratch.d);
+  uint8_t* base = v->scratch.d.as<uint8_t>();
   BfState* st = reinterpret_cast<BfState*>(base);
   float* lut = reinterpret_cast<float*>(base + lut_at);
   float* metres = reinterpret_cast<float*>(base + img_at);

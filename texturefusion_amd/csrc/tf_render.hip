@@ -306,7 +306,7 @@ int render_check(tf_volume* v, int64_t n_vertices, int64_t n_indices, const void
     return TF_ERR_INVALID;
   }
   if (mode >= 3 && rgba) {
-    if (tex ? (tex_w <= 0 || tex_h <= 0) : (!v->atlas.buf || v->atlas.aw <= 0 || v->atlas.ah <= 0)) {
+    if (tex ? (tex_w <= 0 || tex_h <= 0) : (!v->dev.atlas || v->atlas.aw <= 0 || v->atlas.ah <= 0)) {
       set_error(tex ? "texture size must be positive" : "no atlas to sample");
       return TF_ERR_INVALID;
     }
@@ -335,7 +335,7 @@ int render_launch(tf_volume* v, const RenderCam& cam, const float* d_vtx, int64_
   a.fx = cam.fx; a.fy = cam.fy; a.cxs = cam.cx + 0.5f; a.cys = cam.cy + 0.5f;
   a.W = cam.W; a.H = cam.H; a.near_p = near_plane; a.far_p = far_plane; a.mode = mode;
   a.vtx = d_vtx; a.nv = (uint32_t)nv; a.idx = d_idx; a.ntri = (uint32_t)(ni / 3);
-  a.tex = d_tex ? d_tex : v->atlas.buf;
+  a.tex = d_tex ? d_tex : v->dev.atlas;
   a.tw = d_tex ? tw : v->atlas.aw;
   a.th = d_tex ? th : v->atlas.ah;
   a.keys = reinterpret_cast<unsigned long long*>(scratch + rs.o_keys);
@@ -375,27 +375,19 @@ int out_fetch(tf_volume* v, const Stage& sg, const RenderOut& o, size_t P, uint8
 int model_stream(tf_volume* v, int64_t* nv, int64_t* ni) {
   RenderState& r = v->render;
   for (int pass = 0; pass < 2; ++pass) {
-    const int rc = draw_stream_device(v, r.d_vtx, r.d_idx, r.cap_v, r.cap_i, nv, ni);
+    int rc = draw_stream_device(v, r.vtx.as<float>(), r.idx.as<uint32_t>(), (int64_t)(r.vtx.bytes / 48), (int64_t)(r.idx.bytes / 4), nv, ni);
     if (rc != TF_ERR_CAPACITY) return rc;
-    TF_HIP(hipStreamSynchronize(v->stream));
-    render_release(v);
     int64_t cv = 1 << 16, ci = 3 << 16;
     while (cv < *nv) cv <<= 1;
     while (ci < *ni) ci <<= 1;
-    TF_HIP(hipMalloc((void**)&r.d_vtx, (size_t)cv * 48));
-    TF_HIP(hipMalloc((void**)&r.d_idx, (size_t)ci * 4));
-    r.cap_v = cv; r.cap_i = ci;
+    if ((rc = fit(r.vtx, (size_t)cv * 48, v->stream)) || (rc = fit(r.idx, (size_t)ci * 4, v->stream))) return rc;
   }
   return TF_ERR_CAPACITY;
 }
 
 }  // namespace
 
-void tf::render_release(tf_volume* v) {
-  if (v->render.d_vtx) hipFree(v->render.d_vtx);
-  if (v->render.d_idx) hipFree(v->render.d_idx);
-  v->render = RenderState{};
-}
+void tf::render_release(tf_volume* v) { v->render = RenderState{}; }
 
 extern "C" {
 
@@ -414,7 +406,7 @@ int tf_render_stream_device(tf_volume* v, const float* d_vertices, int64_t n_ver
   // the device half -- the pool only waits for the device when it has to grow)
   if ((rc = reserve(v, v->scratch, L.size, 0))) return rc;
   return render_launch(v, cam, d_vertices, n_vertices, d_indices, n_indices, d_texture, tex_w, tex_h, pose, near_plane,
-                       far_plane, mode, reinterpret_cast<uint8_t*>(v->scratch.d), rs, d_rgba, d_depth, d_tri);
+                       far_plane, mode, v->scratch.d.as<uint8_t>(), rs, d_rgba, d_depth, d_tri);
 }
 
 int tf_render_stream(tf_volume* v, const float* vertices, int64_t n_vertices, const uint32_t* indices, int64_t n_indices,
@@ -459,8 +451,8 @@ int tf_render_model_device(tf_volume* v, const float pose[12], float near_plane,
   Layout L;
   const RenderScratch rs = render_layout(L, cam, (size_t)(ni / 3));
   if ((rc = reserve(v, v->scratch, L.size, 0))) return rc;
-  return render_launch(v, cam, v->render.d_vtx, nv, v->render.d_idx, ni, nullptr, 0, 0, pose, near_plane, far_plane, mode,
-                       reinterpret_cast<uint8_t*>(v->scratch.d), rs, d_rgba, d_depth, d_tri);
+  return render_launch(v, cam, v->render.vtx.as<float>(), nv, v->render.idx.as<uint32_t>(), ni, nullptr, 0, 0, pose, near_plane, far_plane, mode,
+                       v->scratch.d.as<uint8_t>(), rs, d_rgba, d_depth, d_tri);
 }
 
 int tf_render_model(tf_volume* v, const float pose[12], float near_plane, float far_plane, int32_t mode, uint8_t* rgba,
@@ -478,7 +470,7 @@ int tf_render_model(tf_volume* v, const float pose[12], float near_plane, float 
   const RenderScratch rs = render_layout(L, cam, (size_t)(ni / 3));
   Stage sg;
   if ((rc = stage_begin(v, v->scratch, L.size, host_bytes, &sg))) return rc;
-  rc = render_launch(v, cam, v->render.d_vtx, nv, v->render.d_idx, ni, nullptr, 0, 0, pose, near_plane, far_plane, mode,
+  rc = render_launch(v, cam, v->render.vtx.as<float>(), nv, v->render.idx.as<uint32_t>(), ni, nullptr, 0, 0, pose, near_plane, far_plane, mode,
                      sg.d, rs, rgba ? sg.d + ro.o_c : nullptr, depth ? sg.dp<float>(ro.o_d) : nullptr,
                      tri ? sg.dp<int32_t>(ro.o_t) : nullptr);
   if (rc) return rc;

@@ -510,13 +510,13 @@ int tm_ensure(tf_volume* v) {
   Layout L;
   const auto carve = [&](auto*& p, size_t bytes, int) { tm_carve(p, d, L, bytes / sizeof(*p)); };
   tm_arrays(t, v->dev.max_chunks, carve);  // (d == null: the block's size)
-  const int rc = [&]() -> int {
-    TF_HIP(hipMalloc(&d, L.size));
+  int rc;
+  if (!(rc = v->tmx.block.alloc(L.size)) && !(rc = v->tmx.h_ctl.alloc(sizeof(TexMapCtl)))) {
+    d = v->tmx.block.p;
     L = Layout{};
     tm_arrays(t, v->dev.max_chunks, carve);
-    TF_HIP(hipHostMalloc((void**)&v->tmx.h_ctl, sizeof(TexMapCtl), hipHostMallocDefault));
-    return tm_fill(v);
-  }();
+    rc = tm_fill(v);
+  }
   if (rc) texmap_release(v);
   return rc;
 }
@@ -538,8 +538,8 @@ int tm_room(tf_volume* v, bool per_node, size_t want) {
 TmProb tm_prob(const TexMapState& x) {
   TmProb P{};
   Layout N, Z;
-  P.take_nodes(N, x.pn.d, x.pn_cap);
-  P.take_labels(Z, x.pz.d, x.pz_cap);
+  P.take_nodes(N, x.pn.d.p, x.pn_cap);
+  P.take_labels(Z, x.pz.d.p, x.pz_cap);
   return P;
 }
 
@@ -549,17 +549,9 @@ unsigned wave_blocks(size_t n) { return (unsigned)std::min<size_t>(std::max<size
 }  // namespace
 
 void texmap_release(tf_volume* v) {
-  TexMapDev& t = v->tm;
-  TexMapState& x = v->tmx;
-  if (t.node) hipFree(t.node);  // the block (tm_arrays)
-  if (x.h_ctl) hipHostFree(x.h_ctl);
-  scratch_free(x.kf);
-  if (x.kf_ev) hipEventDestroy(x.kf_ev);
-  scratch_free(x.pn);
-  scratch_free(x.pz);
-  if (x.d_ctu_raw) hipFree(x.d_ctu_raw);  // (d_ctu lies behind it)
-  t = TexMapDev{};
-  x = TexMapState{};
+  if (v->tmx.kf_ev) hipEventDestroy(v->tmx.kf_ev);
+  v->tm = TexMapDev{};
+  v->tmx = TexMapState{};  // (its owners free the map's block, the control block's pinned copy, the pools and the lists)
 }
 
 void launch_tm_work_labels(tf_volume* v, uint32_t n, uint32_t* d_first_fail) {
@@ -596,12 +588,12 @@ int tf_texmap_set_keyframes(tf_volume* v, const int32_t* key_frame_index, int32_
   else TF_HIP(hipEventSynchronize(x.kf_ev));  // the previous upload has left the staging buffer
   const size_t bytes = 4 * std::max<size_t>((size_t)n_rows + 64, 256);  // (64 words behind the rows: the tail's keyframes to update)
   if ((rc = reserve(v, x.kf, bytes, bytes))) { v->tm.kf_row = nullptr; v->tm.n_rows = 0; return rc; }
-  memcpy(x.kf.h, key_frame_index, 4 * (size_t)n_rows);
-  TF_HIP(hipMemcpyAsync(x.kf.d, x.kf.h, 4 * (size_t)n_rows, hipMemcpyHostToDevice, v->stream));
+  memcpy(x.kf.h.p, key_frame_index, 4 * (size_t)n_rows);
+  TF_HIP(hipMemcpyAsync(x.kf.d.p, x.kf.h.p, 4 * (size_t)n_rows, hipMemcpyHostToDevice, v->stream));
   TF_HIP(hipEventRecord(x.kf_ev, v->stream));
   x.kf_row.assign(key_frame_index, key_frame_index + n_rows);
   x.kf_inv.swap(inv);
-  v->tm.kf_row = static_cast<const int32_t*>(x.kf.d);
+  v->tm.kf_row = x.kf.d.as<const int32_t>();
   v->tm.n_rows = n_rows;
   return TF_OK;
 }
@@ -611,16 +603,16 @@ static int tm_list_buffers(tf_volume* v) {
   TexMapState& x = v->tmx;
   if (x.d_ctu) return TF_OK;
   const size_t mc = v->dev.max_chunks;
-  TF_HIP(hipMalloc((void**)&x.d_ctu_raw, 2 * mc * 16));
-  x.d_ctu = x.d_ctu_raw + mc;
-  return TF_OK;
+  const int rc = x.ctu.alloc(2 * mc * 16);
+  if (!rc) x.d_ctu = x.ctu.as<int4>() + mc;
+  return rc;
 }
 // frames_to_update of the tail: into the tail of the keyframe table's device half, through its pinned half
 static int tm_frames_upload(tf_volume* v, const int32_t* frames, int32_t n, const int32_t** d_out) {
   TexMapState& x = v->tmx;
   const size_t rows = (size_t)v->tm.n_rows;
-  if (rows + (size_t)n > x.kf.d_bytes / 4) { set_error("texmap: more keyframes to update than the keyframe table has room behind its rows"); return TF_ERR_CAPACITY; }
-  int32_t *h = static_cast<int32_t*>(x.kf.h) + rows, *d = static_cast<int32_t*>(x.kf.d) + rows;
+  if (rows + (size_t)n > x.kf.d.bytes / 4) { set_error("texmap: more keyframes to update than the keyframe table has room behind its rows"); return TF_ERR_CAPACITY; }
+  int32_t *h = x.kf.h.as<int32_t>() + rows, *d = x.kf.d.as<int32_t>() + rows;
   TF_HIP(hipEventSynchronize(x.kf_ev));
   memcpy(h, frames, 4 * (size_t)n);
   TF_HIP(hipMemcpyAsync(d, h, 4 * (size_t)n, hipMemcpyHostToDevice, v->stream));
@@ -706,9 +698,9 @@ static int tm_removal(tf_volume* v, int (*enqueue)(tf_volume*), int64_t* n_remov
   if (!v->tm.node) return TF_OK;
   const int rc = enqueue(v);
   if (rc || !n_removed) return rc;
-  TF_HIP(hipMemcpyAsync(v->tmx.h_ctl, v->tm.ctl, sizeof(TexMapCtl), hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(v->tmx.h_ctl.p, v->tm.ctl, sizeof(TexMapCtl), hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
-  *n_removed = v->tmx.h_ctl->n_removed;
+  *n_removed = v->tmx.h_ctl.as<TexMapCtl>()->n_removed;
   return TF_OK;
 }
 
@@ -737,9 +729,9 @@ static int tm_select(tf_volume* v, const int4* d_ids, uint32_t n, const uint32_t
   int rc;
   if (bound <= 0) {  // (tsdfFusion asks num_nodes() > 0 first; `concerns.empty()` returns)
     if (want.list_n) {
-      TF_HIP(hipMemcpyAsync(x.h_ctl, ctl, sizeof(TexMapCtl), hipMemcpyDeviceToHost, s));
+      TF_HIP(hipMemcpyAsync(x.h_ctl.p, ctl, sizeof(TexMapCtl), hipMemcpyDeviceToHost, s));
       TF_HIP(hipStreamSynchronize(s));
-      *want.list_n = x.h_ctl->n_list;
+      *want.list_n = x.h_ctl.as<TexMapCtl>()->n_list;
     }
     return TF_OK;
   }
@@ -752,10 +744,10 @@ static int tm_select(tf_volume* v, const int4* d_ids, uint32_t n, const uint32_t
   hipLaunchKernelGGL(k_tm_scan, dim3(1), dim3(1024), 0, s, tm_dev(v), P);
   TF_HIP(hipGetLastError());
   // the one wait: {n_nodes, nnz} size the solver's scratch and the launch grids
-  TF_HIP(hipMemcpyAsync(x.h_ctl, ctl, sizeof(TexMapCtl), hipMemcpyDeviceToHost, s));
+  TF_HIP(hipMemcpyAsync(x.h_ctl.p, ctl, sizeof(TexMapCtl), hipMemcpyDeviceToHost, s));
   TF_HIP(hipStreamSynchronize(s));
-  if (want.list_n) *want.list_n = x.h_ctl->n_list;
-  const int64_t nn = std::min<int64_t>(x.h_ctl->n_nodes, (int64_t)P.cap), nnz = (int64_t)x.h_ctl->nnz;
+  if (want.list_n) *want.list_n = x.h_ctl.as<TexMapCtl>()->n_list;
+  const int64_t nn = std::min<int64_t>(x.h_ctl.as<TexMapCtl>()->n_nodes, (int64_t)P.cap), nnz = (int64_t)x.h_ctl.as<TexMapCtl>()->nnz;
   if (want.n_nodes) *want.n_nodes = nn;
   if (nn == 0) return TF_OK;
   if ((rc = tm_room(v, false, (size_t)nnz))) return rc;
@@ -774,8 +766,8 @@ static int tm_select(tf_volume* v, const int4* d_ids, uint32_t n, const uint32_t
   if (!want.rounds) return TF_OK;
   // the caller wants the trace: wait for it.  (A refused problem: k_tm_assign wrote nothing, labels and the solved flag are as before.)
   if ((rc = reserve(v, v->scratch, 0, MrfResult::bytes(R)))) return rc;
-  const MrfResult* res = static_cast<const MrfResult*>(v->scratch.h);
-  if ((rc = mrf_read_back(v, a, R, static_cast<MrfResult*>(v->scratch.h)))) return rc;
+  const MrfResult* res = v->scratch.h.as<const MrfResult>();
+  if ((rc = mrf_read_back(v, a, R, v->scratch.h.as<MrfResult>()))) return rc;
   *want.rounds = res->rounds[0];
   if (want.energy && res->rounds[0] >= 0) memcpy(want.energy, res->energy, 8 * (size_t)(res->rounds[0] + 1));
   return TF_OK;
@@ -800,8 +792,8 @@ int tf_texmap_view_selection(tf_volume* v, const int32_t* ids, int64_t n, int32_
   if (rc) return rc;
   Stage sg;
   if ((rc = stage_ids(v, v->scratch, (size_t)n * 16, ids, n, &sg))) return rc;
-  TF_HIP(hipMemcpyAsync(v->tmx.d_ctu_raw, sg.d, (size_t)n * 16, hipMemcpyDeviceToDevice, v->stream));
-  return tm_select(v, v->tmx.d_ctu_raw, (uint32_t)n, nullptr, max_rounds, want);
+  TF_HIP(hipMemcpyAsync(v->tmx.ctu.as<int4>(), sg.d, (size_t)n * 16, hipMemcpyDeviceToDevice, v->stream));
+  return tm_select(v, v->tmx.ctu.as<int4>(), (uint32_t)n, nullptr, max_rounds, want);
 }
 
 // MobileFusion::tsdfFusion's tail (GCFusion/MobileFusion.cpp:330-382; CompensateColor with TF_TAIL_COMPENSATE_COLOR) in one call
@@ -820,9 +812,9 @@ int tf_texture_tail_device(tf_volume* v, int32_t frame_index, const int32_t* fra
   // :345-355 chunksToUpdate + CompressMeshes; the list sorted on the device
   uint32_t bound = 0;
   uint32_t* d_count = &v->tm.ctl->n_raw;
-  if ((rc = compress_device_list(v, x.d_ctu_raw, v->dev.max_chunks, d_count, &bound))) return rc;
+  if ((rc = compress_device_list(v, x.ctu.as<int4>(), v->dev.max_chunks, d_count, &bound))) return rc;
   const uint32_t rank_grid = (uint32_t)std::min<size_t>(std::max<size_t>(blocks_of(bound, 256), 1), 2048);
-  hipLaunchKernelGGL(k_tm_rank, dim3(rank_grid), dim3(256), 0, s, tm_dev(v), x.d_ctu_raw, d_count, v->dev.max_chunks, x.d_ctu);
+  hipLaunchKernelGGL(k_tm_rank, dim3(rank_grid), dim3(256), 0, s, tm_dev(v), x.ctu.as<int4>(), d_count, v->dev.max_chunks, x.d_ctu);
   const uint32_t* d_n = &v->tm.ctl->n_list;
   // :356-361 (the keyframes to update travel through the words behind the keyframe table's rows: n_frames <= 12 in the reference)
   const int32_t* d_frames = nullptr;

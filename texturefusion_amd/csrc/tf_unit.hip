@@ -24,16 +24,19 @@ namespace tf {
 // the top reaches the end of the arena the live regions are moved together first (k_kf_store, one workgroup, no host
 // involvement).
 struct UnitState {
-  int4* arena = nullptr;
+  bool ready = false;  // set last by the first use: everything below is there, or nothing is
+  DevMem arena;        // int4[cap]
   uint32_t cap = 0;
   bool fixed_arena = false;  // TF_UNIT_ARENA: a test pins the arena (compaction is then the only way to make room)
-  KfTab* tab = nullptr;
+  DevMem tab;  // a KfTab with `slots` slots
   uint32_t slots = 0;
-  uint32_t* h_fill = nullptr;  // pinned: [0] top, [1] longest list, [2] live words -- as of the last store the device finished
+  PinMem h_fill;  // u32: [0] top, [1] longest list, [2] live words -- as of the last store the device finished
   uint64_t grows = 0;
   std::unordered_map<int32_t, int> slot_of;
-  float4* group_pre = nullptr;  // scratch of the keyframe-group kernel (list records + centroid tables of six frames)
-  float* group_cen = nullptr;
+  DevMem group;  // scratch of the keyframe-group kernel: list records (group_pre), then the centroid tables of six frames
+  float4* group_pre() const { return group.as<float4>(); }
+  float* group_cen() const { return group.as<float>(sizeof(float4) * (size_t)kGroupFrames * 4 * max_list); }
+  size_t max_list = 0;  // VolumeDev::max_list of the handle
   // The front end of a fresh group (k_bbox -> k_select -> k_pre_group: a pure function of the group's images and poses and of
   // which chunks exist / are parked) runs on a stream of its own behind the LAST launch that changes chunks -- ev_mut, recorded
   // at the end of every group -- and into the next selection set of the ring: when unit calls follow each other it overlaps
@@ -43,7 +46,9 @@ struct UnitState {
   hipEvent_t ev_mut = nullptr, ev_front = nullptr;
   uint64_t mut_seq = 0;  // tf_volume::call_seq of the call that recorded ev_mut
 };
-static std::unordered_map<tf_volume*, UnitState> g_units;  // (one per handle; freed by tf_keyframe_unit_release)
+// one per handle; freed by tf_keyframe_unit_release.  The map itself is never destroyed: the unit of a handle that is still
+// open when the process ends must not free device memory from a static destructor, behind the runtime's own teardown
+static std::unordered_map<tf_volume*, UnitState>& g_units = *new std::unordered_map<tf_volume*, UnitState>();
 static std::mutex g_units_mu;                              // (handles may live on different threads)
 
 __global__ __launch_bounds__(1024) void k_kf_store(VolumeDev v, KfStoreArgs a) {
@@ -95,27 +100,40 @@ __global__ __launch_bounds__(256) void k_kf_load(VolumeDev v, const KfTab* tab, 
   }
 }
 
+static void unit_free(UnitState& u) {
+  if (u.front) { hipStreamSynchronize(u.front); hipStreamDestroy(u.front); }
+  if (u.ev_mut) hipEventDestroy(u.ev_mut);
+  if (u.ev_front) hipEventDestroy(u.ev_front);
+  u = UnitState{};  // (its owners free the arena, the table, the fill words and the group scratch)
+}
+static int unit_init(tf_volume* v, UnitState& u) {
+  u.cap = (uint32_t)std::min<size_t>((size_t)v->dev.max_list * 16, (size_t)1 << 26);
+  if (const char* e = getenv("TF_UNIT_ARENA")) { u.cap = (uint32_t)std::max(1024, atoi(e)); u.fixed_arena = true; }  // test knob: a small, pinned arena
+  u.slots = kUnitSlots0;
+  if (const char* e = getenv("TF_UNIT_SLOTS")) u.slots = (uint32_t)std::max(4, atoi(e));  // test knob: initial slots
+  u.max_list = v->dev.max_list;
+  int rc;
+  if ((rc = u.arena.alloc(sizeof(int4) * (size_t)u.cap)) || (rc = u.tab.alloc(kf_tab_bytes(u.slots))) || (rc = u.h_fill.alloc(64)) ||
+      (rc = u.group.alloc(sizeof(float4) * (size_t)kGroupFrames * 4 * u.max_list + sizeof(float) * (size_t)kGroupFrames * 3 * kChunkVoxels)))
+    return rc;
+  TF_HIP(hipMemsetAsync(u.tab.p, 0, kf_tab_bytes(u.slots), v->stream));
+  memset(u.h_fill.p, 0, 64);
+  if (!(getenv("TF_UNIT_SERIAL_FRONT") && atoi(getenv("TF_UNIT_SERIAL_FRONT")))) {  // (A/B knob: everything on the handle's stream)
+    TF_HIP(hipStreamCreateWithFlags(&u.front, hipStreamNonBlocking));
+    TF_HIP(hipEventCreateWithFlags(&u.ev_mut, hipEventDisableTiming | hipEventDisableSystemFence));  // (both sides are this GPU: no system-scope writeback / invalidate at the edge)
+    TF_HIP(hipEventCreateWithFlags(&u.ev_front, hipEventDisableTiming | hipEventDisableSystemFence));
+  }
+  return TF_OK;
+}
+// The handle's unit; first use is all or nothing: one that fails gives back what it took and leaves the unit not ready
 static int unit_state(tf_volume* v, UnitState** out) {
   std::unique_lock<std::mutex> lock(g_units_mu);
   UnitState& u = g_units[v];  // (references into an unordered_map stay valid when other handles are added)
   lock.unlock();
-  if (!u.arena) {
-    u.cap = (uint32_t)std::min<size_t>((size_t)v->dev.max_list * 16, (size_t)1 << 26);
-    if (const char* e = getenv("TF_UNIT_ARENA")) { u.cap = (uint32_t)std::max(1024, atoi(e)); u.fixed_arena = true; }  // test knob: a small, pinned arena
-    u.slots = kUnitSlots0;
-    if (const char* e = getenv("TF_UNIT_SLOTS")) u.slots = (uint32_t)std::max(4, atoi(e));  // test knob: initial slots
-    TF_HIP(hipMalloc((void**)&u.arena, sizeof(int4) * (size_t)u.cap));
-    TF_HIP(hipMalloc((void**)&u.tab, kf_tab_bytes(u.slots)));
-    TF_HIP(hipMemsetAsync(u.tab, 0, kf_tab_bytes(u.slots), v->stream));
-    TF_HIP(hipHostMalloc((void**)&u.h_fill, 64, hipHostMallocDefault));
-    memset(u.h_fill, 0, 64);
-    TF_HIP(hipMalloc((void**)&u.group_pre, sizeof(float4) * (size_t)kGroupFrames * 4 * v->dev.max_list));
-    TF_HIP(hipMalloc((void**)&u.group_cen, sizeof(float) * (size_t)kGroupFrames * 3 * kChunkVoxels));
-    if (!(getenv("TF_UNIT_SERIAL_FRONT") && atoi(getenv("TF_UNIT_SERIAL_FRONT")))) {  // (A/B knob: everything on the handle's stream)
-      TF_HIP(hipStreamCreateWithFlags(&u.front, hipStreamNonBlocking));
-      TF_HIP(hipEventCreateWithFlags(&u.ev_mut, hipEventDisableTiming | hipEventDisableSystemFence));  // (both sides are this GPU: no system-scope writeback / invalidate at the edge)
-      TF_HIP(hipEventCreateWithFlags(&u.ev_front, hipEventDisableTiming | hipEventDisableSystemFence));
-    }
+  if (!u.ready) {
+    const int rc = unit_init(v, u);
+    if (rc) { unit_free(u); return rc; }
+    u.ready = true;
   }
   *out = &u;
   return TF_OK;
@@ -196,7 +214,7 @@ static int integrate_group(tf_volume* v, UnitState* u, const tf_unit_group* g, i
     launch_bbox(d, img.depth, v->cam, P, fs);
     launch_select(d, img.depth, v->cam, v->ig, P, v->res, /*emit=*/true, fs, /*plain=*/true);
   } else {
-    hipLaunchKernelGGL(k_kf_load, dim3(256), dim3(256), 0, s, d, u->tab, u->slots, u->arena, kf_slot, g->kf_id, v->tm);
+    hipLaunchKernelGGL(k_kf_load, dim3(256), dim3(256), 0, s, d, u->tab.as<KfTab>(), u->slots, u->arena.as<int4>(), kf_slot, g->kf_id, v->tm);
   }
   // the per-chunk records and centroid tables of all the group's frames in ONE launch (k_pre + k_pre_group were two)
   const float* dd[kGroupFrames];
@@ -205,9 +223,9 @@ static int integrate_group(tf_volume* v, UnitState* u, const tf_unit_group* g, i
     dd[f] = g->local[f].d_depth;
     memcpy(poses + 12 * f, flag ? g->local[f].pose : g->old_local_pose[f], 48);
   }
-  launch_pre_frames(d, P, g->n_local, poses, u->group_pre, u->group_cen, v->ig, v->res, v->cam, fs,
+  launch_pre_frames(d, P, g->n_local, poses, u->group_pre(), u->group_cen(), v->ig, v->res, v->cam, fs,
                     /*acquire=*/flag ? (g->n_local > 0 ? 2 : 1) : 0,  // (lazily when the group kernel finalizes the list)
-                    /*clear_word=*/flag ? nullptr : kf_off(u->tab) + u->slots + kf_slot);  // kf.validChunks.clear() (:217): the list is loaded
+                    /*clear_word=*/flag ? nullptr : kf_off(u->tab.as<KfTab>()) + u->slots + kf_slot);  // kf.validChunks.clear() (:217): the list is loaded
   if (fs != s) {  // join: the group's passes wait for its front end
     TF_HIP(hipEventRecord(u->ev_front, fs));
     TF_HIP(hipStreamWaitEvent(s, u->ev_front, 0));
@@ -224,19 +242,19 @@ static int integrate_group(tf_volume* v, UnitState* u, const tf_unit_group* g, i
   // kernel's waves, each behind its entry's last frame (k_finalize + k_dirty_frame were two launches, 7 + 9 us)
   const bool folded = g->n_local > 0;
   if (folded) {
-    launch_integrate_group(d, g->n_local, dd, poses, u->group_pre, u->group_cen, v->cam, v->ig, v->res, flag, s, true, g->kf_id,
+    launch_integrate_group(d, g->n_local, dd, poses, u->group_pre(), u->group_cen(), v->cam, v->ig, v->res, flag, s, true, g->kf_id,
                            /*fin=*/1, v->epoch++, dirty_par, dirty_stamp, key_in_group ? &img : nullptr, key_in_group ? &P : nullptr);
   } else {
     launch_obs_record(d, g->kf_id, s);
     launch_finalize(d, v->epoch++, s);
   }
   const int slack = !(getenv("TF_UNIT_NO_SLACK") && atoi(getenv("TF_UNIT_NO_SLACK")));  // test knob (read per call): exact-fit regions
-  const KfStoreArgs sa{u->tab, u->slots, u->arena, u->cap, kf_slot, slack, u->h_fill};
+  const KfStoreArgs sa{u->tab.as<KfTab>(), u->slots, u->arena.as<int4>(), u->cap, kf_slot, slack, u->h_fill.as<uint32_t>()};
   bool stored = false;
   if (dirty_par >= 0 && !folded) {
     VolumeDev dd = d;
-    dd.work_ids = v->atlas.d_work_ids + (size_t)dirty_par * d.max_chunks;
-    dd.work_slot = v->atlas.d_work_slot + (size_t)dirty_par * d.max_chunks;
+    dd.work_ids = v->dev.work_ids + (size_t)dirty_par * d.max_chunks;
+    dd.work_slot = v->dev.work_slot + (size_t)dirty_par * d.max_chunks;
     // (the group's validChunks are stored by one more workgroup of the same launch: k_kf_store alone is 11 us of launch floor)
     if (flag) { launch_dirty_frame_store(dd, dirty_par, dirty_stamp, sa, s); stored = true; }
     else launch_dirty_frame(dd, dirty_par, dirty_stamp, s);
@@ -258,15 +276,16 @@ static int integrate_group(tf_volume* v, UnitState* u, const tf_unit_group* g, i
 static int grow_slots(tf_volume* v, UnitState* u) {
   TF_HIP(hipStreamSynchronize(v->stream));
   const uint32_t ns = u->slots * 2u;
-  KfTab* nt = nullptr;
-  TF_HIP(hipMalloc((void**)&nt, kf_tab_bytes(ns)));
+  DevMem grown;  // (an error return below frees it; the old table stays)
+  const int rc = grown.alloc(kf_tab_bytes(ns));
+  if (rc) return rc;
+  KfTab *nt = grown.as<KfTab>(), *ot = u->tab.as<KfTab>();
   TF_HIP(hipMemset(nt, 0, kf_tab_bytes(ns)));
-  TF_HIP(hipMemcpy(nt, u->tab, sizeof(KfTab), hipMemcpyDeviceToDevice));
+  TF_HIP(hipMemcpy(nt, ot, sizeof(KfTab), hipMemcpyDeviceToDevice));
   for (int a = 0; a < 3; ++a)  // off | n | capn (the order scratch carries nothing)
-    TF_HIP(hipMemcpy(kf_off(nt) + (size_t)a * ns, kf_off(u->tab) + (size_t)a * u->slots, sizeof(uint32_t) * u->slots, hipMemcpyDeviceToDevice));
+    TF_HIP(hipMemcpy(kf_off(nt) + (size_t)a * ns, kf_off(ot) + (size_t)a * u->slots, sizeof(uint32_t) * u->slots, hipMemcpyDeviceToDevice));
   TF_HIP(hipDeviceSynchronize());
-  hipFree(u->tab);
-  u->tab = nt;
+  u->tab = std::move(grown);
   u->slots = ns;
   u->grows += 1;
   return TF_OK;
@@ -276,7 +295,8 @@ static int grow_slots(tf_volume* v, UnitState* u) {
 // itself and, failing that, reports TF_ERR_CAPACITY as before.
 static int grow_arena_if_needed(tf_volume* v, UnitState* u, int stores) {
   if (u->fixed_arena) return TF_OK;
-  const uint64_t top = __atomic_load_n(&u->h_fill[0], __ATOMIC_ACQUIRE), longest = u->h_fill[1], live = u->h_fill[2];
+  const uint32_t* fill = u->h_fill.as<uint32_t>();
+  const uint64_t top = __atomic_load_n(&fill[0], __ATOMIC_ACQUIRE), longest = fill[1], live = fill[2];
   (void)top;
   const uint64_t per = std::max<uint64_t>(longest, 1024) * 5 / 4 + 64;
   const uint64_t margin = (uint64_t)(stores + 8) * per;
@@ -285,15 +305,12 @@ static int grow_arena_if_needed(tf_volume* v, UnitState* u, int stores) {
   while (live + margin > ncap * 3 / 4) ncap *= 2;
   if (ncap > 0xFFFFFFF0ull) { set_error("the keyframes' validChunks exceed 2^32 entries"); return TF_ERR_CAPACITY; }
   TF_HIP(hipStreamSynchronize(v->stream));
-  int4* na = nullptr;
-  if (hipMalloc((void**)&na, sizeof(int4) * (size_t)ncap) != hipSuccess) {
-    set_error("cannot grow the keyframes' validChunks store (hipMalloc)");
-    return TF_ERR_HIP;
-  }
-  TF_HIP(hipMemcpy(na, u->arena, sizeof(int4) * (size_t)u->cap, hipMemcpyDeviceToDevice));  // (regions keep their offsets)
+  DevMem grown;  // (an error return below frees it; the old arena stays)
+  const int rc = grown.alloc(sizeof(int4) * (size_t)ncap);
+  if (rc) return rc;
+  TF_HIP(hipMemcpy(grown.p, u->arena.p, sizeof(int4) * (size_t)u->cap, hipMemcpyDeviceToDevice));  // (regions keep their offsets)
   TF_HIP(hipDeviceSynchronize());
-  hipFree(u->arena);
-  u->arena = na;
+  u->arena = std::move(grown);
   u->cap = (uint32_t)ncap;
   u->grows += 1;
   return TF_OK;
@@ -376,7 +393,7 @@ int tf_keyframe_unit_device(tf_volume* v, const tf_unit_group* fresh, const tf_u
   bool have_ride = false;
   if (fresh) {  // :316-323
     const int slot = slot_for(fresh->kf_id, true);
-    if (slot < 0) return TF_ERR_HIP;  // (the table could not grow: hipMalloc's message is in tf_last_error)
+    if (slot < 0) return TF_ERR_HIP;  // (the table could not grow: the allocation's message is in tf_last_error)
     if ((rc = integrate_group(v, u, fresh, 1, slot, dirty_par, dirty_stamp, texture ? &ride_store : nullptr, fresh_front, true))) return rc;
     have_ride = ride_store.tab != nullptr;  // (a group without local frames stored with its dirty-set launch)
   }
@@ -396,7 +413,7 @@ int tf_keyframe_unit_device(tf_volume* v, const tf_unit_group* fresh, const tf_u
   const size_t cap = (size_t)v->dev.max_chunks;
   rc = dirty_list_enqueue(v);
   if (rc) return rc;
-  const uint8_t* db = reinterpret_cast<const uint8_t*>(v->scratch.d);
+  const uint8_t* db = v->scratch.d.as<const uint8_t>();
   (void)nbr_next_seq(v);
   launch_mesh(v->dev, v->mesh_par, reinterpret_cast<const int4*>(db + 16), reinterpret_cast<const uint32_t*>(db), (uint32_t)cap,
               ++v->mesh_epoch, v->res, false, -1, 1u << 30, nullptr, -1, v->stream);
@@ -421,7 +438,7 @@ int tf_keyframe_unit_stats(tf_volume* v, int64_t out[5]) {
   }
   TF_DEV(v);
   uint32_t h[4];
-  TF_HIP(hipMemcpyAsync(h, u->tab, sizeof(h), hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipMemcpyAsync(h, u->tab.p, sizeof(h), hipMemcpyDeviceToHost, v->stream));
   TF_HIP(hipStreamSynchronize(v->stream));
   out[0] = u->cap; out[1] = h[0]; out[2] = h[1]; out[3] = h[2]; out[4] = h[3];
   return TF_OK;
@@ -450,15 +467,7 @@ int tf_keyframe_unit_release(tf_volume* v) {
   TF_HIP(hipStreamSynchronize(v->stream));
   std::lock_guard<std::mutex> lock(g_units_mu);
   auto it = g_units.find(v);
-  UnitState& u = it->second;
-  if (u.arena) hipFree(u.arena);
-  if (u.tab) hipFree(u.tab);
-  if (u.h_fill) hipHostFree(u.h_fill);
-  if (u.group_pre) hipFree(u.group_pre);
-  if (u.group_cen) hipFree(u.group_cen);
-  if (u.front) { hipStreamSynchronize(u.front); hipStreamDestroy(u.front); }
-  if (u.ev_mut) hipEventDestroy(u.ev_mut);
-  if (u.ev_front) hipEventDestroy(u.ev_front);
+  unit_free(it->second);
   g_units.erase(it);
   return TF_OK;
 }

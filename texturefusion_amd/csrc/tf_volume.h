@@ -12,6 +12,7 @@
 #include "../../include/tf_fusion.h"
 #include "tf_copy_pool.h"
 #include "tf_device.h"
+#include "tf_mem.h"
 
 namespace tf {
 
@@ -59,17 +60,15 @@ void set_error(const std::string& msg);
     }                                                                                       \
   } while (0)
 
-// Scratch pool: a device half and a pinned host half, each grown on demand to a power of two.  Before a half that is in use
-// grows, the stream is synchronised and the old allocation freed.  The halves grow independently: growing the host half
-// never frees the device half (which may hold the dirty list tf_compress_meshes takes over, tf_volume::dirty_list_seq).
+// Scratch pool: a device half and a pinned host half, two fitted buffers (tf_mem.h) that reserve() grows on demand to a
+// power of two, draining the handle's stream first.  The halves grow independently: growing the host half never frees the
+// device half (which may hold the dirty list tf_compress_meshes takes over, tf_volume::dirty_list_seq).  `s = Scratch{}`
+// gives both back.
 struct Scratch {
-  void* d = nullptr;
-  size_t d_bytes = 0;
-  void* h = nullptr;
-  size_t h_bytes = 0;
+  DevMem d;
+  PinMem h;
 };
 int reserve(tf_volume* v, Scratch& s, size_t dev_bytes, size_t host_bytes);
-void scratch_free(Scratch& s);
 
 // Byte layout of a staging area: each block at a 16-byte aligned offset; size = the total.
 struct Layout {
@@ -108,32 +107,21 @@ struct ProfEvent {
 };
 
 struct KeyframeSlot {
-  uint8_t* rgb = nullptr;   // device, u8[H][W][stride]
-  float* depth = nullptr;   // device, f32[H][W]
-  bool owned = false;
-  int slot = -1;            // entry of the device keyframe table
+  DevMem rgb, depth;  // tf_keyframe_cache's copies, u8[H][W][3] and f32[H][W], fitted to the camera; empty: the caller's images
+  int slot = -1;      // entry of the device keyframe table
 };
 
 struct AtlasState {
   int32_t aw = 13824, ah = 13824;
   uint64_t pw = 0, ph = 0;
-  uint8_t* buf = nullptr;  // device, u8[ah][aw][3]
+  DevMem buf;    // VolumeDev::atlas, u8[ah][aw][3]
+  DevMem block;  // everything else of VolumeDev's atlas part, carved (atlas_init)
   // keyframe table (device copy + host mirror)
   std::unordered_map<int32_t, KeyframeSlot> keyframes;
   std::vector<KfDev> h_kf;
   std::vector<uint8_t> kf_used;
-  KfDev* d_kf = nullptr;
   int kf_cap = 0;
-  AtlasCtl* d_actl = nullptr;
-  int4* d_work_ids = nullptr;
-  uint32_t* d_work_slot = nullptr;
-  int4* d_wl_ids = nullptr;        // VolumeDev::wl_*: the dirty set K-A builds (shard lists, two parities)
-  uint32_t* d_wl_slot = nullptr;
-  uint32_t* d_wl_cnt = nullptr;
-  int4* d_patch_list = nullptr;
-  uint32_t* d_patch_cnt = nullptr;
-  uint32_t* h_dirty_len = nullptr;  // pinned, device-visible: the mesher's filter leaves the length of a frame's dirty list here
-  unsigned long long* d_cand = nullptr;
+  PinMem h_dirty_len;  // one u32, device-visible: the mesher's filter leaves the length of a frame's dirty list here
   int fused_par = 0;   // counter set of the next fused frame
   // fused flow: the patch stage of textured frame f (slot hand-out, CompressMeshes' exchange, CalculateTexCoords,
   // UpdateBuffer) is not launched behind the frame's mesher but rides on the NEXT frame's launch, next to its voxel
@@ -160,36 +148,35 @@ struct TexMapState {
   Scratch kf;
   hipEvent_t kf_ev = nullptr;
   int64_t nodes_bound = 0;           // chunks ever handed to tf_texmap_update: an upper bound of the node count
-  TexMapCtl* h_ctl = nullptr;        // pinned: the control block as read back; there whenever the map's device block is
+  DevMem block;                      // the map's device block (tm_arrays): what tf_volume::tm's pointers point into
+  PinMem h_ctl;                      // a TexMapCtl: the control block as read back; there whenever the map's device block is
   // the problem assembled last: per-node arrays (pn, room for pn_cap nodes), per-label arrays (pz, pz_cap labels); device halves
   Scratch pn, pz;
   size_t pn_cap = 0, pz_cap = 0;
   int64_t n = 0, nnz = 0;            // its size
   // tf_texture_tail_device: chunksToUpdate as a device list (raw = as the dirty set gave it, ctu = ascending chunk id);
   // one allocation, d_ctu behind d_ctu_raw
-  int4* d_ctu_raw = nullptr;
+  DevMem ctu;
   int4* d_ctu = nullptr;
   int64_t ctu_n = 0;                 // its length, known since the tail's one wait
 };
 
 // Device-resident CompensateColor (tf_cc.hip): its list, cluster table and partial sums in one block, null until first use
 struct CcState {
-  void* block = nullptr;
+  DevMem block;
 };
 
-// tf_render_model (tf_render.hip): the model's DrawMeshes stream, null until first use, grown on demand
+// tf_render_model (tf_render.hip): the model's DrawMeshes stream, empty until first use, fitted on demand
 struct RenderState {
-  float* d_vtx = nullptr;     // f32[cap_v][12]
-  uint32_t* d_idx = nullptr;  // u32[cap_i]
-  int64_t cap_v = 0, cap_i = 0;
+  DevMem vtx;  // f32[cap_v][12]
+  DevMem idx;  // u32[cap_i]
 };
 
 // RCCL communicator of the handle (tf_comm_init) and the exchange buffers
 struct CommState {
   void* comm = nullptr;  // ncclComm_t
   int rank = 0, nranks = 0;
-  void* d_send = nullptr;
-  void* d_recv = nullptr;
+  DevMem send, recv;
   int64_t cap_records = 0;
   int mode = TF_XCHG_NEIGHBOURS;
   uint64_t exchanges = 0, bytes_received = 0, bytes_sent = 0;  // tf_comm_stats / tf_comm_stats_ex
@@ -230,33 +217,30 @@ struct tf_volume {
   struct Primed { const float* depth; float pose[12]; };
   Primed primed[2];
   int n_primed = 0;
-  std::vector<void*> allocs;
-  // frame images
-  float* d_depth = nullptr;      // owned staging targets
-  uint8_t* d_rgba = nullptr;
-  float* d_quality = nullptr;
-  size_t img_pixels = 0;
+  std::vector<tf::DevMem> allocs;  // the fixed allocations of tf_volume_create
+  // frame images: the staging targets of tf_frame_upload, one fitted buffer carved as depth | rgba | quality
+  tf::DevMem images;
   // drop-in per-frame host path (tf_integrate_frame_host): ring of pinned staging + device image slots, H2D on
   // its own stream so that the copy of frame f+1 overlaps the kernels of frame f
   static constexpr int kHostRing = 8;  // four deferred frames + the one being staged + three whose kernels may still run
                                        // (a frame's images are read by its patch stage one launch behind its voxel update)
   struct HostSlot {
-    uint8_t* h = nullptr;      // pinned: depth f32[npix] | rgba u8[4 npix]
-    uint8_t* d = nullptr;      // device: same layout
+    tf::PinMem h;              // depth f32[npix] | rgba u8[4 npix]
+    tf::DevMem d;              // depth | colour as uploaded (RGBA, or RGB + valid flags) | RGBA packed from an RGB upload
     hipEvent_t copied = nullptr;
     uint32_t free_when = 0;    // 0: free; else the progress stamp (h_progress) at which the last launch that reads d is through
   };
   // Launch progress without stream events: every frame launch writes its sequence number into this pinned word when it
   // STARTS (= every launch ahead of it on the stream is through).  An event record between two launches of a frame cost
   // the host-frames path 6.8 us per frame of idle device time (profiles/r3, run 29).
-  uint32_t* h_progress = nullptr;
+  tf::PinMem h_progress;  // one u32, null until the host ring is first prepared
   uint32_t progress_seq = 0;   // stamp of the last frame launch put on the stream
   HostSlot hslot[kHostRing];
   // caller buffers registered with tf_host_register (page-locked in place): host frames that lie inside one are uploaded
   // straight out of it -- no staging copy -- and the call returns when that upload is through
   struct HostRange { const uint8_t* p; size_t n; const uint8_t* locked; };  // locked: base of the process-wide page-locked range that covers it
   std::vector<HostRange> host_ranges;
-  size_t hslot_pixels = 0;
+  size_t hslot_pixels = 0;  // the camera all eight slots fit and are laid out for; 0: the ring is not ready
   int hslot_next = 0;
   hipStream_t copy_stream = nullptr;
   hipStream_t copy_stream2 = nullptr;  // registered caller buffers: the colour image goes up next to the depth image (a second copy queue)
@@ -278,7 +262,7 @@ struct tf_volume {
   // the call right before it (MobileFusion.cpp:327-345 calls them back to back; nothing in between can have marked a chunk)
   uint64_t call_seq = 0, dirty_list_seq = ~0ull;
   uint32_t dirty_list_n = 0;
-  uint32_t* h_ctl = nullptr;  // pinned: FrameCtl head + VolCtl as fetch_ctl reads them
+  tf::PinMem h_ctl;  // pinned: FrameCtl head + VolCtl as fetch_ctl reads them
   uint32_t epoch = 0;        // finalize counter (mark / erase stamps are epoch + 1)
   uint32_t clear_floor = 0;  // stamps <= this were cleared (Chisel::CompressMeshes' chunksToUpdate.clear())
   uint32_t mesh_epoch = 0;   // meshing passes so far (MeshRec::epoch)
@@ -302,8 +286,7 @@ struct tf_volume {
   bool host_defer = true;  // tf_integrate_frame_host runs kHostDefer frames behind its caller (tf_host_frame_set_deferral)
   bool host_async = false;           // tf_host_frame_set_async: a call out of registered buffers returns before its upload is through
   hipEvent_t last_upload = nullptr;  // the newest frame's upload (tf_host_frame_fence waits for it)
-  float* d_group = nullptr;  // staging of tf_integrate_depth_group_host: six depth images
-  size_t d_group_pixels = 0;
+  tf::DevMem group;  // staging of tf_integrate_depth_group_host: six depth images
   tf::Scratch scratch;  // on-demand staging of the entry points (uploads / downloads, device scratch)
   // profiling
   bool prof_open = false;
@@ -319,7 +302,7 @@ struct tf_volume {
   tf::RenderState render;
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
   // band counts of a frame's selection as the host sees them: pinned words [0] tag (frame epoch + 1), [1..4] FrameCtl::band_cnt
-  uint32_t* h_xchg = nullptr;
+  tf::PinMem h_xchg;  // u32[16], null until first use (xchg_words)
   uint32_t xchg_pub_enq = 0;  // frame tag of the publish that is already on the stream (0: none)
   uint32_t xchg_pub_seq = 0;  // ... the sequence number that publish writes into h_xchg[0] (what the host waits for)
   // the per-frame exchange overlapped with the interior meshes (texture_stage): second stream, fork / join events
@@ -334,8 +317,7 @@ struct tf_volume {
   std::atomic<int32_t> atlas_frame{-1};
   hipStream_t read_stream = nullptr;
   hipEvent_t read_ev = nullptr;
-  uint8_t* d_snap = nullptr;
-  size_t d_snap_bytes = 0;
+  tf::DevMem snap;
   bool xchg_overlap = true;        // tf_comm_exchange_overlap
   uint64_t xchg_overlapped = 0;    // exchanges that ran next to an interior mesh pass (tf_comm_stats_ex)
   uint32_t xchg_seq = 0;      // publish sequence numbers handed out (monotonic over the handle's life: a stale word never matches)
@@ -369,6 +351,7 @@ int texture_stage(tf_volume* v, const SelBuf& sel, const FrameImages& img, uint3
 int texture_stage_finish(tf_volume* v, const FrameImages& img, uint32_t frame_epoch, const float* pose_inv16, int32_t frame_id, int par);
 // the four band counts of the frame whose selection wrote `ctl` (tag = its epoch + 1): waits for the device to publish them
 int xchg_band_counts(tf_volume* v, const FrameCtl* ctl, uint32_t tag, uint32_t cnt[4], hipStream_t s = nullptr);
+int xchg_words(tf_volume* v);  // tf_volume::h_xchg is there (allocated and zeroed on first use)
 uint32_t nbr_next_seq(tf_volume* v);  // neighbour table: the seq of the filter launch about to go out (tf_capi.cpp)
 int flush_deferred(tf_volume* v);
 // the dirty set (Chisel::meshesToUpdate) as a device list in scratch.d: [0,16) count word, ids from byte 16 (tf_mesh.hip)
@@ -380,7 +363,6 @@ int fused_arm(tf_volume* v);  // the fused flow's counter sets in their start st
 void prof_begin(tf_volume* v, int kind, hipStream_t s = nullptr);
 void prof_end(tf_volume* v, hipStream_t s = nullptr);
 int atlas_init(tf_volume* v);
-void atlas_destroy(tf_volume* v);
 int atlas_reset(tf_volume* v);
 int comm_exchange(tf_volume* v, int64_t cap_records, int dirty_par, uint32_t stamp, const FrameCtl* ctl = nullptr,
                   uint32_t tag = 0, const FrameCtl* next_ctl = nullptr, hipStream_t xs = nullptr);  // xs: the stream it runs on (null: the handle's)
