@@ -860,13 +860,71 @@ TF_API int tf_render_stream_device(tf_volume* v, const float* d_vertices, int64_
 TF_API int tf_render_stream(tf_volume* v, const float* vertices, int64_t n_vertices, const uint32_t* indices,
                             int64_t n_indices, const uint8_t* texture, int32_t tex_w, int32_t tex_h, const float pose[12],
                             float near_plane, float far_plane, int32_t mode, uint8_t* rgba, float* depth, int32_t* tri);
-/* The current model: DrawMeshes' device form into a stream of the handle's own (allocated by the first call, grown on
- * demand, freed by tf_volume_reset / tf_volume_destroy; the pack waits for the device once, as tf_draw_meshes_device
- * does), rendered with the atlas.  A model with no complete() patch renders an empty image and returns 0. */
+/* The current model, rendered with the atlas: the stream is the handle's resident model stream (tf_model_stream_* below).
+ * While that stream is current -- packed since the last call that could have changed a mesh, a patch or a pool slot --
+ * a render packs nothing and waits for nothing: tf_render_model_device is then asynchronous like tf_render_stream_device,
+ * and where the host has not read the stream's counts the rasteriser takes them from the stream's control block (grids
+ * and the queue of large triangles are sized from the capacity, surplus lanes leave at once).  While it is not, the render
+ * first packs it as tf_model_stream_update does: one wait.  Atlas texels are read at render time and are no part of the
+ * stream.  A model with no complete() patch renders an empty image and returns 0.
+ * A render behind a tf_model_stream_update_device whose model did not fit is such a render too: that stream counts as
+ * current, its control block reads 0 vertices, so the image is EMPTY (the previous model still lies in the buffers but is
+ * not shown) until the next synchronising call reports TF_ERR_CAPACITY and the caller reserves more or calls
+ * tf_model_stream_update.  tf_model_stream_stats counts that render as served from the stream all the same.
+ * Memory: the first render (or tf_model_stream_* call) of a handle allocates the pack's lists, about 84 B per
+ * tf_config.max_chunks (44 MB at 2^19 chunks), and, where nothing was reserved, a stream of 2^16 vertices / 3 * 2^16
+ * indices (3.9 MB) even for an empty model -- earlier a render allocated the stream alone.  tf_model_stream_release
+ * gives all of it back. */
 TF_API int tf_render_model_device(tf_volume* v, const float pose[12], float near_plane, float far_plane, int32_t mode,
                                   uint8_t* d_rgba, float* d_depth, int32_t* d_tri);
 TF_API int tf_render_model(tf_volume* v, const float pose[12], float near_plane, float far_plane, int32_t mode,
                            uint8_t* rgba, float* depth, int32_t* tri);
+/* ---- the model stream, resident in the handle (tf_model.hip) -------------------------------
+ * Chisel::DrawMeshes (Structure/Chisel.cpp:288-355; GCFusion/MobileFusion.cpp:384 at the end of a keyframe) into buffers
+ * of the handle's own, with nothing crossing to the host: the list of complete() patches, their order (ascending chunk
+ * id, as tf_draw_meshes), the running vertex / index counts and the pack are kernels on the handle's stream, the counts
+ * stay in device words.  The contents are tf_draw_meshes' bit for bit (the same text per patch).  The stream is kept
+ * until the model changes: the handle counts a model generation that EVERY entry point advances except a named set of
+ * readers -- tf_model_stream_*, tf_render_*, tf_raycast*, tf_query_points*, tf_sync, and the getters that touch no
+ * device state (tf_atlas_size, tf_atlas_patch_size, tf_atlas_snapshot_rows, tf_last_error) -- so a reader missing from
+ * that set costs one repack and no writer can be missed; a reader that first has to bring deferred frames onto the
+ * stream counts as a writer for that call.  A stream is current when it was packed at the present generation.
+ *   control block  u32[8] {n_vertices, n_indices, n_patches, status, need_vertices, need_indices, 0, 0}: status != 0 = the
+ *                  model did not fit; then n_* are 0, need_* say what it takes, and NOTHING was written -- the buffers
+ *                  hold what they held, a half-written model is never visible.  (need_* are always what the model takes.)
+ *   tf_model_stream_reserve        sets the capacity in vertices / indices (the reference's tsdf_vertices_buffer /
+ *                  tsdf_indices_buffer are fixed-size too).  A changed capacity reallocates (waits for the stream once)
+ *                  and drops the contents; it never goes below what a current stream holds.
+ *   tf_model_stream_update_device  enqueues the pack and returns: no wait, no copy to the host.  TF_ERR_INVALID without a
+ *                  capacity (tf_model_stream_reserve, or one left by tf_model_stream_update / tf_render_model).  A
+ *                  model that does not fit sets a sticky status bit: the next synchronising call returns
+ *                  TF_ERR_CAPACITY, as for a full mesh store.  Behind tf_texture_tail_device this is the reference's
+ *                  DrawMeshes at MobileFusion.cpp:384, and the keyframe still waits once.
+ *   tf_model_stream_update         the same, then one wait for the control block; on overflow the buffers grow to a power
+ *                  of two (at least 2^16 vertices / 3 * 2^16 indices) and the pack runs again; nothing becomes sticky.
+ *                  Counts returned (either may be NULL); a model with no complete() patch gives 0 / 0 and TF_OK.
+ *   tf_model_stream_get            borrows the device pointers (any may be NULL); d_counts is the control block.  Valid until a
+ *                  call that reallocates or frees the buffers (reserve with another capacity, a growing update /
+ *                  render, release, tf_volume_reset, tf_volume_destroy).  Does not synchronise: order reads behind the
+ *                  handle's stream.  TF_ERR_INVALID while there are no buffers.
+ *   tf_model_stream_stats          host counters, no wait: out[0] packs enqueued, out[1] tf_render_model(_device) calls
+ *                  served from a current stream without a pack, out[2] / out[3] capacity in vertices / indices.
+ *   tf_model_stream_release        waits for the stream, frees the buffers (about 84 B per tf_config.max_chunks besides the
+ *                  two streams); tf_volume_reset and tf_volume_destroy do the same.  The counters stay.
+ *   tf_model_stream_time           measurement aid, no part of the flow: one pack between HIP events on the handle's stream,
+ *                  then a wait; us[0..3] = list, rank (with the placing), scan, write in microseconds (tools/model_stream_time.py).  It is
+ *                  an entry point of its own, like tf_profile_calibrate, because tf_profile's kinds are a fixed-size
+ *                  part of the ABI (TF_PROF_COUNT) that four more kinds would change for every caller.  Needs a
+ *                  capacity (TF_ERR_INVALID without); a model that does not fit is timed as it is and raises NO sticky
+ *                  status. */
+TF_API int tf_model_stream_reserve(tf_volume* v, int64_t cap_vertices, int64_t cap_indices);
+TF_API int tf_model_stream_update_device(tf_volume* v);
+TF_API int tf_model_stream_update(tf_volume* v, int64_t* n_vertices, int64_t* n_indices);
+TF_API int tf_model_stream_get(tf_volume* v, const float** d_vertices, const uint32_t** d_indices,
+                               const uint32_t** d_counts, int64_t* cap_vertices, int64_t* cap_indices);
+TF_API int tf_model_stream_stats(tf_volume* v, int64_t out[4]);
+TF_API int tf_model_stream_release(tf_volume* v);
+TF_API int tf_model_stream_time(tf_volume* v, double us[4]);
 /* Patch mirrors of listed chunks (Structure/Patch.h:51-94): texloc (~0 = no slot), frameid, boundingbox
  *   (x, y, w, h), flags (TF_PATCH_*), ratio; texcoord f32[2 nv], texcolor / labs f32[3 nv] packed by
  *   vert_offsets (from tf_mesh_counts).  Any output may be NULL. */

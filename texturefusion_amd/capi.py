@@ -40,6 +40,8 @@ SYMBOLS = (
     "tf_keyframe_release", "tf_atlas_patch_size", "tf_atlas_loc_next", "tf_atlas_size", "tf_meshes_upload",
     "tf_generate_patches", "tf_compensate_color", "tf_compensate_color_device", "tf_compensate_color_device_count", "tf_update_atlas", "tf_draw_meshes", "tf_draw_meshes_device",
     "tf_render_stream", "tf_render_stream_device", "tf_render_model", "tf_render_model_device",
+    "tf_model_stream_reserve", "tf_model_stream_update_device", "tf_model_stream_update", "tf_model_stream_get",
+    "tf_model_stream_stats", "tf_model_stream_release", "tf_model_stream_time",
     "tf_patches_download", "tf_atlas_download_rows", "tf_atlas_snapshot_rows", "tf_stream_frames_device",
     "tf_stream_frames_textured_device", "tf_get_texture_stats", "tf_integrate_frame_host", "tf_integrate_frame_host_rgb", "tf_host_frame_times", "tf_host_register", "tf_host_unregister",
     "tf_host_frame_buffers", "tf_host_frame_deferral", "tf_host_frame_set_deferral", "tf_host_frame_set_async", "tf_host_frame_fence", "tf_texture_frame_device_phase", "tf_comm_exchange_overlap", "tf_texture_frame_device", "tf_boundary_block_bytes", "tf_boundary_pack_block", "tf_boundary_pack_bands", "tf_boundary_band_bounds", "tf_boundary_pack_bands2", "tf_boundary_unpack_pair", "tf_comm_exchange_mode", "tf_comm_stats", "tf_comm_stats_ex",
@@ -187,6 +189,13 @@ def lib():
                                           C.c_float, C.c_int32, vp, vp, vp]
     L.tf_render_model.argtypes = [vp, fp, C.c_float, C.c_float, C.c_int32, u8p, fp, C.POINTER(C.c_int32)]
     L.tf_render_model_device.argtypes = [vp, fp, C.c_float, C.c_float, C.c_int32, vp, vp, vp]
+    L.tf_model_stream_reserve.argtypes = [vp, C.c_int64, C.c_int64]
+    L.tf_model_stream_update_device.argtypes = [vp]
+    L.tf_model_stream_update.argtypes = [vp, i64p, i64p]
+    L.tf_model_stream_get.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64p, i64p]
+    L.tf_model_stream_stats.argtypes = [vp, i64p]
+    L.tf_model_stream_release.argtypes = [vp]
+    L.tf_model_stream_time.argtypes = [vp, C.POINTER(C.c_double)]
     L.tf_patches_download.argtypes = [vp, i32p, C.c_int64, i64p, u64p, i32p, i32p, i32p, fp, fp, fp, fp]
     L.tf_stream_frames_device.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(vp), C.POINTER(vp), fp]
     L.tf_stream_frames_textured_device.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(vp), C.POINTER(vp), fp, fp,
@@ -664,6 +673,42 @@ class Volume:
         pose = _f32(pose).reshape(12)
         self._ck(self.L.tf_render_model_device(self.h, _p(pose, C.c_float), float(near), float(far), int(mode),
                                                d_rgba or None, d_depth or None, d_tri or None))
+
+    def model_stream_reserve(self, cap_vertices, cap_indices):
+        """Capacity of the resident model stream (DrawMeshes' stream kept in the handle) in vertices / indices."""
+        self._ck(self.L.tf_model_stream_reserve(self.h, int(cap_vertices), int(cap_indices)))
+
+    def model_stream_update_device(self):
+        """Enqueues the pack of the model stream: no wait, the counts stay in the stream's control block."""
+        self._ck(self.L.tf_model_stream_update_device(self.h))
+
+    def model_stream_update(self):
+        """The pack, one wait, buffers grown when the model does not fit -> (n_vertices, n_indices)"""
+        nv, ni = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.tf_model_stream_update(self.h, C.byref(nv), C.byref(ni)))
+        return nv.value, ni.value
+
+    def model_stream_get(self):
+        """Borrowed device pointers -> dict(vertices, indices, counts (the u32[8] control block), cap_vertices, cap_indices)"""
+        dv, di, dc = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        cv, ci = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.tf_model_stream_get(self.h, C.byref(dv), C.byref(di), C.byref(dc), C.byref(cv), C.byref(ci)))
+        return dict(vertices=dv.value, indices=di.value, counts=dc.value, cap_vertices=cv.value, cap_indices=ci.value)
+
+    def model_stream_stats(self):
+        """Host counters -> dict(packs, hits, cap_vertices, cap_indices)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.L.tf_model_stream_stats(self.h, out))
+        return dict(packs=out[0], hits=out[1], cap_vertices=out[2], cap_indices=out[3])
+
+    def model_stream_release(self):
+        self._ck(self.L.tf_model_stream_release(self.h))
+
+    def model_stream_time(self):
+        """One pack between HIP events -> dict(list, rank, scan, write) in microseconds (a measurement aid)"""
+        us = (C.c_double * 4)()
+        self._ck(self.L.tf_model_stream_time(self.h, us))
+        return dict(zip(("list", "rank", "scan", "write"), us))
 
     def distance_from_surface(self, points):
         """Chisel::GetDistanceFromSurface at world points [n, 3] -> (dist [n] f32, tsdf_weight [n] f32)."""

@@ -21,6 +21,7 @@
 
 #include "tf_cc_solve.h"
 #include "tf_devfn.h"
+#include "tf_draw_body.h"
 #include "tf_patch_body.h"
 #include "tf_volume.h"
 
@@ -274,55 +275,9 @@ __global__ __launch_bounds__(256) void k_list_patches(VolumeDev v, PatchRow* out
 // Chisel::DrawMeshes (Structure/Chisel.cpp:288-355): interleaved vertex stream + rebased indices.
 // One workgroup per complete() patch; every output element is written once, 48 B per vertex.
 // ---------------------------------------------------------------------------------------
-struct DrawPatch {
-  uint32_t slot, nv, nt, flags;  // flags: bit1 wrong_mapping, bit2 labs valid
-  unsigned long long vout, iout;  // output positions (running counts over the patches before this one)
-};
-// one 9-bit field of the colour delta.  A delta that is not a number (labs of a one-vertex cluster: 0 / (N - 1) = 0 / 0)
-// packs as a zero delta, 255: stated here, as in the oracle, not left to what the hardware conversion makes of a NaN
-__device__ __forceinline__ int pack_delta(const float a) { return a != a ? 255 : (int)(a * 255.0f) + 255; }
 __global__ __launch_bounds__(256) void k_draw(VolumeDev v, const DrawPatch* __restrict__ pt, float* __restrict__ out_v,
                                               uint32_t* __restrict__ out_i) {
-  const DrawPatch P = pt[blockIdx.x];
-  const MeshRec rec = v.mesh_rec[P.slot];
-  const float ox = (float)(rec.texloc % (unsigned long long)v.atlas_w);  // Atlas::GetTexLoc (Atlas.cpp:66-69)
-  const float oy = (float)(rec.texloc / (unsigned long long)v.atlas_w);
-  const float rx = rec.ratio[0], ry = rec.ratio[1];
-  const float aw = (float)v.atlas_w, ah = (float)v.atlas_h;
-  for (uint32_t j = threadIdx.x; j < P.nt; j += 256)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out_i[P.iout + 3 * (size_t)j + a] = (uint32_t)tri_plane(v, rec.block, a)[j] + (uint32_t)P.vout;
-  for (uint32_t k = threadIdx.x; k < P.nv; k += 256) {
-    float* o = out_v + 12 * (P.vout + k);
-    float tx = mesh_plane(v, rec.block, kMpTc)[k], ty = mesh_plane(v, rec.block, kMpTc + 1)[k];
-    if (rx < 1.0f) tx = tx * rx;
-    if (ry < 1.0f) ty = ty * ry;
-    tx = tx + ox;
-    ty = ty + oy;
-    const float c0 = mesh_plane(v, rec.block, kMpCol)[k], c1 = mesh_plane(v, rec.block, kMpCol + 1)[k],
-                c2 = mesh_plane(v, rec.block, kMpCol + 2)[k];
-    int rgb = (int)(c0 * 255.0f);
-    rgb = (rgb << 8) + (int)(c1 * 255.0f);
-    rgb = (rgb << 8) + (int)(c2 * 255.0f);
-    float adj = 0.0f;
-    if (P.flags & 4u) {
-      const float a0 = mesh_plane(v, rec.block, kMpLabs)[k] - mesh_plane(v, rec.block, kMpTcol)[k],
-                  a1 = mesh_plane(v, rec.block, kMpLabs + 1)[k] - mesh_plane(v, rec.block, kMpTcol + 1)[k],
-                  a2 = mesh_plane(v, rec.block, kMpLabs + 2)[k] - mesh_plane(v, rec.block, kMpTcol + 2)[k];
-      int ad = pack_delta(a0);
-      ad = (ad << 9) + pack_delta(a1);
-      ad = (ad << 9) + pack_delta(a2);
-      adj = (float)ad;
-    }
-    const float4 q0 = make_float4(mesh_plane(v, rec.block, kMpPos)[k], mesh_plane(v, rec.block, kMpPos + 1)[k],
-                                  mesh_plane(v, rec.block, kMpPos + 2)[k], 50.0f);
-    const float4 q1 = make_float4((float)rgb, adj, tx / aw, ty / ah);
-    const float4 q2 = make_float4(mesh_plane(v, rec.block, kMpNrm)[k], mesh_plane(v, rec.block, kMpNrm + 1)[k],
-                                  mesh_plane(v, rec.block, kMpNrm + 2)[k], (P.flags & 2u) ? 1.0f : 0.0f);
-    reinterpret_cast<float4*>(o)[0] = q0;
-    reinterpret_cast<float4*>(o)[1] = q1;
-    reinterpret_cast<float4*>(o)[2] = q2;
-  }
+  draw_patch_body(v, pt[blockIdx.x], out_v, out_i);  // (tf_draw_body.h: shared with the resident model stream, tf_model.hip)
 }
 
 // Patch mirrors of listed chunks: per patch record + texcoord / texcolor / labs in the reference's layouts
@@ -945,9 +900,7 @@ int tf_compensate_color(tf_volume* v, int64_t* out_n_clusters) {
 }
 
 // Patch::complete (Patch.cpp:191-196) from a listed row
-static bool row_complete(const PatchRow& r) {
-  return r.nv > 0 && (r.state & kMsSimplified) && (r.pflags & kPfHasImage) && r.frameid >= 0;
-}
+static bool row_complete(const PatchRow& r) { return draw_complete(r.nv, r.state, r.pflags, r.frameid); }
 
 static int draw_common(tf_volume* v, float* d_vertices, uint32_t* d_indices, float* h_vertices, uint32_t* h_indices,
                        int64_t cap_v, int64_t cap_i, int64_t* out_nv, int64_t* out_ni) {
@@ -963,8 +916,7 @@ static int draw_common(tf_volume* v, float* d_vertices, uint32_t* d_indices, flo
     if (!row_complete(r)) continue;
     DrawPatch P;
     P.slot = r.slot; P.nv = r.nv; P.nt = r.nt;
-    const bool labs_valid = (r.pflags & kPfAdjusted) && !(r.pflags & kPfWrong);  // has_adjusted && !labs.empty()
-    P.flags = 1u | ((r.pflags & kPfWrong) ? 2u : 0u) | (labs_valid ? 4u : 0u);
+    P.flags = draw_flags(r.pflags);
     P.vout = vout; P.iout = iout;
     vout += r.nv; iout += 3ull * r.nt;
     dp.push_back(P);
@@ -1106,10 +1058,3 @@ int tf_atlas_download_rows(tf_volume* v, int64_t row0, int64_t row1, uint8_t* ds
 }
 
 }  // extern "C"
-
-// Chisel::DrawMeshes, device form, for tf_render_model (tf_render.hip): TF_ERR_CAPACITY with the counts set when a buffer is
-// too small
-int tf::draw_stream_device(tf_volume* v, float* d_vertices, uint32_t* d_indices, int64_t cap_vertices, int64_t cap_indices,
-                           int64_t* n_vertices, int64_t* n_indices) {
-  return draw_common(v, d_vertices, d_indices, nullptr, nullptr, cap_vertices, cap_indices, n_vertices, n_indices);
-}

@@ -165,6 +165,7 @@ static int status_to_error(uint32_t st) {
   if (st & kStMeshFull) m += " the mesh store is exhausted: no block left for a chunk's first mesh (raise tf_config.mesh_blocks) or for a mesh beyond mesh_max_vertices / mesh_max_triangles (raise tf_config.mesh_overflow_blocks or those)";
   if (st & kStAtlasFull) m += " No enough space for texture storage.";  // std::overflow_error text, Atlas.cpp:53
   if (st & kStXchgFull) m += " a rank's ghost band did not fit the boundary exchange block (raise cap_records)";
+  if (st & kStModelFull) m += " the model stream does not fit its buffers (tf_model_stream_reserve, or tf_model_stream_update to grow them)";
   if (st & kStInvalid) m += " a listed chunk is no node of the resident chunk graph, or its label names no cached keyframe";
   set_error(m);
   if (st & kStAtlasFull) return TF_ERR_ATLAS_FULL;
@@ -537,7 +538,7 @@ int tf_volume_reset(tf_volume* v) {
   TF_HIP(hipStreamSynchronize(v->stream));
   texmap_release(v);  // TexMap::clear, and its storage given back
   cc_release(v);
-  render_release(v);
+  model_release(v);
   rc = init_device_state(v);
   if (rc) return rc;
   return atlas_reset(v);
@@ -1732,7 +1733,7 @@ int tf_get_texture_stats(tf_volume* v, tf_texture_stats* out) {
 
 int tf_sync(tf_volume* v) {
   if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
-  TF_DEV(v);
+  TF_DEV_READER(v);
   CtlSnap ctl;
   return fetch_ctl(v, &ctl);
 }

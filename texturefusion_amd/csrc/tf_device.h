@@ -33,6 +33,7 @@ constexpr uint32_t kStHashFull = 16u;
 constexpr uint32_t kStMeshFull = 32u;   // a mesh exceeds tf_config.mesh_max_vertices / mesh_max_triangles
 constexpr uint32_t kStAtlasFull = 64u;
 constexpr uint32_t kStXchgFull = 128u;  // a rank's ghost band did not fit the exchange block (raise cap_records)  // Atlas::AddPatch overflow (std::overflow_error, Atlas.cpp:52-53)
+constexpr uint32_t kStModelFull = 512u; // the model stream's buffers are too small for the model (tf_model_stream_reserve / tf_model_stream_update)
 constexpr uint32_t kStInvalid = 256u;   // a work entry the call cannot process (tf_generate_patches_selected: no node / label without a cached keyframe)
 
 struct Cam {

@@ -589,7 +589,7 @@ int tf_query_points_device(tf_volume* v, const float* d_xyz, int64_t n, uint32_t
                            float* d_grad3, float* d_sdf_tri, uint8_t* d_rgb3, uint32_t* d_flags) {
   int rc = query_check(v, d_xyz, n, want_mask, d_sdf, d_weight, d_grad3, d_sdf_tri, d_rgb3, d_flags);
   if (rc) return rc;
-  TF_DEV(v);
+  TF_DEV_READER(v);
   if (n == 0) return TF_OK;
   return query_launch(v, d_xyz, (uint32_t)n, want_mask, d_sdf, d_weight, d_grad3, d_sdf_tri, d_rgb3, d_flags);
 }
@@ -598,7 +598,7 @@ int tf_query_points(tf_volume* v, const float* xyz, int64_t n, uint32_t want_mas
                     float* sdf_tri, uint8_t* rgb3, uint32_t* flags) {
   int rc = query_check(v, xyz, n, want_mask, sdf, weight, grad3, sdf_tri, rgb3, flags);
   if (rc) return rc;
-  TF_DEV(v);
+  TF_DEV_READER(v);
   if (n == 0) return TF_OK;
   // staging: xyz | sdf | weight | grad | sdf_tri | flags | rgb
   Layout L;
@@ -647,7 +647,7 @@ int tf_raycast_device(tf_volume* v, const float pose[12], float near_plane, floa
   RayCam cam;
   int rc = ray_check(v, pose, near_plane, far_plane, max_steps, &cam);
   if (rc) return rc;
-  TF_DEV(v);
+  TF_DEV_READER(v);
   return ray_launch(v, pose, near_plane, far_plane, max_steps, cam, d_depth, d_normal, d_rgba, d_vertex);
 }
 
@@ -656,7 +656,7 @@ int tf_raycast(tf_volume* v, const float pose[12], float near_plane, float far_p
   RayCam cam;
   int rc = ray_check(v, pose, near_plane, far_plane, max_steps, &cam);
   if (rc) return rc;
-  TF_DEV(v);
+  TF_DEV_READER(v);
   const size_t P = (size_t)cam.W * cam.H;
   Layout L;
   const size_t o_d = L.take(depth ? 4 * P : 0), o_n = L.take(normal ? 12 * P : 0), o_c = L.take(rgba ? 4 * P : 0),

@@ -84,6 +84,7 @@ struct RenderArgs {
   unsigned long long* keys;  // [H][W]
   uint32_t* queue;           // [ntri]
   uint32_t* qcount;
+  const uint32_t* counts;    // null, or the model stream's control block: {n_vertices, n_indices, ...} bound nv / ntri
   uint8_t* rgba;
   float* depth;
   int32_t* tri;
@@ -94,6 +95,14 @@ struct Tri {
   float z0, z1, z2;
   uint32_t i0, i1, i2;  // vertices of the oriented triangle (i0 is the stream's first: 1 and 2 swap)
 };
+
+// the stream's lengths when they are device words (tf_model.hip's control block): nv / ntri as given are then the capacity
+// the grids and the queue were sized from, and surplus lanes leave at once.  Wave-uniform loads: the counts stay scalar.
+__device__ __forceinline__ void render_counts(RenderArgs& a) {
+  if (!a.counts) return;
+  a.nv = min(a.nv, a.counts[0]);
+  a.ntri = min(a.ntri, a.counts[1] / 3u);
+}
 
 __device__ __forceinline__ bool render_vertex(const RenderArgs& a, uint32_t i, float* zc, int* X, int* Y) {
   const float* p = a.vtx + 12 * (size_t)i;
@@ -178,6 +187,7 @@ __device__ __forceinline__ void tri_sample(const RenderArgs& a, const Tri& T, ui
 }
 
 __global__ __launch_bounds__(256) void k_render_bin(RenderArgs a) {
+  render_counts(a);
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;
   if (t >= a.ntri) return;
   Tri T;
@@ -192,6 +202,7 @@ __global__ __launch_bounds__(256) void k_render_bin(RenderArgs a) {
 }
 
 __global__ __launch_bounds__(256) void k_render_large(RenderArgs a) {
+  render_counts(a);
   const uint32_t n = min(*a.qcount, a.ntri);
   for (uint32_t q = blockIdx.x; q < n; q += gridDim.x) {
     const uint32_t t = a.queue[q];
@@ -220,6 +231,7 @@ __device__ __forceinline__ void tex_axis(float u, int n, int* i0, int* i1, float
 __device__ __forceinline__ uint8_t to_u8(const float c) { return (uint8_t)(int)(fminf(fmaxf(c, 0.0f), 1.0f) * 255.0f + 0.5f); }
 
 __global__ __launch_bounds__(256) void k_render_resolve(RenderArgs a) {
+  render_counts(a);
   const uint32_t o = blockIdx.x * 256 + threadIdx.x;
   if (o >= (uint32_t)(a.W * a.H)) return;
   const unsigned long long key = a.keys[o];
@@ -326,7 +338,8 @@ RenderScratch render_layout(Layout& L, const RenderCam& cam, size_t ntri) {
 
 int render_launch(tf_volume* v, const RenderCam& cam, const float* d_vtx, int64_t nv, const uint32_t* d_idx, int64_t ni,
                   const uint8_t* d_tex, int tw, int th, const float* pose, float near_plane, float far_plane, int mode,
-                  uint8_t* scratch, const RenderScratch& rs, uint8_t* d_rgba, float* d_depth, int32_t* d_tri) {
+                  uint8_t* scratch, const RenderScratch& rs, uint8_t* d_rgba, float* d_depth, int32_t* d_tri,
+                  const uint32_t* d_counts = nullptr) {
   RenderArgs a;
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) a.R[3 * r + c] = pose[4 * r + c];
@@ -341,6 +354,7 @@ int render_launch(tf_volume* v, const RenderCam& cam, const float* d_vtx, int64_
   a.keys = reinterpret_cast<unsigned long long*>(scratch + rs.o_keys);
   a.queue = reinterpret_cast<uint32_t*>(scratch + rs.o_queue);
   a.qcount = reinterpret_cast<uint32_t*>(scratch + rs.o_cnt);
+  a.counts = d_counts;
   a.rgba = d_rgba; a.depth = d_depth; a.tri = d_tri;
   const size_t P = (size_t)cam.W * cam.H;
   TF_HIP(hipMemsetAsync(a.keys, 0xFF, 8 * P, v->stream));  // kNoKey
@@ -371,23 +385,21 @@ int out_fetch(tf_volume* v, const Stage& sg, const RenderOut& o, size_t P, uint8
   return TF_OK;
 }
 
-// the current model as a stream of the handle's own (Chisel::DrawMeshes, device form); grows the buffers on demand
-int model_stream(tf_volume* v, int64_t* nv, int64_t* ni) {
-  RenderState& r = v->render;
-  for (int pass = 0; pass < 2; ++pass) {
-    int rc = draw_stream_device(v, r.vtx.as<float>(), r.idx.as<uint32_t>(), (int64_t)(r.vtx.bytes / 48), (int64_t)(r.idx.bytes / 4), nv, ni);
-    if (rc != TF_ERR_CAPACITY) return rc;
-    int64_t cv = 1 << 16, ci = 3 << 16;
-    while (cv < *nv) cv <<= 1;
-    while (ci < *ni) ci <<= 1;
-    if ((rc = fit(r.vtx, (size_t)cv * 48, v->stream)) || (rc = fit(r.idx, (size_t)ci * 4, v->stream))) return rc;
-  }
-  return TF_ERR_CAPACITY;
+// The model's stream for a render (tf_model.hip).  Current: no pack, no wait -- the lengths are the host's when it has read
+// them, else the capacity with the control block as d_counts.  Not current: the synchronous pack, one wait.
+struct ModelView { const float* vtx; const uint32_t* idx; const uint32_t* counts; int64_t nv, ni; };
+int model_view(tf_volume* v, ModelView* out) {
+  ModelState& m = v->model;
+  if (m.packed && m.gen == v->model_gen) ++m.hits;
+  else if (const int rc = model_stream_sync(v)) return rc;
+  out->vtx = m.vtx.as<float>(); out->idx = m.idx.as<uint32_t>();
+  out->counts = m.counted ? nullptr : m.ctl.as<uint32_t>();
+  out->nv = m.counted ? m.nv : m.cap_v;
+  out->ni = m.counted ? m.ni : m.cap_i - m.cap_i % 3;
+  return TF_OK;
 }
 
 }  // namespace
-
-void tf::render_release(tf_volume* v) { v->render = RenderState{}; }
 
 extern "C" {
 
@@ -399,7 +411,7 @@ int tf_render_stream_device(tf_volume* v, const float* d_vertices, int64_t n_ver
                         d_depth, d_tri, &cam);
   if (rc) return rc;
   if ((n_vertices > 0 && !d_vertices) || (n_indices > 0 && !d_indices)) { set_error("null stream"); return TF_ERR_INVALID; }
-  TF_DEV(v);
+  TF_DEV_READER(v);
   Layout L;
   const RenderScratch rs = render_layout(L, cam, (size_t)(n_indices / 3));
   // (no stage_begin: nothing touches the pool's host half, and the stream orders this render behind every earlier user of
@@ -417,7 +429,7 @@ int tf_render_stream(tf_volume* v, const float* vertices, int64_t n_vertices, co
                         tri, &cam);
   if (rc) return rc;
   if ((n_vertices > 0 && !vertices) || (n_indices > 0 && !indices)) { set_error("null stream"); return TF_ERR_INVALID; }
-  TF_DEV(v);
+  TF_DEV_READER(v);
   const size_t P = (size_t)cam.W * cam.H;
   const size_t bv = 48 * (size_t)n_vertices, bi = 4 * (size_t)n_indices;
   const size_t bt = texture && tex_w > 0 && tex_h > 0 ? 3 * (size_t)tex_w * tex_h : 0;
@@ -445,14 +457,14 @@ int tf_render_model_device(tf_volume* v, const float pose[12], float near_plane,
   RenderCam cam;
   int rc = render_check(v, 0, 0, nullptr, 0, 0, pose, near_plane, far_plane, mode, d_rgba, d_depth, d_tri, &cam);
   if (rc) return rc;
-  TF_DEV(v);
-  int64_t nv = 0, ni = 0;
-  if ((rc = model_stream(v, &nv, &ni))) return rc;
+  TF_DEV_READER(v);
+  ModelView mv;
+  if ((rc = model_view(v, &mv))) return rc;
   Layout L;
-  const RenderScratch rs = render_layout(L, cam, (size_t)(ni / 3));
+  const RenderScratch rs = render_layout(L, cam, (size_t)(mv.ni / 3));
   if ((rc = reserve(v, v->scratch, L.size, 0))) return rc;
-  return render_launch(v, cam, v->render.vtx.as<float>(), nv, v->render.idx.as<uint32_t>(), ni, nullptr, 0, 0, pose, near_plane, far_plane, mode,
-                       v->scratch.d.as<uint8_t>(), rs, d_rgba, d_depth, d_tri);
+  return render_launch(v, cam, mv.vtx, mv.nv, mv.idx, mv.ni, nullptr, 0, 0, pose, near_plane, far_plane, mode,
+                       v->scratch.d.as<uint8_t>(), rs, d_rgba, d_depth, d_tri, mv.counts);
 }
 
 int tf_render_model(tf_volume* v, const float pose[12], float near_plane, float far_plane, int32_t mode, uint8_t* rgba,
@@ -460,19 +472,19 @@ int tf_render_model(tf_volume* v, const float pose[12], float near_plane, float 
   RenderCam cam;
   int rc = render_check(v, 0, 0, nullptr, 0, 0, pose, near_plane, far_plane, mode, rgba, depth, tri, &cam);
   if (rc) return rc;
-  TF_DEV(v);
-  int64_t nv = 0, ni = 0;
-  if ((rc = model_stream(v, &nv, &ni))) return rc;
+  TF_DEV_READER(v);
+  ModelView mv;
+  if ((rc = model_view(v, &mv))) return rc;
   const size_t P = (size_t)cam.W * cam.H;
   Layout L;
   const RenderOut ro = out_layout(L, P, rgba, depth, tri);
   const size_t host_bytes = L.size;
-  const RenderScratch rs = render_layout(L, cam, (size_t)(ni / 3));
+  const RenderScratch rs = render_layout(L, cam, (size_t)(mv.ni / 3));
   Stage sg;
   if ((rc = stage_begin(v, v->scratch, L.size, host_bytes, &sg))) return rc;
-  rc = render_launch(v, cam, v->render.vtx.as<float>(), nv, v->render.idx.as<uint32_t>(), ni, nullptr, 0, 0, pose, near_plane, far_plane, mode,
+  rc = render_launch(v, cam, mv.vtx, mv.nv, mv.idx, mv.ni, nullptr, 0, 0, pose, near_plane, far_plane, mode,
                      sg.d, rs, rgba ? sg.d + ro.o_c : nullptr, depth ? sg.dp<float>(ro.o_d) : nullptr,
-                     tri ? sg.dp<int32_t>(ro.o_t) : nullptr);
+                     tri ? sg.dp<int32_t>(ro.o_t) : nullptr, mv.counts);
   if (rc) return rc;
   return out_fetch(v, sg, ro, P, rgba, depth, tri);
 }

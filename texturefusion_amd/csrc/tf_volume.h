@@ -33,6 +33,7 @@ void set_error(const std::string& msg);
 #define TF_DEV_NOFLUSH(v)                                                                   \
   do {                                                                                      \
     ++(v)->call_seq;                                                                        \
+    ++(v)->model_gen;                                                                       \
     hipError_t _e = hipSetDevice((v)->device);                                              \
     if (_e != hipSuccess) {                                                                 \
       ::tf::set_error(std::string("hipSetDevice: ") + hipGetErrorString(_e));               \
@@ -58,6 +59,19 @@ void set_error(const std::string& msg);
       int _rc = ::tf::patch_flush(v);                                                       \
       if (_rc) return _rc;                                                                  \
     }                                                                                       \
+  } while (0)
+
+// The model generation (tf_volume::model_gen) decides whether the resident model stream (ModelState) is current.  It is
+// advanced by EVERY entry point -- TF_DEV_NOFLUSH above -- except the few that enter through TF_DEV_READER: calls that
+// provably change no mesh, no patch and no pool slot (tf_model_stream_*, tf_render_*, tf_raycast*, tf_query_points*,
+// tf_sync).  A reader that is not on that list costs one repack; a writer cannot be forgotten.  A reader that has to bring
+// deferred frames or a pending patch stage onto the stream first is a writer for that call.
+#define TF_DEV_READER(v)                                                                    \
+  do {                                                                                      \
+    const uint64_t _gen = (v)->model_gen;                                                   \
+    const bool _writes = (v)->n_pend || (v)->atlas.pend_patch.on;                           \
+    TF_DEV(v);                                                                              \
+    if (!_writes) (v)->model_gen = _gen;                                                    \
   } while (0)
 
 // Scratch pool: a device half and a pinned host half, two fitted buffers (tf_mem.h) that reserve() grows on demand to a
@@ -166,10 +180,22 @@ struct CcState {
   DevMem block;
 };
 
-// tf_render_model (tf_render.hip): the model's DrawMeshes stream, empty until first use, fitted on demand
-struct RenderState {
-  DevMem vtx;  // f32[cap_v][12]
-  DevMem idx;  // u32[cap_i]
+// The model's DrawMeshes stream, resident in the handle (tf_model.hip): packed on the device, counts in device words,
+// kept until the model changes.  Everything is empty until first use; `ModelState{}` gives it all back.
+struct ModelState {
+  DevMem vtx;    // f32[cap_v][12]
+  DevMem idx;    // u32[cap_i]
+  DevMem list;   // the complete() patches as listed | the same in ascending chunk key, [max_chunks] each
+  DevMem rank;   // u32[max_chunks] rank of every listed patch
+  DevMem rec;    // DrawPatch[max_chunks] in rank order
+  DevMem ctl;    // u32[8] the control block tf_model_stream_get hands out, u32[8] the pack's own words behind it
+  PinMem h_ctl;  // the control block as the synchronous update reads it back
+  int64_t cap_v = 0, cap_i = 0;  // capacity in vertices / indices (0: none yet)
+  bool packed = false;           // a pack is on the stream (or through) ...
+  uint64_t gen = 0;              // ... and this was tf_volume::model_gen when it was enqueued
+  bool counted = false;          // the host has read that pack's counts: nv / ni
+  int64_t nv = 0, ni = 0;
+  uint64_t packs = 0, hits = 0;  // tf_model_stream_stats
 };
 
 // RCCL communicator of the handle (tf_comm_init) and the exchange buffers
@@ -299,7 +325,8 @@ struct tf_volume {
   tf::TexMapDev tm{};   // TexMap resident on the device: null pointers until the first tf_texmap_* call
   tf::TexMapState tmx;
   tf::CcState cc;
-  tf::RenderState render;
+  tf::ModelState model;
+  uint64_t model_gen = 0;  // advanced by every entry point that is not a whitelisted reader (TF_DEV_READER)
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
   // band counts of a frame's selection as the host sees them: pinned words [0] tag (frame epoch + 1), [1..4] FrameCtl::band_cnt
   tf::PinMem h_xchg;  // u32[16], null until first use (xchg_words)
@@ -391,10 +418,12 @@ int patch_stage_device(tf_volume* v, const int4* d_list, uint32_t n, uint32_t* d
 // Chisel::CompensateColor enqueued on the handle's stream, nothing read back (tf_cc.hip); cc_release frees its buffers
 int cc_enqueue(tf_volume* v, uint32_t* d_n_clusters);
 void cc_release(tf_volume* v);
-// tf_render_model's stream: DrawMeshes' device form (tf_atlas.hip); render_release frees the handle's stream buffers
-int draw_stream_device(tf_volume* v, float* d_vertices, uint32_t* d_indices, int64_t cap_vertices, int64_t cap_indices,
-                       int64_t* n_vertices, int64_t* n_indices);
-void render_release(tf_volume* v);
+// the resident model stream (tf_model.hip).  model_pack_enqueue: list, rank, scan and write on the handle's stream, nothing
+// read back (the buffers exist and have a capacity); model_stream_sync: the pack, one wait for the control block, the
+// buffers grown and the pack repeated on overflow -- ModelState::nv / ni are the counts afterwards; model_release frees all
+int model_pack_enqueue(tf_volume* v);
+int model_stream_sync(tf_volume* v);
+void model_release(tf_volume* v);
 void launch_patch_fused(tf_volume* v, const VolumeDev& d, int par, const KfDev& kf, hipStream_t s);
 inline uint64_t host_pack_id(const int32_t id[3]) {
   return ((uint64_t)((uint32_t)(id[0] + (1 << 20)) & 0x1FFFFFu) << 42) |
