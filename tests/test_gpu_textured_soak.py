@@ -14,6 +14,31 @@ from tests.test_gpu_atlas import _compare_patches, _compare_atlas
 pytestmark = pytest.mark.gpu
 
 
+def compare_with_oracle(ov, oa, gv, stride=1):
+    """chunks, meshes, patches, atlas_loc_next and the atlas rows in use of a synchronised volume against the oracle's, bit for
+    bit (every stride-th chunk / mesh / patch); returns the number of meshes"""
+    oids = sorted_ids(ov.list_chunks())
+    assert np.array_equal(oids, sorted_ids(gv.list_chunks()))
+    assert_chunks_equal(ov, gv, oids[::stride], "textured soak")
+    mids = sorted_ids(ov.list_meshes())
+    assert np.array_equal(mids, sorted_ids(gv.list_meshes()))
+    sub = mids[::stride]
+    voff, ioff, V, N, Cc, I, adj, simp = gv.get_meshes(sub)
+    for i, cid in enumerate(sub):
+        m = ov.get_mesh(cid)
+        assert np.array_equal(V[voff[i]:voff[i + 1]].view(np.uint32), m["verts"].view(np.uint32)), cid
+        assert np.array_equal(N[voff[i]:voff[i + 1]].view(np.uint32), m["normals"].view(np.uint32)), cid
+        assert np.array_equal(I[ioff[i]:ioff[i + 1]], m["indices"]), cid
+        assert bool(simp[i]) == m["simplified"] and np.array_equal(adj[i], m["adj"]), cid
+    assert gv.atlas_loc_next() == oa.loc_next()
+    g = _compare_patches(ov, gv, sub, "textured soak")
+    gall = gv.get_patches(mids)
+    used = gall["texloc"][gall["texloc"] != np.uint64((1 << 64) - 1)]
+    if len(used):
+        _compare_atlas(oa, gv, oa.hot_range(used))
+    return len(mids)
+
+
 def _run(cam, res, frames, host_frames=False, max_chunks=1 << 17, stride=1):
     ov = O.Volume(res, O.camera_from(cam), O.default_integrator())
     # (TF_SOAK_MESH_BLOCKS: a small mesh store -- the runs of tools/soak_random.py then live off recycled blocks)
@@ -69,26 +94,7 @@ def _run(cam, res, frames, host_frames=False, max_chunks=1 << 17, stride=1):
         poses = np.stack([f[3].reshape(12) for f in frames])
         gv.stream_frames_textured_device([b[0].ptr for b in bufs], [b[1].ptr for b in bufs], poses, np.stack(pinv), 10)
     gv.sync()
-    oids = sorted_ids(ov.list_chunks())
-    assert np.array_equal(oids, sorted_ids(gv.list_chunks()))
-    assert_chunks_equal(ov, gv, oids[::stride], "textured soak")
-    mids = sorted_ids(ov.list_meshes())
-    assert np.array_equal(mids, sorted_ids(gv.list_meshes()))
-    sub = mids[::stride]
-    voff, ioff, V, N, Cc, I, adj, simp = gv.get_meshes(sub)
-    for i, cid in enumerate(sub):
-        m = ov.get_mesh(cid)
-        assert np.array_equal(V[voff[i]:voff[i + 1]].view(np.uint32), m["verts"].view(np.uint32)), cid
-        assert np.array_equal(N[voff[i]:voff[i + 1]].view(np.uint32), m["normals"].view(np.uint32)), cid
-        assert np.array_equal(I[ioff[i]:ioff[i + 1]], m["indices"]), cid
-        assert bool(simp[i]) == m["simplified"] and np.array_equal(adj[i], m["adj"]), cid
-    assert gv.atlas_loc_next() == oa.loc_next()
-    g = _compare_patches(ov, gv, sub, "textured soak")
-    gall = gv.get_patches(mids)
-    used = gall["texloc"][gall["texloc"] != np.uint64((1 << 64) - 1)]
-    if len(used):
-        _compare_atlas(oa, gv, oa.hot_range(used))
-    n_meshes = len(mids)
+    n_meshes = compare_with_oracle(ov, oa, gv, stride)
     for a, b in bufs:
         a.free(); b.free()
     gv.close()
@@ -215,9 +221,9 @@ def test_hall_bench_stream_30_frames(gpu_required):
 
 
 def test_host_frames_deferral_is_not_observable(gpu_required):
-    """tf_integrate_frame_host runs two frames behind internally; any other entry point has to see every frame that was
-    handed over: state queries after 1, 2, 3, 5 and 6 calls (pipeline depths 1, 2, 2, 2, 1 at the flush), a
-    call-by-call integration in between, and another stream of host frames behind it."""
+    """tf_integrate_frame_host runs four frames (kHostDefer) behind internally; any other entry point has to see every frame
+    that was handed over: state queries after 1, 2, 3, 5 and 6 calls (each query flushes: 1, 1, 1, 2 and 1 frames pending at
+    the flush), a call-by-call integration in between, and another stream of host frames behind it."""
     cam = synth.Camera()
     res = np.float32(0.005)
     ov = O.Volume(res, O.camera_from(cam), O.default_integrator())

@@ -8,33 +8,11 @@
 #include <algorithm>
 #include <chrono>
 #include <thread>
-#include <sched.h>
 #include <limits>
-#include <map>
 #include <memory>
-#include <mutex>
 
 #include "tf_host_math.h"
 #include "tf_volume.h"
-
-// Page-locking is a property of the PROCESS: two handles (two volumes on one GPU, or a volume per GPU) may be fed from the
-// same caller buffers.  The ranges the library locked are counted here; the pages are locked by the first handle that
-// registers a range and released by the last that lets go of it.
-namespace {
-struct LockedRange { size_t n; int refs; };
-std::mutex g_locked_mu;
-std::map<const uint8_t*, LockedRange> g_locked;
-}  // namespace
-static int host_range_release(const uint8_t* p) {
-  using namespace tf;
-  std::lock_guard<std::mutex> lk(g_locked_mu);
-  auto it = g_locked.find(p);
-  if (it == g_locked.end()) return TF_OK;
-  if (--it->second.refs > 0) return TF_OK;
-  g_locked.erase(it);
-  TF_HIP(hipHostUnregister(const_cast<uint8_t*>(p)));
-  return TF_OK;
-}
 
 namespace tf {
 
@@ -194,14 +172,12 @@ static int fetch_ctl(tf_volume* v, CtlSnap* out) {
   return TF_OK;
 }
 
-}  // namespace tf
-int tf::sync_status(tf_volume* v, uint32_t* n_tmp) {
+int sync_status(tf_volume* v, uint32_t* n_tmp) {
   CtlSnap ctl;
   const int rc = fetch_ctl(v, &ctl);
   if (n_tmp) *n_tmp = ctl.vc.n_tmp;
   return rc;
 }
-namespace tf {
 
 static int init_device_state(tf_volume* v) {
   VolumeDev& d = v->dev;
@@ -248,15 +224,14 @@ static void discard_primed(tf_volume* v) {
   v->xchg_pub_enq = 0;  // (band counts published for a discarded selection are stale)
 }
 
-}  // namespace tf (the two functions below are shared with tf_unit.hip: declared in tf_volume.h)
-int tf::xchg_words(tf_volume* v) {
+// (the two functions below are shared with tf_unit.hip: declared in tf_volume.h)
+int xchg_words(tf_volume* v) {
   if (v->h_xchg) return TF_OK;
   const int rc = v->h_xchg.alloc(64);
   if (!rc) memset(v->h_xchg.p, 0, 64);
   return rc;
 }
-int tf::xchg_band_counts(tf_volume* v, const tf::FrameCtl* ctl, uint32_t tag, uint32_t cnt[4], hipStream_t s) {
-  using namespace tf;
+int xchg_band_counts(tf_volume* v, const FrameCtl* ctl, uint32_t tag, uint32_t cnt[4], hipStream_t s) {
   if (!s) s = v->stream;
   const int rc = xchg_words(v);
   if (rc) return rc;
@@ -285,8 +260,7 @@ int tf::xchg_band_counts(tf_volume* v, const tf::FrameCtl* ctl, uint32_t tag, ui
   for (int q = 0; q < 4; ++q) cnt[q] = w[1 + q];
   return TF_OK;
 }
-int tf::launch_prepare(tf_volume* v, const tf::Pose& pose, bool with_acquire, hipStream_t s) {
-  using namespace tf;
+int launch_prepare(tf_volume* v, const Pose& pose, bool with_acquire, hipStream_t s) {
   if (!s) s = v->stream;
   const SelectConsts sc = make_select_consts(pose.p, v->res);
   prof_begin(v, TF_PROF_BBOX, s);
@@ -306,7 +280,6 @@ int tf::launch_prepare(tf_volume* v, const tf::Pose& pose, bool with_acquire, hi
   return TF_OK;
 }
 
-namespace tf {
 // Make the device-resident list equal to the caller's list (upload + slot lookup if it is not
 // the list the last tf_prepare produced).
 static int sync_list(tf_volume* v, const int32_t* ids, int64_t n) {
@@ -344,6 +317,338 @@ static bool flags_current(const tf_volume* v, const std::vector<uint8_t>& mirror
   return v->host_flags_n == n && v->host_list_n == n && (int64_t)mirror.size() == n && memcmp(mirror.data(), flags, (size_t)n) == 0;
 }
 
+// Chisel::UpdateMeshes -> CompressMeshes -> GeneratePatches(label = this frame) -> UpdateAtlas over the dirty
+// chunks of ONE integrated frame (GCFusion/MobileFusion.cpp:327-382 without the host-side view selection): `sel`
+// holds the frame's visible list with its needsUpdate flags, `frame_epoch` the finalize epoch of that frame.
+// The patch stage (adjacency exchange, slot hand-out, projection, blit) reads meshes and images only; it is left
+// PENDING here and rides on the next frame's launch next to that frame's voxel update (AtlasState::pend_patch).
+int fused_arm(tf_volume* v) {
+  AtlasState& a = v->atlas;
+  if (a.fused_armed) return TF_OK;
+  // first textured frame after a reset / a call-by-call atlas call: empty work lists
+  AtlasCtl::Set z[2];
+  memset(z, 0, sizeof(z));
+  TF_HIP(hipMemcpyAsync(&v->dev.actl->set[0], z, sizeof(z), hipMemcpyHostToDevice, v->stream));
+  TF_HIP(hipMemsetAsync(v->dev.patch_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
+  TF_HIP(hipMemsetAsync(v->dev.wl_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
+  TF_HIP(hipStreamSynchronize(v->stream));
+  a.fused_par = 0;
+  a.fused_armed = true;
+  return TF_OK;
+}
+
+// Neighbour table (VolumeDev::nbr): every filter launch carries a seq above that of every launch ahead of it on the
+// stream, so that a row it checks outlives exactly the key insertions that come later (VolCtl::create_seq).  After 2^32
+// launches the table starts over.
+uint32_t nbr_next_seq(tf_volume* v) {
+  if (v->dev.seq >= 0xFFFFFFF0u) {
+    (void)hipMemsetAsync(v->dev.nbr, 0, (size_t)v->dev.max_chunks * kNbrWords * 4, v->stream);
+    (void)hipMemsetAsync(&v->dev.vctl->create_seq, 0, 4, v->stream);
+    v->dev.seq = 1;
+  }
+  return ++v->dev.seq;
+}
+
+int boundary_pack_block_on(tf_volume* v, void* d_block, int64_t cap_records, hipStream_t s) {
+  uint8_t* blk = reinterpret_cast<uint8_t*>(d_block);
+  TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, s));
+  launch_boundary_pack(v->dev, blk + 16, (uint32_t)cap_records, s);
+  v->dev.xl_par ^= 1u;  // (the voxel kernels list what they touch from now on into the other list)
+  launch_boundary_headers(v->dev, reinterpret_cast<uint32_t*>(blk), (uint32_t)cap_records, nullptr, 0, s);  // the count travels in-band
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+int boundary_pack_bands2_on(tf_volume* v, void* d_block_down, int64_t cap_down, void* d_block_up, int64_t cap_up, hipStream_t s) {
+  // ONE launch: the counters live in VolCtl::xchg_cnt, the last workgroup writes the in-band counts and re-arms them
+  // (round 4: two memsets + the pack + a header launch -- the exchange of a frame was seven stream operations at their
+  // launch floor, 49 us with nothing on the wire; profiles/r5/README.md)
+  launch_boundary_pack_bands(v->dev, reinterpret_cast<uint8_t*>(d_block_down), reinterpret_cast<uint8_t*>(d_block_up),
+                             (uint32_t)cap_down, (uint32_t)cap_up, s);
+  v->dev.xl_par ^= 1u;  // (the voxel kernels list what they touch from now on into the other list)
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+
+// claimed: the dirty set of this frame is already in the lists of the current parity -- K-A built it (FrameStage::claim_par
+// = the parity used here), or the caller ran launch_dirty_frame over each of its lists (the keyframe unit)
+int texture_stage(tf_volume* v, const SelBuf& sel, const FrameImages& img, uint32_t frame_epoch,
+                      const float* pose_inv16, int32_t frame_id, bool claimed, const FrameCtl* next_ctl, bool ride_filter,
+                      bool sized_xchg, int phase, const KfStoreArgs* store) {
+  AtlasState& a = v->atlas;
+  if (phase == 2) {
+    // second half of a stage whose first half (dirty set + interior meshes) ran before the caller's own exchange
+    if (!a.phase1_on || a.phase1_epoch != frame_epoch) { set_error("tf_texture_frame_device_phase: phase 2 without phase 1 of the same frame"); return TF_ERR_INVALID; }
+    a.phase1_on = false;
+    const int par = a.fused_par;
+    a.fused_par ^= 1;
+    VolumeDev d = v->dev;
+    d.sel = sel;
+    d.work_ids = v->dev.work_ids + (size_t)par * d.max_chunks;
+    d.work_slot = v->dev.work_slot + (size_t)par * d.max_chunks;
+    prof_begin(v, TF_PROF_MESH);
+    d.seq = nbr_next_seq(v);
+    launch_mesh(d, v->mesh_par, d.work_ids, &d.actl->set[par].n_work, d.max_chunks, ++v->mesh_epoch, v->res, true, par ^ 1, 0u, nullptr, par,
+                v->stream, nullptr, &v->cam, /*cls=*/2);
+    v->mesh_par ^= 1;
+    prof_end(v);
+    return texture_stage_finish(v, img, frame_epoch, pose_inv16, frame_id, par);
+  }
+  if (a.phase1_on) { set_error("a texture stage is half done: call tf_texture_frame_device_phase(.., 2) first"); return TF_ERR_INVALID; }
+  // A patch stage still pending here (the previous textured frame's) must read its meshes before this frame's mesher
+  // rewrites them: it goes out on its own first -- or (ride_filter: the keyframe unit, which has no k_frame launch for it)
+  // rides on this frame's FILTER launch (launch_mesh below).  In the per-frame stream the stage rides on k_frame instead:
+  // next to the filter the two latency chains cost more than the stage costs K-A (profiles/r4/README.md, runs c2 / s1;
+  // variants/r4_experiments.patch has the knob).
+  const bool ride = a.pend_patch.on && a.fused_armed && ride_filter;
+  int rc = TF_OK;
+  if (!ride) { rc = patch_flush(v); if (rc) return rc; }
+  rc = fused_arm(v);
+  if (rc) return rc;
+  const int par = a.fused_par;
+  if (phase != 1) a.fused_par ^= 1;  // (phase 1: the caller's unpack still appends to this parity's list)
+  VolumeDev d = v->dev;
+  d.sel = sel;
+  d.work_ids = v->dev.work_ids + (size_t)par * d.max_chunks;
+  d.work_slot = v->dev.work_slot + (size_t)par * d.max_chunks;
+  prof_begin(v, TF_PROF_DIRTY);
+  // meshesToUpdate = everything marked since CompressMeshes last cleared it (Chisel.h:192-208, Chisel.cpp:146).  In a
+  // textured stream that is this frame's chunks (stamps <= frame_epoch are cleared); after frames integrated without
+  // the textured unit the older marks are still there and the general dirty list takes over for this frame.
+  if (claimed) { /* nothing to launch: the shard lists of `par` hold the set */ }
+  else if (v->clear_floor < frame_epoch) launch_dirty_backlog(d, par, v->clear_floor, v->stream);
+  else launch_dirty_frame(d, par, frame_epoch + 1u, v->stream);
+  prof_end(v);
+  // (the filter's form follows the dirty-list length of an earlier frame: the kernel leaves it in host-visible memory,
+  // read here without any synchronisation -- whatever value is there is good enough)
+  const uint32_t len_guess = a.h_dirty_len ? *a.h_dirty_len.as<volatile uint32_t>() : 0u;
+  const PatchStage prev = a.pend_patch.st;  // (copied: the pending record is overwritten below)
+  // one filter + mesher pass over the frame's dirty set (cls: every chunk / interior chunks only / boundary chunks only);
+  // the shard lists of this parity are walked in any case: empty when K-A did not claim -- the previous frame's mesher
+  // re-armed them
+  // (new_seq = false: the pass runs NEXT TO the unpack launch of an overlapped exchange, which carries the same seq -- a
+  // key that launch inserts voids what this pass checks of the neighbour table)
+  auto mesh_pass = [&](int cls, const uint32_t* flat_count, bool with_hint, bool with_ride, bool new_seq = true) -> bool {
+    prof_begin(v, TF_PROF_MESH);
+    d.seq = new_seq ? nbr_next_seq(v) : v->dev.seq;
+    std::unique_ptr<AtlasWriteScope> aw;  // (a patch stage riding on the filter launch writes atlas texels)
+    if (with_ride) aw.reset(new AtlasWriteScope(v, prev.kf.kf_id));
+    const bool rode = launch_mesh(d, v->mesh_par, d.work_ids, flat_count, d.max_chunks, ++v->mesh_epoch, v->res, true, par ^ 1,
+                                  len_guess, with_hint ? a.h_dirty_len.as<uint32_t>() : nullptr, par, v->stream, with_ride ? &prev : nullptr,
+                                  &v->cam, cls, store);
+    aw.reset();
+    store = nullptr;  // (once)
+    v->mesh_par ^= 1;
+    prof_end(v);
+    return rode;
+  };
+  bool rode = false;
+  if (phase == 1) {
+    // a caller with its own transport: the interior meshes now, the boundary ones behind its unpack (phase 2).  The flat
+    // list of this parity holds the frame's own entries (stream order: the unpack has not run yet)
+    rode = mesh_pass(1, &d.actl->set[par].n_work, true, false);
+    a.phase1_on = true;
+    a.phase1_epoch = frame_epoch;
+    return TF_OK;
+  }
+  if (v->comm_cap > 0) {  // multi-GPU: ghost bands of this frame's updates, before the mesher reads them
+    // (sized by this frame's selection when the fused stream ran it -- sel.ctl then holds the band counts, tagged with the
+    // frame's epoch + 1; lists of the call-by-call flow and the keyframe unit carry no counts: fixed-capacity blocks)
+    const FrameCtl* xc = sized_xchg ? sel.ctl : nullptr;
+    const FrameCtl* xn = sized_xchg ? next_ctl : nullptr;
+    // The exchange leaves the critical path: pack -> send / receive -> unpack run on a second stream while the main
+    // stream filters and meshes the INTERIOR chunks of the dirty set -- those whose 27-chunk neighbourhood is owned, so that
+    // nothing they read can arrive from another rank -- and only the boundary chunks (and what the arriving ghosts add to
+    // the dirty set) wait for it.  Needs the dirty set in the shard lists K-A filled (claimed: the flat list, which the
+    // unpack launch appends to, is then ignored by the interior pass) and no patch stage riding on the filter launch.
+    // (sized_xchg = the stage comes from the fused stream: `claimed` then means K-A's shard lists; the keyframe unit also
+    // passes claimed, with its dirty set in the FLAT list)
+    const bool overlap = claimed && sized_xchg && !ride && v->xchg_overlap;
+    if (overlap) {
+      if (!v->xstream) {
+        TF_HIP(hipStreamCreateWithFlags(&v->xstream, hipStreamNonBlocking));
+        TF_HIP(hipEventCreateWithFlags(&v->ev_fork, hipEventDisableTiming));
+        TF_HIP(hipEventCreateWithFlags(&v->ev_join, hipEventDisableTiming));
+      }
+      TF_HIP(hipEventRecord(v->ev_fork, v->stream));          // behind the voxel update of this frame
+      (void)nbr_next_seq(v);   // the unpack launch and the interior pass next to it share this seq
+      // the interior pass goes onto the main stream FIRST: the host then spends its time on the exchange's enqueue (band
+      // counts, pack, transport, unpack: ~15 us) while the device already filters and meshes (a kernel trace of the other
+      // order showed the main stream idle for 12 us behind every voxel update)
+      rode = mesh_pass(1, &d.vctl->zero_word, true, false, /*new_seq=*/false);
+      TF_HIP(hipStreamWaitEvent(v->xstream, v->ev_fork, 0));
+      rc = comm_exchange(v, v->comm_cap, par, frame_epoch + 1u, xc, frame_epoch + 1u, xn, v->xstream);
+      if (rc) return rc;
+      TF_HIP(hipEventRecord(v->ev_join, v->xstream));
+      prof_begin(v, TF_PROF_XCHG_WAIT);                        // what of the exchange is NOT hidden behind the interior pass
+      TF_HIP(hipStreamWaitEvent(v->stream, v->ev_join, 0));
+      prof_end(v);
+      rode = mesh_pass(2, &d.actl->set[par].n_work, false, false);
+      v->xchg_overlapped += 1;
+    } else {
+      rc = comm_exchange(v, v->comm_cap, par, frame_epoch + 1u, xc, frame_epoch + 1u, xn);
+      if (rc) return rc;
+      rode = mesh_pass(0, &d.actl->set[par].n_work, true, ride);
+    }
+  } else {
+    rode = mesh_pass(0, &d.actl->set[par].n_work, true, ride);
+  }
+  if (ride) {
+    if (!rode) { set_error("internal: the pending patch stage found no filter launch"); return TF_ERR_INVALID; }
+    rc = patch_launched(v);
+    if (rc) return rc;
+  }
+  return texture_stage_finish(v, img, frame_epoch, pose_inv16, frame_id, par);
+}
+// the tail of a texture stage: this frame's patch stage becomes the pending one
+int texture_stage_finish(tf_volume* v, const FrameImages& img, uint32_t frame_epoch, const float* pose_inv16, int32_t frame_id,
+                             int par) {
+  AtlasState& a = v->atlas;
+  // (CompressMeshes' neighbour exchange, the list of chunks that own a mesh and the slot candidates are produced
+  // by the mesher and consumed by the patch kernel: no kernel of their own in the fused flow)
+  KfDev kf;
+  memset(&kf, 0, sizeof(kf));
+  kf.rgb = reinterpret_cast<const uint8_t*>(img.rgba);
+  kf.depth = img.depth;
+  kf.stride = 4;
+  kf.kf_id = frame_id;
+  static const int pdbg = getenv("TF_PATCH_DBG") ? atoi(getenv("TF_PATCH_DBG")) : 0;  // triage switch
+  kf.pad[0] = pdbg;
+  memcpy(kf.T, pose_inv16, 64);
+  a.pend_patch.on = true;
+  a.pend_patch.st.par = par;
+  a.pend_patch.st.kf = kf;
+  a.pend_patch.host_slot = -1;
+  v->clear_floor = frame_epoch + 1u;  // CompressMeshes cleared meshesToUpdate
+  return TF_OK;
+}
+// the pending patch stage has been put on the stream (as a role of a frame / filter launch or on its own)
+int patch_launched(tf_volume* v) {
+  AtlasState& a = v->atlas;
+  a.pend_patch.on = false;
+  if (a.pend_patch.host_slot >= 0) {  // its frame's staging slot is free once this launch is through = the next one has started
+    host_slot_release(v, a.pend_patch.host_slot);
+    a.pend_patch.host_slot = -1;
+  }
+  return TF_OK;
+}
+int patch_flush(tf_volume* v) {  // the pending patch stage as a launch of its own
+  AtlasState& a = v->atlas;
+  if (!a.pend_patch.on) return TF_OK;
+  {
+    AtlasWriteScope aw(v, a.pend_patch.st.kf.kf_id);
+    launch_patch_fused(v, v->dev, a.pend_patch.st.par, a.pend_patch.st.kf, v->stream);
+  }
+  TF_HIP(hipGetLastError());
+  return patch_launched(v);
+}
+
+// Software-pipelined enqueue of n frames on the handle's stream: launch i carries K-A of frame i,
+// K-C of frame i+1 and K-B of frame i+2 as independent block ranges of one kernel (launch_frame),
+// so the only synchronisation is the kernel boundary.  The arrays may hold n_ahead (<= 2) frames more
+// than the n that are integrated: their selection stages run in this call's last launches and stay
+// valid ("primed") for the next call, which then starts with K-A at once -- a stream fed call by call
+// costs one launch per frame, not n + 2 per call.  tex != nullptr: after K-A of frame i its dirty chunks
+// are meshed and textured from the frame itself (the per-frame unit of BASELINE configs[2]).
+int enqueue_frames(tf_volume* v, int64_t n, int64_t n_ahead, const float* const* d_depth,
+                          const uint8_t* const* d_rgba, const float* poses12, const TexturedArgs* tex) {
+  const int NS = tf_volume::kSelSets;
+  const int64_t n_all = n + n_ahead;
+  auto stage = [&](int64_t f, FrameStage* st) {
+    st->sel = v->selbuf[(v->cur_sel + 1 + f) % NS];
+    st->img.depth = d_depth[f];
+    st->img.rgba = (d_rgba && d_rgba[f]) ? reinterpret_cast<const uchar4*>(d_rgba[f]) : nullptr;
+    st->img.quality = nullptr;
+    memcpy(st->pose.p, poses12 + 12 * f, sizeof(st->pose.p));
+    st->epoch = v->epoch + (uint32_t)f;
+    st->coarse_summ = tex == nullptr;  // a TSDF-only stream: K-A skips the class ballots (tf_device.h)
+    st->claim_par = -1;
+  };
+  if (tex) { int rc = fused_arm(v); if (rc) return rc; }  // (before the first launch appends to the shard lists)
+  // how many leading frames already went through their selection stages in the previous call?
+  int primed = 0;
+  for (int k = 0; k < v->n_primed && k < n_all; ++k) {
+    const tf_volume::Primed& p = v->primed[k];
+    if (p.depth != d_depth[k] || memcmp(p.pose, poses12 + 12 * k, 48) != 0) break;
+    primed = k + 1;
+  }
+  if (primed < v->n_primed) {  // the stream changed course: discard the selections made ahead
+    for (int k = 0; k < v->n_primed; ++k) {
+      VolumeDev d = v->dev;
+      d.sel = v->selbuf[(v->cur_sel + 1 + k) % NS];
+      launch_reset_ctl(d, false, v->stream);
+    }
+    primed = 0;
+    v->xchg_pub_enq = 0;
+  }
+  v->n_primed = 0;
+  // a primed frame 0 has its list (K-B and K-C ran), a primed frame 1 its bounding box (K-B ran)
+  for (int64_t i = (primed == 2 ? 0 : (primed == 1 ? -1 : -2)); i < n; ++i) {
+    FrameStage cur, nxt, nx2;
+    const bool hc = i >= 0;
+    bool hn = (i + 1 >= 0) && (i + 1 < n_all), h2 = (i + 2 < n_all);
+    if (i + 2 < primed) h2 = false;               // K-B of that frame ran in the previous call
+    if (primed >= 1 && i + 1 == 0) hn = false;    // K-C of frame 0 ran in the previous call
+    if (hc) stage(i, &cur);
+    // K-A builds the frame's dirty set itself when the frame's own chunks are all there is to mesh (marks of earlier,
+    // untextured frames still waiting -> the general dirty list, texture_stage)
+    // Both shortcuts pay for room-sized frames (a K-A wave has one or two chunks) and cost on hall-sized ones, where a
+    // wave walks ten chunks and the claim's dependent hops add up behind each of them (hall: k_frame 250 -> 296 us for
+    // 26 us of k_dirty_frame, profiles/r3): decided by the length of an earlier frame's dirty list, which the mesher's
+    // filter leaves in host-visible memory (no synchronisation; any value gives correct results).
+    const uint32_t dirty_hint = v->atlas.h_dirty_len ? *v->atlas.h_dirty_len.as<volatile uint32_t>() : 0u;
+    static const uint32_t small_max = getenv("TF_SMALL_FRAME") ? (uint32_t)atoi(getenv("TF_SMALL_FRAME")) : 20000u;
+    const bool small_frame = dirty_hint <= small_max;
+    if (hc) cur.small_frame = small_frame;
+    const bool claimed = hc && tex && small_frame && v->clear_floor >= cur.epoch;
+    if (claimed) cur.claim_par = v->atlas.fused_par;
+    if (hn) stage(i + 1, &nxt);
+    if (h2) stage(i + 2, &nx2);
+    if (!hc && !hn && !h2) continue;
+    // the patch stage of the previous textured frame rides on this launch when it carries a colour voxel update
+    // (the fused kernel has no depth-only instance with that role); otherwise it goes out on its own first
+    AtlasState::PendPatch& pp = v->atlas.pend_patch;
+    const bool carry = pp.on && hc && cur.img.rgba != nullptr;
+    if (pp.on && hc && !carry) { int rc = patch_flush(v); if (rc) return rc; }
+    if (hc) prof_begin(v, TF_PROF_INTEGRATE);
+    if (carry) {  // (the launch writes atlas texels: ordered against tf_atlas_snapshot_rows)
+      AtlasWriteScope aw(v, pp.st.kf.kf_id);
+      launch_frame(v->dev, &cur, hn ? &nxt : nullptr, h2 ? &nx2 : nullptr, &pp.st, v->cam, v->ig, v->res, v->stream, v->h_progress.as<uint32_t>(),
+                   &v->progress_seq);
+    } else {
+      launch_frame(v->dev, hc ? &cur : nullptr, hn ? &nxt : nullptr, h2 ? &nx2 : nullptr, nullptr, v->cam, v->ig, v->res, v->stream,
+                   v->h_progress.as<uint32_t>(), &v->progress_seq);
+    }
+    if (hc) prof_end(v);
+    if (carry) { int rc = patch_launched(v); if (rc) return rc; }
+    if (hc && tex) {
+      // (the next frame's selection role rode on this launch: its band counts can be published behind this frame's exchange)
+      int rc = texture_stage(v, cur.sel, cur.img, cur.epoch, tex->pose_inv16 + 16 * i, tex->first_frame_id + (int32_t)i, claimed,
+                             hn ? nxt.sel.ctl : nullptr, false, /*sized_xchg=*/true);
+      if (rc) return rc;
+    }
+  }
+  for (int64_t k = 0; k < n_ahead; ++k) {
+    tf_volume::Primed& p = v->primed[k];
+    p.depth = d_depth[n + k];
+    memcpy(p.pose, poses12 + 12 * (n + k), 48);
+  }
+  v->n_primed = (int)n_ahead;
+  v->epoch += (uint32_t)n;
+  v->cur_sel = (int)((v->cur_sel + n) % NS);
+  v->dev.sel = v->selbuf[v->cur_sel];
+  v->host_list_n = -1;
+  TF_HIP(hipGetLastError());
+  return TF_OK;
+}
+
+int bind_frame(tf_volume* v, const float* d_depth, const uint8_t* d_rgba) {  // tf_frame_bind_device without the entry checks
+  v->frame.depth = d_depth;
+  v->frame.rgba = reinterpret_cast<const uchar4*>(d_rgba);
+  v->frame.quality = nullptr;
+  v->frame_bound = true;
+  return TF_OK;
+}
+
 }  // namespace tf
 
 using namespace tf;
@@ -379,7 +684,7 @@ int tf_volume_create_sized(const int32_t chunk_dim[3], float resolution, int use
     return TF_ERR_NO_DEVICE;
   }
   tf_volume* v = new tf_volume();
-  v->host_defer = tf::host_defer_default();
+  v->hf.host_defer = host_defer_default();
   memset(&v->cfg, 0, sizeof(v->cfg));
   if (cfg) memcpy(&v->cfg, cfg, std::min(cfg_bytes, sizeof(v->cfg)));  // (fields the caller's header lacks: defaults)
   if (v->cfg.max_chunks <= 0) v->cfg.max_chunks = 1ll << 20;
@@ -513,18 +818,7 @@ int tf_volume_destroy(tf_volume* v) {
   if (v->read_ev) hipEventDestroy(v->read_ev);
   if (v->ev_fork) hipEventDestroy(v->ev_fork);
   if (v->ev_join) hipEventDestroy(v->ev_join);
-  for (const tf_volume::HostRange& r : v->host_ranges) (void)host_range_release(r.locked);
-  for (int k = 0; k < tf_volume::kHostRing; ++k)
-    if (v->hslot[k].copied) hipEventDestroy(v->hslot[k].copied);
-  if (v->host_trace[5] > 0 && getenv("TF_HOST_TRACE") && atoi(getenv("TF_HOST_TRACE")))
-    fprintf(stderr, "tf host frames: %.0f calls; per call us: wait kernels %.1f, wait upload %.1f, staging copy %.1f, "
-                    "upload enqueue %.1f, launches %.1f; copies a launch waited for in the stream: %ld\n", v->host_trace[5],
-            v->host_trace[0] / v->host_trace[5], v->host_trace[1] / v->host_trace[5], v->host_trace[2] / v->host_trace[5],
-            v->host_trace[3] / v->host_trace[5], v->host_trace[4] / v->host_trace[5], v->host_waits);
-  delete v->copy_pool;
-  if (v->copy_stream) hipStreamDestroy(v->copy_stream);
-  if (v->copy_stream2) hipStreamDestroy(v->copy_stream2);
-  if (v->copy_join) hipEventDestroy(v->copy_join);
+  v->hf.release();
   if (v->own_stream && v->stream) hipStreamDestroy(v->stream);
   delete v;  // every device and pinned allocation of the handle is a member that frees itself (tf_mem.h)
   return TF_OK;
@@ -850,339 +1144,6 @@ int tf_finalize(tf_volume* v, const int32_t* ids, const uint8_t* needs_update, c
   return TF_OK;
 }
 
-// Chisel::UpdateMeshes -> CompressMeshes -> GeneratePatches(label = this frame) -> UpdateAtlas over the dirty
-// chunks of ONE integrated frame (GCFusion/MobileFusion.cpp:327-382 without the host-side view selection): `sel`
-// holds the frame's visible list with its needsUpdate flags, `frame_epoch` the finalize epoch of that frame.
-// The patch stage (adjacency exchange, slot hand-out, projection, blit) reads meshes and images only; it is left
-// PENDING here and rides on the next frame's launch next to that frame's voxel update (AtlasState::pend_patch).
-}  // extern "C" (C++ linkage for the helper below)
-static int patch_launched(tf_volume* v);
-int tf::fused_arm(tf_volume* v) {
-  AtlasState& a = v->atlas;
-  if (a.fused_armed) return TF_OK;
-  // first textured frame after a reset / a call-by-call atlas call: empty work lists
-  AtlasCtl::Set z[2];
-  memset(z, 0, sizeof(z));
-  TF_HIP(hipMemcpyAsync(&v->dev.actl->set[0], z, sizeof(z), hipMemcpyHostToDevice, v->stream));
-  TF_HIP(hipMemsetAsync(v->dev.patch_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
-  TF_HIP(hipMemsetAsync(v->dev.wl_cnt, 0, sizeof(uint32_t) * 2 * kMeshShards * 16, v->stream));
-  TF_HIP(hipStreamSynchronize(v->stream));
-  a.fused_par = 0;
-  a.fused_armed = true;
-  return TF_OK;
-}
-
-// Neighbour table (VolumeDev::nbr): every filter launch carries a seq above that of every launch ahead of it on the
-// stream, so that a row it checks outlives exactly the key insertions that come later (VolCtl::create_seq).  After 2^32
-// launches the table starts over.
-uint32_t tf::nbr_next_seq(tf_volume* v) {
-  if (v->dev.seq >= 0xFFFFFFF0u) {
-    (void)hipMemsetAsync(v->dev.nbr, 0, (size_t)v->dev.max_chunks * kNbrWords * 4, v->stream);
-    (void)hipMemsetAsync(&v->dev.vctl->create_seq, 0, 4, v->stream);
-    v->dev.seq = 1;
-  }
-  return ++v->dev.seq;
-}
-
-int tf::boundary_pack_block_on(tf_volume* v, void* d_block, int64_t cap_records, hipStream_t s) {
-  uint8_t* blk = reinterpret_cast<uint8_t*>(d_block);
-  TF_HIP(hipMemsetAsync(&v->dev.vctl->n_tmp, 0, 4, s));
-  launch_boundary_pack(v->dev, blk + 16, (uint32_t)cap_records, s);
-  v->dev.xl_par ^= 1u;  // (the voxel kernels list what they touch from now on into the other list)
-  launch_boundary_headers(v->dev, reinterpret_cast<uint32_t*>(blk), (uint32_t)cap_records, nullptr, 0, s);  // the count travels in-band
-  TF_HIP(hipGetLastError());
-  return TF_OK;
-}
-int tf::boundary_pack_bands2_on(tf_volume* v, void* d_block_down, int64_t cap_down, void* d_block_up, int64_t cap_up, hipStream_t s) {
-  // ONE launch: the counters live in VolCtl::xchg_cnt, the last workgroup writes the in-band counts and re-arms them
-  // (round 4: two memsets + the pack + a header launch -- the exchange of a frame was seven stream operations at their
-  // launch floor, 49 us with nothing on the wire; profiles/r5/README.md)
-  launch_boundary_pack_bands(v->dev, reinterpret_cast<uint8_t*>(d_block_down), reinterpret_cast<uint8_t*>(d_block_up),
-                             (uint32_t)cap_down, (uint32_t)cap_up, s);
-  v->dev.xl_par ^= 1u;  // (the voxel kernels list what they touch from now on into the other list)
-  TF_HIP(hipGetLastError());
-  return TF_OK;
-}
-
-// claimed: the dirty set of this frame is already in the lists of the current parity -- K-A built it (FrameStage::claim_par
-// = the parity used here), or the caller ran launch_dirty_frame over each of its lists (the keyframe unit)
-int tf::texture_stage(tf_volume* v, const SelBuf& sel, const FrameImages& img, uint32_t frame_epoch,
-                      const float* pose_inv16, int32_t frame_id, bool claimed, const FrameCtl* next_ctl, bool ride_filter,
-                      bool sized_xchg, int phase, const KfStoreArgs* store) {
-  AtlasState& a = v->atlas;
-  if (phase == 2) {
-    // second half of a stage whose first half (dirty set + interior meshes) ran before the caller's own exchange
-    if (!a.phase1_on || a.phase1_epoch != frame_epoch) { set_error("tf_texture_frame_device_phase: phase 2 without phase 1 of the same frame"); return TF_ERR_INVALID; }
-    a.phase1_on = false;
-    const int par = a.fused_par;
-    a.fused_par ^= 1;
-    VolumeDev d = v->dev;
-    d.sel = sel;
-    d.work_ids = v->dev.work_ids + (size_t)par * d.max_chunks;
-    d.work_slot = v->dev.work_slot + (size_t)par * d.max_chunks;
-    prof_begin(v, TF_PROF_MESH);
-    d.seq = nbr_next_seq(v);
-    launch_mesh(d, v->mesh_par, d.work_ids, &d.actl->set[par].n_work, d.max_chunks, ++v->mesh_epoch, v->res, true, par ^ 1, 0u, nullptr, par,
-                v->stream, nullptr, &v->cam, /*cls=*/2);
-    v->mesh_par ^= 1;
-    prof_end(v);
-    return texture_stage_finish(v, img, frame_epoch, pose_inv16, frame_id, par);
-  }
-  if (a.phase1_on) { set_error("a texture stage is half done: call tf_texture_frame_device_phase(.., 2) first"); return TF_ERR_INVALID; }
-  // A patch stage still pending here (the previous textured frame's) must read its meshes before this frame's mesher
-  // rewrites them: it goes out on its own first -- or (ride_filter: the keyframe unit, which has no k_frame launch for it)
-  // rides on this frame's FILTER launch (launch_mesh below).  In the per-frame stream the stage rides on k_frame instead:
-  // next to the filter the two latency chains cost more than the stage costs K-A (profiles/r4/README.md, runs c2 / s1;
-  // variants/r4_experiments.patch has the knob).
-  const bool ride = a.pend_patch.on && a.fused_armed && ride_filter;
-  int rc = TF_OK;
-  if (!ride) { rc = patch_flush(v); if (rc) return rc; }
-  rc = fused_arm(v);
-  if (rc) return rc;
-  const int par = a.fused_par;
-  if (phase != 1) a.fused_par ^= 1;  // (phase 1: the caller's unpack still appends to this parity's list)
-  VolumeDev d = v->dev;
-  d.sel = sel;
-  d.work_ids = v->dev.work_ids + (size_t)par * d.max_chunks;
-  d.work_slot = v->dev.work_slot + (size_t)par * d.max_chunks;
-  prof_begin(v, TF_PROF_DIRTY);
-  // meshesToUpdate = everything marked since CompressMeshes last cleared it (Chisel.h:192-208, Chisel.cpp:146).  In a
-  // textured stream that is this frame's chunks (stamps <= frame_epoch are cleared); after frames integrated without
-  // the textured unit the older marks are still there and the general dirty list takes over for this frame.
-  if (claimed) { /* nothing to launch: the shard lists of `par` hold the set */ }
-  else if (v->clear_floor < frame_epoch) launch_dirty_backlog(d, par, v->clear_floor, v->stream);
-  else launch_dirty_frame(d, par, frame_epoch + 1u, v->stream);
-  prof_end(v);
-  // (the filter's form follows the dirty-list length of an earlier frame: the kernel leaves it in host-visible memory,
-  // read here without any synchronisation -- whatever value is there is good enough)
-  const uint32_t len_guess = a.h_dirty_len ? *a.h_dirty_len.as<volatile uint32_t>() : 0u;
-  const PatchStage prev = a.pend_patch.st;  // (copied: the pending record is overwritten below)
-  // one filter + mesher pass over the frame's dirty set (cls: every chunk / interior chunks only / boundary chunks only);
-  // the shard lists of this parity are walked in any case: empty when K-A did not claim -- the previous frame's mesher
-  // re-armed them
-  // (new_seq = false: the pass runs NEXT TO the unpack launch of an overlapped exchange, which carries the same seq -- a
-  // key that launch inserts voids what this pass checks of the neighbour table)
-  auto mesh_pass = [&](int cls, const uint32_t* flat_count, bool with_hint, bool with_ride, bool new_seq = true) -> bool {
-    prof_begin(v, TF_PROF_MESH);
-    d.seq = new_seq ? nbr_next_seq(v) : v->dev.seq;
-    std::unique_ptr<AtlasWriteScope> aw;  // (a patch stage riding on the filter launch writes atlas texels)
-    if (with_ride) aw.reset(new AtlasWriteScope(v, prev.kf.kf_id));
-    const bool rode = launch_mesh(d, v->mesh_par, d.work_ids, flat_count, d.max_chunks, ++v->mesh_epoch, v->res, true, par ^ 1,
-                                  len_guess, with_hint ? a.h_dirty_len.as<uint32_t>() : nullptr, par, v->stream, with_ride ? &prev : nullptr,
-                                  &v->cam, cls, store);
-    aw.reset();
-    store = nullptr;  // (once)
-    v->mesh_par ^= 1;
-    prof_end(v);
-    return rode;
-  };
-  bool rode = false;
-  if (phase == 1) {
-    // a caller with its own transport: the interior meshes now, the boundary ones behind its unpack (phase 2).  The flat
-    // list of this parity holds the frame's own entries (stream order: the unpack has not run yet)
-    rode = mesh_pass(1, &d.actl->set[par].n_work, true, false);
-    a.phase1_on = true;
-    a.phase1_epoch = frame_epoch;
-    return TF_OK;
-  }
-  if (v->comm_cap > 0) {  // multi-GPU: ghost bands of this frame's updates, before the mesher reads them
-    // (sized by this frame's selection when the fused stream ran it -- sel.ctl then holds the band counts, tagged with the
-    // frame's epoch + 1; lists of the call-by-call flow and the keyframe unit carry no counts: fixed-capacity blocks)
-    const FrameCtl* xc = sized_xchg ? sel.ctl : nullptr;
-    const FrameCtl* xn = sized_xchg ? next_ctl : nullptr;
-    // The exchange leaves the critical path: pack -> send / receive -> unpack run on a second stream while the main
-    // stream filters and meshes the INTERIOR chunks of the dirty set -- those whose 27-chunk neighbourhood is owned, so that
-    // nothing they read can arrive from another rank -- and only the boundary chunks (and what the arriving ghosts add to
-    // the dirty set) wait for it.  Needs the dirty set in the shard lists K-A filled (claimed: the flat list, which the
-    // unpack launch appends to, is then ignored by the interior pass) and no patch stage riding on the filter launch.
-    // (sized_xchg = the stage comes from the fused stream: `claimed` then means K-A's shard lists; the keyframe unit also
-    // passes claimed, with its dirty set in the FLAT list)
-    const bool overlap = claimed && sized_xchg && !ride && v->xchg_overlap;
-    if (overlap) {
-      if (!v->xstream) {
-        TF_HIP(hipStreamCreateWithFlags(&v->xstream, hipStreamNonBlocking));
-        TF_HIP(hipEventCreateWithFlags(&v->ev_fork, hipEventDisableTiming));
-        TF_HIP(hipEventCreateWithFlags(&v->ev_join, hipEventDisableTiming));
-      }
-      TF_HIP(hipEventRecord(v->ev_fork, v->stream));          // behind the voxel update of this frame
-      (void)nbr_next_seq(v);   // the unpack launch and the interior pass next to it share this seq
-      // the interior pass goes onto the main stream FIRST: the host then spends its time on the exchange's enqueue (band
-      // counts, pack, transport, unpack: ~15 us) while the device already filters and meshes (a kernel trace of the other
-      // order showed the main stream idle for 12 us behind every voxel update)
-      rode = mesh_pass(1, &d.vctl->zero_word, true, false, /*new_seq=*/false);
-      TF_HIP(hipStreamWaitEvent(v->xstream, v->ev_fork, 0));
-      rc = comm_exchange(v, v->comm_cap, par, frame_epoch + 1u, xc, frame_epoch + 1u, xn, v->xstream);
-      if (rc) return rc;
-      TF_HIP(hipEventRecord(v->ev_join, v->xstream));
-      prof_begin(v, TF_PROF_XCHG_WAIT);                        // what of the exchange is NOT hidden behind the interior pass
-      TF_HIP(hipStreamWaitEvent(v->stream, v->ev_join, 0));
-      prof_end(v);
-      rode = mesh_pass(2, &d.actl->set[par].n_work, false, false);
-      v->xchg_overlapped += 1;
-    } else {
-      rc = comm_exchange(v, v->comm_cap, par, frame_epoch + 1u, xc, frame_epoch + 1u, xn);
-      if (rc) return rc;
-      rode = mesh_pass(0, &d.actl->set[par].n_work, true, ride);
-    }
-  } else {
-    rode = mesh_pass(0, &d.actl->set[par].n_work, true, ride);
-  }
-  if (ride) {
-    if (!rode) { set_error("internal: the pending patch stage found no filter launch"); return TF_ERR_INVALID; }
-    rc = patch_launched(v);
-    if (rc) return rc;
-  }
-  return texture_stage_finish(v, img, frame_epoch, pose_inv16, frame_id, par);
-}
-// the tail of a texture stage: this frame's patch stage becomes the pending one
-int tf::texture_stage_finish(tf_volume* v, const FrameImages& img, uint32_t frame_epoch, const float* pose_inv16, int32_t frame_id,
-                             int par) {
-  AtlasState& a = v->atlas;
-  // (CompressMeshes' neighbour exchange, the list of chunks that own a mesh and the slot candidates are produced
-  // by the mesher and consumed by the patch kernel: no kernel of their own in the fused flow)
-  KfDev kf;
-  memset(&kf, 0, sizeof(kf));
-  kf.rgb = reinterpret_cast<const uint8_t*>(img.rgba);
-  kf.depth = img.depth;
-  kf.stride = 4;
-  kf.kf_id = frame_id;
-  static const int pdbg = getenv("TF_PATCH_DBG") ? atoi(getenv("TF_PATCH_DBG")) : 0;  // triage switch
-  kf.pad[0] = pdbg;
-  memcpy(kf.T, pose_inv16, 64);
-  a.pend_patch.on = true;
-  a.pend_patch.st.par = par;
-  a.pend_patch.st.kf = kf;
-  a.pend_patch.host_slot = -1;
-  v->clear_floor = frame_epoch + 1u;  // CompressMeshes cleared meshesToUpdate
-  return TF_OK;
-}
-// the pending patch stage has been put on the stream (as a role of a frame / filter launch or on its own)
-static int patch_launched(tf_volume* v) {
-  AtlasState& a = v->atlas;
-  a.pend_patch.on = false;
-  if (a.pend_patch.host_slot >= 0) {  // its frame's staging slot is free once this launch is through = the next one has started
-    v->hslot[a.pend_patch.host_slot].free_when = v->progress_seq + 1u;
-    a.pend_patch.host_slot = -1;
-  }
-  return TF_OK;
-}
-namespace tf {
-int patch_flush(tf_volume* v) {  // the pending patch stage as a launch of its own
-  AtlasState& a = v->atlas;
-  if (!a.pend_patch.on) return TF_OK;
-  {
-    AtlasWriteScope aw(v, a.pend_patch.st.kf.kf_id);
-    launch_patch_fused(v, v->dev, a.pend_patch.st.par, a.pend_patch.st.kf, v->stream);
-  }
-  TF_HIP(hipGetLastError());
-  return patch_launched(v);
-}
-}  // namespace tf
-extern "C" {
-
-// Software-pipelined enqueue of n frames on the handle's stream: launch i carries K-A of frame i,
-// K-C of frame i+1 and K-B of frame i+2 as independent block ranges of one kernel (launch_frame),
-// so the only synchronisation is the kernel boundary.  The arrays may hold n_ahead (<= 2) frames more
-// than the n that are integrated: their selection stages run in this call's last launches and stay
-// valid ("primed") for the next call, which then starts with K-A at once -- a stream fed call by call
-// costs one launch per frame, not n + 2 per call.  tex != nullptr: after K-A of frame i its dirty chunks
-// are meshed and textured from the frame itself (the per-frame unit of BASELINE configs[2]).
-struct TexturedArgs {
-  const float* pose_inv16;  // per frame: f32(SE3d.inverse().matrix()) of the frame's pose
-  int32_t first_frame_id;
-};
-static int enqueue_frames(tf_volume* v, int64_t n, int64_t n_ahead, const float* const* d_depth,
-                          const uint8_t* const* d_rgba, const float* poses12, const TexturedArgs* tex) {
-  const int NS = tf_volume::kSelSets;
-  const int64_t n_all = n + n_ahead;
-  auto stage = [&](int64_t f, FrameStage* st) {
-    st->sel = v->selbuf[(v->cur_sel + 1 + f) % NS];
-    st->img.depth = d_depth[f];
-    st->img.rgba = (d_rgba && d_rgba[f]) ? reinterpret_cast<const uchar4*>(d_rgba[f]) : nullptr;
-    st->img.quality = nullptr;
-    memcpy(st->pose.p, poses12 + 12 * f, sizeof(st->pose.p));
-    st->epoch = v->epoch + (uint32_t)f;
-    st->coarse_summ = tex == nullptr;  // a TSDF-only stream: K-A skips the class ballots (tf_device.h)
-    st->claim_par = -1;
-  };
-  if (tex) { int rc = fused_arm(v); if (rc) return rc; }  // (before the first launch appends to the shard lists)
-  // how many leading frames already went through their selection stages in the previous call?
-  int primed = 0;
-  for (int k = 0; k < v->n_primed && k < n_all; ++k) {
-    const tf_volume::Primed& p = v->primed[k];
-    if (p.depth != d_depth[k] || memcmp(p.pose, poses12 + 12 * k, 48) != 0) break;
-    primed = k + 1;
-  }
-  if (primed < v->n_primed) {  // the stream changed course: discard the selections made ahead
-    for (int k = 0; k < v->n_primed; ++k) {
-      VolumeDev d = v->dev;
-      d.sel = v->selbuf[(v->cur_sel + 1 + k) % NS];
-      launch_reset_ctl(d, false, v->stream);
-    }
-    primed = 0;
-    v->xchg_pub_enq = 0;
-  }
-  v->n_primed = 0;
-  // a primed frame 0 has its list (K-B and K-C ran), a primed frame 1 its bounding box (K-B ran)
-  for (int64_t i = (primed == 2 ? 0 : (primed == 1 ? -1 : -2)); i < n; ++i) {
-    FrameStage cur, nxt, nx2;
-    const bool hc = i >= 0;
-    bool hn = (i + 1 >= 0) && (i + 1 < n_all), h2 = (i + 2 < n_all);
-    if (i + 2 < primed) h2 = false;               // K-B of that frame ran in the previous call
-    if (primed >= 1 && i + 1 == 0) hn = false;    // K-C of frame 0 ran in the previous call
-    if (hc) stage(i, &cur);
-    // K-A builds the frame's dirty set itself when the frame's own chunks are all there is to mesh (marks of earlier,
-    // untextured frames still waiting -> the general dirty list, texture_stage)
-    // Both shortcuts pay for room-sized frames (a K-A wave has one or two chunks) and cost on hall-sized ones, where a
-    // wave walks ten chunks and the claim's dependent hops add up behind each of them (hall: k_frame 250 -> 296 us for
-    // 26 us of k_dirty_frame, profiles/r3): decided by the length of an earlier frame's dirty list, which the mesher's
-    // filter leaves in host-visible memory (no synchronisation; any value gives correct results).
-    const uint32_t dirty_hint = v->atlas.h_dirty_len ? *v->atlas.h_dirty_len.as<volatile uint32_t>() : 0u;
-    static const uint32_t small_max = getenv("TF_SMALL_FRAME") ? (uint32_t)atoi(getenv("TF_SMALL_FRAME")) : 20000u;
-    const bool small_frame = dirty_hint <= small_max;
-    if (hc) cur.small_frame = small_frame;
-    const bool claimed = hc && tex && small_frame && v->clear_floor >= cur.epoch;
-    if (claimed) cur.claim_par = v->atlas.fused_par;
-    if (hn) stage(i + 1, &nxt);
-    if (h2) stage(i + 2, &nx2);
-    if (!hc && !hn && !h2) continue;
-    // the patch stage of the previous textured frame rides on this launch when it carries a colour voxel update
-    // (the fused kernel has no depth-only instance with that role); otherwise it goes out on its own first
-    AtlasState::PendPatch& pp = v->atlas.pend_patch;
-    const bool carry = pp.on && hc && cur.img.rgba != nullptr;
-    if (pp.on && hc && !carry) { int rc = patch_flush(v); if (rc) return rc; }
-    if (hc) prof_begin(v, TF_PROF_INTEGRATE);
-    if (carry) {  // (the launch writes atlas texels: ordered against tf_atlas_snapshot_rows)
-      AtlasWriteScope aw(v, pp.st.kf.kf_id);
-      launch_frame(v->dev, &cur, hn ? &nxt : nullptr, h2 ? &nx2 : nullptr, &pp.st, v->cam, v->ig, v->res, v->stream, v->h_progress.as<uint32_t>(),
-                   &v->progress_seq);
-    } else {
-      launch_frame(v->dev, hc ? &cur : nullptr, hn ? &nxt : nullptr, h2 ? &nx2 : nullptr, nullptr, v->cam, v->ig, v->res, v->stream,
-                   v->h_progress.as<uint32_t>(), &v->progress_seq);
-    }
-    if (hc) prof_end(v);
-    if (carry) { int rc = patch_launched(v); if (rc) return rc; }
-    if (hc && tex) {
-      // (the next frame's selection role rode on this launch: its band counts can be published behind this frame's exchange)
-      int rc = texture_stage(v, cur.sel, cur.img, cur.epoch, tex->pose_inv16 + 16 * i, tex->first_frame_id + (int32_t)i, claimed,
-                             hn ? nxt.sel.ctl : nullptr, false, /*sized_xchg=*/true);
-      if (rc) return rc;
-    }
-  }
-  for (int64_t k = 0; k < n_ahead; ++k) {
-    tf_volume::Primed& p = v->primed[k];
-    p.depth = d_depth[n + k];
-    memcpy(p.pose, poses12 + 12 * (n + k), 48);
-  }
-  v->n_primed = (int)n_ahead;
-  v->epoch += (uint32_t)n;
-  v->cur_sel = (int)((v->cur_sel + n) % NS);
-  v->dev.sel = v->selbuf[v->cur_sel];
-  v->host_list_n = -1;
-  TF_HIP(hipGetLastError());
-  return TF_OK;
-}
-
 int tf_integrate_frame(tf_volume* v, const float pose[12], int use_color) {
   if (!v || !pose) { set_error("null argument"); return TF_ERR_INVALID; }
   TF_DEV(v);
@@ -1190,66 +1151,6 @@ int tf_integrate_frame(tf_volume* v, const float pose[12], int use_color) {
   const float* dd[1] = {v->frame.depth};
   const uint8_t* dc[1] = {use_color ? reinterpret_cast<const uint8_t*>(v->frame.rgba) : nullptr};
   return enqueue_frames(v, 1, 0, dd, dc, pose, nullptr);
-}
-
-static int bind_frame(tf_volume* v, const float* d_depth, const uint8_t* d_rgba) {  // tf_frame_bind_device without the entry checks
-  v->frame.depth = d_depth;
-  v->frame.rgba = reinterpret_cast<const uchar4*>(d_rgba);
-  v->frame.quality = nullptr;
-  v->frame_bound = true;
-  return TF_OK;
-}
-// a frame of the host ring has been enqueued: its staging slot is free when the last launch that reads its device
-// images is through -- the frame's own launch, or the one that carries its pending patch stage
-static int host_slot_done(tf_volume* v, int slot) {
-  AtlasState::PendPatch& pp = v->atlas.pend_patch;
-  if (pp.on && pp.host_slot < 0) { pp.host_slot = slot; return TF_OK; }
-  v->hslot[slot].free_when = v->progress_seq + 1u;  // through = a later frame launch has started
-  return TF_OK;
-}
-
-// Blocks until the last launch that reads a staging slot's device images is through.  No stream event: the frame
-// launches stamp tf_volume::h_progress when they start.  The launch that follows the slot's last reader is normally on
-// the stream already (the entry point runs three frames behind); if none comes (the caller changed entry points), the
-// stream is drained instead.
-static int host_slot_wait(tf_volume* v, tf_volume::HostSlot& s) {
-  if (!s.free_when) return TF_OK;
-  volatile uint32_t* p = v->h_progress.as<uint32_t>();
-  if ((int32_t)(v->progress_seq - s.free_when) < 0) {  // no launch that would stamp it is on the stream
-    TF_HIP(hipStreamSynchronize(v->stream));
-    s.free_when = 0;
-    return TF_OK;
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t spin = 0;; ++spin) {
-    if ((int32_t)(*p - s.free_when) >= 0) break;
-    static const int poll_sleep = getenv("TF_HOST_POLL_SLEEP_US") ? atoi(getenv("TF_HOST_POLL_SLEEP_US")) : 0;
-    if (poll_sleep > 0) { std::this_thread::sleep_for(std::chrono::microseconds(poll_sleep)); continue; }
-    __builtin_ia32_pause();
-    if ((spin & 1023u) == 1023u) {
-      const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-      if (us > 20000.0) { TF_HIP(hipStreamSynchronize(v->stream)); break; }  // (a stalled device: fail through the API)
-      if (us > 200.0) sched_yield();
-    }
-  }
-  s.free_when = 0;
-  return TF_OK;
-}
-
-// the H2D copy of a staged host frame must be through before a launch reads its device images: nothing to do when the
-// copy event is already complete (the usual case: the entry point runs behind), otherwise the stream waits for it
-static int host_copy_ready(tf_volume* v, tf_volume::Pending* p) {
-  if (p->copied) return TF_OK;
-  hipEvent_t ev = v->hslot[p->slot].copied;
-  const hipError_t q = hipEventQuery(ev);
-  if (q == hipErrorNotReady) {
-    TF_HIP(hipStreamWaitEvent(v->stream, ev, 0));
-    if (v->host_trace[5] >= 0) v->host_waits += 1;
-  } else if (q != hipSuccess) {
-    TF_HIP(q);
-  }
-  p->copied = true;
-  return TF_OK;
 }
 
 static int check_frames(int64_t n_all, const float* const* d_depth, const uint8_t* const* d_rgba) {
@@ -1301,379 +1202,6 @@ int tf_stream_frames_textured_device(tf_volume* v, int64_t n_frames, int64_t n_a
   return bind_frame(v, d_depth[n_frames - 1], d_rgba[n_frames - 1]);
 }
 
-// ring of staging slots of the per-frame host path, (re)sized to the camera
-
-static int host_ring_prepare(tf_volume* v) {
-  const size_t npix = (size_t)v->cam.W * v->cam.H;
-  if (v->hslot_pixels == npix && v->copy_stream) return TF_OK;
-  v->hslot_pixels = 0;  // not ready until every slot below fits
-  TF_HIP(hipStreamSynchronize(v->stream));
-  if (!v->copy_stream) TF_HIP(hipStreamCreateWithFlags(&v->copy_stream, hipStreamNonBlocking));
-  TF_HIP(hipStreamSynchronize(v->copy_stream));
-  int rc;
-  for (int k = 0; k < tf_volume::kHostRing; ++k) {
-    tf_volume::HostSlot& s = v->hslot[k];
-    if ((rc = fit(s.h, npix * 8, v->stream)) || (rc = fit(s.d, npix * 12, v->stream))) return rc;
-    if (!s.copied) TF_HIP(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-    s.free_when = 0;  // (both streams were drained above)
-  }
-  if (!v->h_progress) {
-    if ((rc = v->h_progress.alloc(64))) return rc;
-    *v->h_progress.as<uint32_t>() = v->progress_seq;
-  }
-  v->hslot_pixels = npix;
-  v->hslot_next = 0;
-  return TF_OK;
-}
-
-}  // extern "C"
-bool tf::host_defer_default() {
-  static const bool on = !(getenv("TF_HOST_DEFER") && !atoi(getenv("TF_HOST_DEFER")));
-  return on;
-}
-extern "C" {
-int tf_host_frame_set_deferral(tf_volume* v, int on) {
-  if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
-  TF_DEV(v);  // (frames still in the pipeline go onto the stream under the old setting)
-  v->host_defer = on != 0;
-  return TF_OK;
-}
-
-int tf_host_frame_set_async(tf_volume* v, int on) {
-  if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
-  v->host_async = on != 0;
-  return TF_OK;
-}
-int tf_host_frame_fence(tf_volume* v) {
-  if (!v) { set_error("null handle"); return TF_ERR_INVALID; }
-  TF_DEV_NOFLUSH(v);
-  if (v->last_upload) TF_HIP(hipEventSynchronize(v->last_upload));  // (uploads of one handle complete in order)
-  return TF_OK;
-}
-
-int tf_host_frame_deferral(tf_volume* v, int32_t* frames_behind, int32_t* ring_slots) {
-  // (a null handle answers for a handle as tf_volume_create makes it: TF_HOST_DEFER=0 in the environment turns the deferral
-  // off for every new handle, tf_host_frame_set_deferral for one)
-  const bool defer = v ? v->host_defer : tf::host_defer_default();
-  if (frames_behind) *frames_behind = defer ? tf_volume::kHostDefer : 0;
-  if (ring_slots) *ring_slots = tf_volume::kHostRing;
-  return TF_OK;
-}
-
-}  // extern "C"
-extern "C" {
-int tf_host_register(tf_volume* v, const void* p, int64_t bytes) {
-  if (!v || !p || bytes <= 0) { set_error("null argument"); return TF_ERR_INVALID; }
-  TF_DEV_NOFLUSH(v);
-  const uint8_t* b = static_cast<const uint8_t*>(p);
-  for (const tf_volume::HostRange& r : v->host_ranges)
-    if (b >= r.p && b + bytes <= r.p + r.n) return TF_OK;  // already inside a range of this handle
-  const uint8_t* locked = b;  // base of the page-locked range that covers [b, b + bytes)
-  {
-    std::lock_guard<std::mutex> lk(g_locked_mu);
-    // a range some handle of this process locked already may CONTAIN this one (depth / colour views inside one arena):
-    // hipHostRegister on pages that are locked fails, so the containing range is shared instead
-    auto it = g_locked.upper_bound(b);
-    const bool have = it != g_locked.begin() && (--it, b < it->first + it->second.n);  // the range at or below b reaches b
-    if (have && b + bytes <= it->first + it->second.n) {
-      it->second.refs += 1;
-      locked = it->first;
-    } else {
-      auto up = g_locked.lower_bound(b);  // the first range that starts at or above b
-      if (have || (up != g_locked.end() && up->first < b + bytes)) {
-        set_error("tf_host_register: the buffer overlaps a range that is page-locked already with a different extent "
-                  "(register the whole arena once, or ranges that do not overlap)");
-        return TF_ERR_INVALID;
-      }
-      TF_HIP(hipHostRegister(const_cast<uint8_t*>(b), (size_t)bytes, hipHostRegisterDefault));
-      g_locked[b] = LockedRange{(size_t)bytes, 1};
-    }
-  }
-  v->host_ranges.push_back({b, (size_t)bytes, locked});
-  return TF_OK;
-}
-int tf_host_unregister(tf_volume* v, const void* p) {
-  if (!v || !p) { set_error("null argument"); return TF_ERR_INVALID; }
-  TF_DEV(v);  // (frames still in the entry point's pipeline have been uploaded; their launches go out now)
-  TF_HIP(hipStreamSynchronize(v->copy_stream ? v->copy_stream : v->stream));
-  for (size_t i = 0; i < v->host_ranges.size(); ++i)
-    if (v->host_ranges[i].p == static_cast<const uint8_t*>(p)) {
-      const uint8_t* locked = v->host_ranges[i].locked;
-      v->host_ranges.erase(v->host_ranges.begin() + (long)i);
-      return host_range_release(locked);
-    }
-  set_error("not a registered buffer");
-  return TF_ERR_INVALID;
-}
-
-int tf_host_frame_times(tf_volume* v, double out[7], int reset) {
-  if (!v || !out) { set_error("null argument"); return TF_ERR_INVALID; }
-  out[0] = v->host_trace[5];  // calls that put a frame's launches on the stream
-  for (int k = 0; k < 5; ++k) out[1 + k] = v->host_trace[k];  // us: waiting for the device to free a slot | waiting for the slot's last upload | staging copy | upload enqueue | launches
-  out[6] = (double)v->host_waits;  // launches that had to wait in the stream for an upload
-  if (reset) { for (int k = 0; k < 6; ++k) v->host_trace[k] = 0.0; v->host_waits = 0; }
-  return TF_OK;
-}
-
-int tf_host_frame_buffers(tf_volume* v, float** depth, uint8_t** rgba) {
-  if (!v || !depth || !rgba) { set_error("null argument"); return TF_ERR_INVALID; }
-  TF_DEV_NOFLUSH(v);
-  int rc = host_ring_prepare(v);
-  if (rc) return rc;
-  tf_volume::HostSlot& s = v->hslot[v->hslot_next];
-  TF_HIP(hipEventSynchronize(s.copied));  // the previous upload out of this slot has left the host buffer
-  *depth = s.h.as<float>();
-  *rgba = s.h.as<uint8_t>(v->hslot_pixels * 4);
-  return TF_OK;
-}
-
-}  // extern "C"
-// rgb != nullptr: the colour image comes as Frame::rgb (3 bytes per pixel) with Frame::colorValidFlag (or none: every pixel
-// valid) -- the inputs of the caller's own RGBA staging loops (MobileFusion.cpp:144-163, :232-243), which then run on the
-// device behind the upload, on the copy stream
-static int integrate_frame_host_impl(tf_volume* v, const float* depth, const uint8_t* rgba, const uint8_t* rgb,
-                                     const uint8_t* color_valid, const float pose[12], const float* pose_inv16, int32_t frame_id) {
-  if (!v || !depth || !pose) { set_error("null argument"); return TF_ERR_INVALID; }
-  if (pose_inv16 && !rgba && !rgb) { set_error("the textured unit needs a colour image"); return TF_ERR_INVALID; }
-  TF_DEV_NOFLUSH(v);
-  int rc = host_ring_prepare(v);
-  if (rc) return rc;
-  constexpr bool trace = true;  // per-phase host time (five clock reads per call): tf_host_frame_times; TF_HOST_TRACE=1 prints it at destroy
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto lap = [&](int k, std::chrono::steady_clock::time_point& t) {
-    if (!trace) return;
-    const auto t1 = now();
-    v->host_trace[k] += std::chrono::duration<double, std::micro>(t1 - t).count();
-    t = t1;
-  };
-  auto t = now();
-  // The launch pipeline of the streaming entry points, kept alive across per-frame calls: this call integrates the
-  // frame that arrived FOUR calls ago, and that launch carries the selection stages of the two frames behind it
-  // (K-A(f-4) | K-C(f-3) | K-B(f-2)); frames f-1 and f are only staged and copied.  A copy therefore has a whole
-  // call's time to finish before a launch needs it, so the host finds the copy event complete and no wait goes into
-  // the stream (a cross-stream wait ahead of a launch costs ~7 us of idle device; with three frames of deferral the
-  // newest image a launch reads was uploaded by the call before, and 6-20 % of the launches still waited).  The deferral cannot be
-  // observed: every other entry point flushes first (TF_DEV).
-  // The launches go out FIRST where that costs nothing -- they need nothing of the new frame -- so that an idle device is
-  // at work while this call stages and uploads (it starts ~45 us earlier: 2 % of a 20-frame window).
-  const bool defer = v->host_defer;
-  constexpr int ND = tf_volume::kHostDefer;
-  const float* bound_d = nullptr;
-  const uint8_t* bound_c = nullptr;
-  auto launch_oldest = [&]() -> int {
-    if (!(defer && v->n_pend == ND)) return TF_OK;
-    tf_volume::Pending all[ND];
-    for (int k = 0; k < ND; ++k) all[k] = v->pend[k];
-    tf_volume::Pending &p0 = all[0], &p1 = all[1], &p2 = all[2];  // the launch reads the oldest frame and the two behind it
-    for (tf_volume::Pending* q : {&p0, &p1, &p2}) { rc = host_copy_ready(v, q); if (rc) return rc; }
-    const float* dd[3] = {p0.d, p1.d, p2.d};
-    const uint8_t* dc[3] = {p0.c, p1.c, p2.c};
-    float poses[36];
-    memcpy(poses, p0.pose, 48); memcpy(poses + 12, p1.pose, 48); memcpy(poses + 24, p2.pose, 48);
-    TexturedArgs tex{p0.pinv, p0.fid};
-    v->n_pend = 0;  // (helpers below enqueue_frames may pass through TF_DEV: nothing to flush while this call runs)
-    rc = enqueue_frames(v, 1, 2, dd, dc, poses, p0.tex ? &tex : nullptr);
-    for (int k = 1; k < ND; ++k) v->pend[k - 1] = all[k];
-    v->n_pend = ND - 1;
-    if (rc) return rc;
-    rc = host_slot_done(v, p0.slot);
-    if (rc) return rc;
-    bound_d = p0.d;
-    bound_c = p0.c;
-    lap(4, t);
-    if (trace) v->host_trace[5] += 1.0;
-    return TF_OK;
-  };
-  // ... but only when they would not wait: the launch also reads the images of the two frames behind the oldest one
-  // (selection roles), and the newest of those was uploaded by the PREVIOUS call.  On an idle device (the start of a
-  // stream, a caller that paces its frames) that copy is through and the launches go out at once; in a saturated stream
-  // it is a few microseconds old -- launching now would put a wait for it into the stream (7 us of idle device per
-  // frame, run 46), launching behind the staging copy finds it complete.
-  bool early = false;
-  if (defer && v->n_pend == ND) {
-    const tf_volume::Pending& newest = v->pend[2];  // (the newest frame the launch reads)
-    early = newest.copied || hipEventQuery(v->hslot[newest.slot].copied) == hipSuccess;
-  }
-  if (early) { rc = launch_oldest(); if (rc) return rc; }
-  const size_t npix = v->hslot_pixels;
-  const int slot_index = v->hslot_next;
-  tf_volume::HostSlot& s = v->hslot[slot_index];
-  v->hslot_next = (v->hslot_next + 1) % tf_volume::kHostRing;
-  // the kernels that read this slot's device images and the upload out of its pinned buffer have finished
-  rc = host_slot_wait(v, s);
-  if (rc) return rc;
-  lap(0, t);
-  TF_HIP(hipEventSynchronize(s.copied));
-  lap(1, t);
-  uint8_t* const sd = s.d.as<uint8_t>();
-  float* hd = s.h.as<float>();
-  uint8_t* hc = s.h.as<uint8_t>(npix * 4);
-  // images inside registered caller buffers (tf_host_register) go up straight from there
-  auto registered = [&](const void* q, size_t n) {
-    const uint8_t* b = static_cast<const uint8_t*>(q);
-    for (const tf_volume::HostRange& r : v->host_ranges)
-      if (b >= r.p && b + n <= r.p + r.n) return true;
-    return false;
-  };
-  const bool direct = !v->host_ranges.empty() && registered(depth, npix * 4) && (!rgba || registered(rgba, npix * 4)) &&
-                      (!rgb || (registered(rgb, npix * 3) && (!color_valid || registered(color_valid, npix))));
-  if (!direct) {  // frames composed in tf_host_frame_buffers' slot skip the staging copy
-    void* dst[2];
-    const void* src[2];
-    size_t nb[2];
-    int nr = 0;
-    if (depth != hd) { dst[nr] = hd; src[nr] = depth; nb[nr++] = npix * 4; }
-    void* dst3[3];
-    const void* src3[3];
-    size_t nb3[3];
-    if (rgba && rgba != hc) { dst[nr] = hc; src[nr] = rgba; nb[nr++] = npix * 4; }
-    if (rgb) {  // RGB at hc, the valid flags behind it (composed in place by a caller of tf_host_frame_buffers: no copy)
-      if (nr) { dst3[0] = dst[0]; src3[0] = src[0]; nb3[0] = nb[0]; }
-      if (rgb != hc) { dst3[nr] = hc; src3[nr] = rgb; nb3[nr++] = npix * 3; }
-      if (color_valid && color_valid != hc + npix * 3) { dst3[nr] = hc + npix * 3; src3[nr] = color_valid; nb3[nr++] = npix; }
-    }
-    if (nr) {
-      if (!v->copy_pool) {
-        const char* e = getenv("TF_COPY_THREADS");
-        int helpers = e ? atoi(e) : 7;
-        if (helpers < 0) helpers = 0;
-        if (helpers > 15) helpers = 15;
-        // helpers run where the scheduler puts them (on a shared host pinned helpers gave 1 run in 3 a 10-ms stall --
-        // 100.8 us per frame at best, 150+ at worst, against a steady 102.6 unpinned; profiles/r3, run 36)
-        const int pin = 0;
-        static const int spin_us = getenv("TF_COPY_SPIN_US") ? atoi(getenv("TF_COPY_SPIN_US")) : 200;
-        v->copy_pool = new CopyPool(helpers, pin, spin_us);
-      }
-      if (rgb) v->copy_pool->copy(dst3, src3, nb3, nr);
-      else v->copy_pool->copy(dst, src, nb, nr);
-    }
-  }
-  lap(2, t);
-  // (depth and colour of a STAGED frame go up as one copy on one copy stream: two streams -- two SDMA queues -- helped a
-  // TSDF-only stream in steady state on a quiet host, 62 -> 52-54 us per frame, and doubled the first window behind resident
-  // frames on a shared one; profiles/r4/README.md, run s13)
-  if (direct) {
-    // (depth and colour are two caller arrays = two copies.  The link moves 2.46 MB as ONE copy in 53 us -- 46 GB/s,
-    // allocated page-locked or page-locked in place alike, tools/h2d_probe.py --; as two copies of 1.2 MB it takes 60 us when
-    // they travel side by side on two copy queues and 66 us one behind the other on one queue (profiles/r5/README.md).  A
-    // kernel that fetches the images itself -- 16-byte loads out of the mapped pages -- was no faster than the DMA
-    // transfers and slowed the step kernels it ran next to: 100 -> 125 us per frame, profiles/r4/README.md)
-    if (rgba) {
-      if (!v->copy_stream2) {
-        TF_HIP(hipStreamCreateWithFlags(&v->copy_stream2, hipStreamNonBlocking));
-        TF_HIP(hipEventCreateWithFlags(&v->copy_join, hipEventDisableTiming));
-      }
-      TF_HIP(hipMemcpyAsync(sd + npix * 4, rgba, npix * 4, hipMemcpyHostToDevice, v->copy_stream2));
-      TF_HIP(hipEventRecord(v->copy_join, v->copy_stream2));
-      TF_HIP(hipMemcpyAsync(sd, depth, npix * 4, hipMemcpyHostToDevice, v->copy_stream));
-      TF_HIP(hipStreamWaitEvent(v->copy_stream, v->copy_join, 0));
-    } else {
-      TF_HIP(hipMemcpyAsync(sd, depth, npix * 4, hipMemcpyHostToDevice, v->copy_stream));
-    }
-    if (rgb) {
-      TF_HIP(hipMemcpyAsync(sd + npix * 4, rgb, npix * 3, hipMemcpyHostToDevice, v->copy_stream));
-      if (color_valid) TF_HIP(hipMemcpyAsync(sd + npix * 7, color_valid, npix, hipMemcpyHostToDevice, v->copy_stream));
-      launch_pack_rgba(sd + npix * 4, color_valid ? sd + npix * 7 : nullptr, reinterpret_cast<uchar4*>(sd + npix * 8), (uint32_t)npix,
-                       v->copy_stream);
-      TF_HIP(hipGetLastError());
-    }
-  } else {
-    {
-      const size_t up = rgba ? npix * 8 : (rgb ? (color_valid ? npix * 8 : npix * 7) : npix * 4);
-      TF_HIP(hipMemcpyAsync(sd, s.h.p, up, hipMemcpyHostToDevice, v->copy_stream));
-    }
-    if (rgb) {  // rgba = valid ? (r, g, b, 1) : 0, behind the upload on the copy stream (null flags: every pixel valid)
-      launch_pack_rgba(sd + npix * 4, color_valid ? sd + npix * 7 : nullptr, reinterpret_cast<uchar4*>(sd + npix * 8), (uint32_t)npix,
-                       v->copy_stream);
-      TF_HIP(hipGetLastError());
-    }
-  }
-  TF_HIP(hipEventRecord(s.copied, v->copy_stream));
-  lap(3, t);
-  tf_volume::Pending cur;
-  cur.d = reinterpret_cast<const float*>(sd);
-  cur.c = rgba ? sd + npix * 4 : (rgb ? sd + npix * 8 : nullptr);
-  memcpy(cur.pose, pose, sizeof(cur.pose));
-  cur.tex = pose_inv16 != nullptr;
-  if (pose_inv16) memcpy(cur.pinv, pose_inv16, sizeof(cur.pinv));
-  cur.fid = frame_id;
-  cur.slot = slot_index;
-  cur.copied = false;
-  // the caller's buffers are its own again when the call returns: an upload straight out of them must be through -- unless
-  // the caller took that on itself (tf_host_frame_set_async: it calls tf_host_frame_fence before it touches a buffer again)
-  v->last_upload = s.copied;
-  auto wait_direct = [&]() {
-    if (v->host_async) return;
-    auto tw = now();
-    // (TF_HOST_POLL_SLEEP_US > 0: sleep between polls instead of spinning -- several ranks under one CPU quota)
-    static const int poll_sleep = getenv("TF_HOST_POLL_SLEEP_US") ? atoi(getenv("TF_HOST_POLL_SLEEP_US")) : 0;
-    for (uint32_t spin = 0; hipEventQuery(s.copied) == hipErrorNotReady; ++spin) {
-      if (poll_sleep > 0) std::this_thread::sleep_for(std::chrono::microseconds(poll_sleep));
-      else if ((spin & 63u) == 63u) __builtin_ia32_pause();
-    }
-    lap(1, tw);
-  };
-  if (!defer) {  // integrate at once: two selection-only launches per frame, the stream waits for the copy
-    if (direct) { wait_direct(); cur.copied = !v->host_async; }
-    rc = host_copy_ready(v, &cur);
-    if (rc) return rc;
-    const float* dd[1] = {cur.d};
-    const uint8_t* dc[1] = {cur.c};
-    TexturedArgs tex{cur.pinv, cur.fid};
-    rc = enqueue_frames(v, 1, 0, dd, dc, cur.pose, cur.tex ? &tex : nullptr);
-    if (rc) return rc;
-    rc = host_slot_done(v, slot_index);
-    if (rc) return rc;
-    return bind_frame(v, cur.d, cur.c);
-  }
-  if (!early) { rc = launch_oldest(); if (rc) return rc; }
-  v->pend[v->n_pend++] = cur;
-  if (direct) { wait_direct(); v->pend[v->n_pend - 1].copied = !v->host_async; }
-  if (bound_d) return bind_frame(v, bound_d, bound_c);
-  return TF_OK;
-}
-extern "C" {
-int tf_integrate_frame_host(tf_volume* v, const float* depth, const uint8_t* rgba, const float pose[12],
-                            const float* pose_inv16, int32_t frame_id) {
-  return integrate_frame_host_impl(v, depth, rgba, nullptr, nullptr, pose, pose_inv16, frame_id);
-}
-int tf_integrate_frame_host_rgb(tf_volume* v, const float* depth, const uint8_t* rgb, const uint8_t* color_valid,
-                                const float pose[12], const float* pose_inv16, int32_t frame_id) {
-  if (!rgb) { set_error("null colour image (tf_integrate_frame_host takes depth-only frames)"); return TF_ERR_INVALID; }
-  return integrate_frame_host_impl(v, depth, nullptr, rgb, color_valid, pose, pose_inv16, frame_id);
-}
-
-}  // extern "C" (C++ linkage for the helper below)
-namespace tf {
-// brings the deferred frames of tf_integrate_frame_host onto the stream, oldest first (each launch still carries
-// the selection stages of the frames behind it)
-int flush_deferred(tf_volume* v) {
-  const int n = v->n_pend;
-  if (!n) return TF_OK;
-  constexpr int ND = tf_volume::kHostDefer;
-  tf_volume::Pending p[ND];
-  for (int k = 0; k < n; ++k) p[k] = v->pend[k];
-  v->n_pend = 0;  // (enqueue_frames' helpers may pass through TF_DEV)
-  for (int k = 0; k < n; ++k) {
-    int rc = host_copy_ready(v, &p[k]);
-    if (rc) return rc;
-  }
-  for (int k = 0; k < n; ++k) {
-    const float* dd[ND];
-    const uint8_t* dc[ND];
-    float poses[12 * ND];
-    for (int j = k; j < n; ++j) { dd[j - k] = p[j].d; dc[j - k] = p[j].c; memcpy(poses + 12 * (j - k), p[j].pose, 48); }
-    TexturedArgs tex{p[k].pinv, p[k].fid};
-    const int ahead = n - 1 - k < 2 ? n - 1 - k : 2;
-    int rc = enqueue_frames(v, 1, ahead, dd, dc, poses, p[k].tex ? &tex : nullptr);
-    if (rc) return rc;
-    rc = host_slot_done(v, p[k].slot);
-    if (rc) return rc;
-  }
-  return bind_frame(v, p[n - 1].d, p[n - 1].c);
-}
-}  // namespace tf
-extern "C" {
 
 int tf_texture_frame_device(tf_volume* v, const float pose_inv16[16], int32_t frame_id) {
   if (!v || !pose_inv16) { set_error("null argument"); return TF_ERR_INVALID; }

@@ -10,8 +10,8 @@
 #include <vector>
 
 #include "../../include/tf_fusion.h"
-#include "tf_copy_pool.h"
 #include "tf_device.h"
+#include "tf_host_frames.h"
 #include "tf_mem.h"
 
 namespace tf {
@@ -40,12 +40,12 @@ void set_error(const std::string& msg);
       return TF_ERR_HIP;                                                                    \
     }                                                                                       \
   } while (0)
-// Every entry point but tf_integrate_frame_host first brings the frames that entry point has deferred (its
-// two-frame launch pipeline, see tf_capi.cpp) onto the stream, so that nothing can observe the deferral.
+// Every entry point but tf_integrate_frame_host first brings the frames that entry point has deferred (it runs
+// HostFrames::kHostDefer frames behind its caller, see tf_host_frames.cpp) onto the stream, so that nothing can observe the deferral.
 #define TF_DEV_STREAM(v)                                                                    \
   do {                                                                                      \
     TF_DEV_NOFLUSH(v);                                                                      \
-    if ((v)->n_pend) {                                                                      \
+    if ((v)->hf.n_pend) {                                                                   \
       int _rc = ::tf::flush_deferred(v);                                                    \
       if (_rc) return _rc;                                                                  \
     }                                                                                       \
@@ -69,7 +69,7 @@ void set_error(const std::string& msg);
 #define TF_DEV_READER(v)                                                                    \
   do {                                                                                      \
     const uint64_t _gen = (v)->model_gen;                                                   \
-    const bool _writes = (v)->n_pend || (v)->atlas.pend_patch.on;                           \
+    const bool _writes = (v)->hf.n_pend || (v)->atlas.pend_patch.on;                        \
     TF_DEV(v);                                                                              \
     if (!_writes) (v)->model_gen = _gen;                                                    \
   } while (0)
@@ -246,34 +246,14 @@ struct tf_volume {
   std::vector<tf::DevMem> allocs;  // the fixed allocations of tf_volume_create
   // frame images: the staging targets of tf_frame_upload, one fitted buffer carved as depth | rgba | quality
   tf::DevMem images;
-  // drop-in per-frame host path (tf_integrate_frame_host): ring of pinned staging + device image slots, H2D on
-  // its own stream so that the copy of frame f+1 overlaps the kernels of frame f
-  static constexpr int kHostRing = 8;  // four deferred frames + the one being staged + three whose kernels may still run
-                                       // (a frame's images are read by its patch stage one launch behind its voxel update)
-  struct HostSlot {
-    tf::PinMem h;              // depth f32[npix] | rgba u8[4 npix]
-    tf::DevMem d;              // depth | colour as uploaded (RGBA, or RGB + valid flags) | RGBA packed from an RGB upload
-    hipEvent_t copied = nullptr;
-    uint32_t free_when = 0;    // 0: free; else the progress stamp (h_progress) at which the last launch that reads d is through
-  };
+  // the per-frame host path (tf_integrate_frame_host, tf_host_*): staging ring, registered caller buffers, deferred frames
+  tf::HostFrames hf;
   // Launch progress without stream events: every frame launch writes its sequence number into this pinned word when it
   // STARTS (= every launch ahead of it on the stream is through).  An event record between two launches of a frame cost
   // the host-frames path 6.8 us per frame of idle device time (profiles/r3, run 29).
+  // Both stay here, not in HostFrames: launch_frame stamps them for every stream, host frames or not.
   tf::PinMem h_progress;  // one u32, null until the host ring is first prepared
   uint32_t progress_seq = 0;   // stamp of the last frame launch put on the stream
-  HostSlot hslot[kHostRing];
-  // caller buffers registered with tf_host_register (page-locked in place): host frames that lie inside one are uploaded
-  // straight out of it -- no staging copy -- and the call returns when that upload is through
-  struct HostRange { const uint8_t* p; size_t n; const uint8_t* locked; };  // locked: base of the process-wide page-locked range that covers it
-  std::vector<HostRange> host_ranges;
-  size_t hslot_pixels = 0;  // the camera all eight slots fit and are laid out for; 0: the ring is not ready
-  int hslot_next = 0;
-  hipStream_t copy_stream = nullptr;
-  hipStream_t copy_stream2 = nullptr;  // registered caller buffers: the colour image goes up next to the depth image (a second copy queue)
-  hipEvent_t copy_join = nullptr;
-  long host_waits = 0;  // copies a launch had to wait for in the stream (TF_HOST_TRACE prints it)
-  double host_trace[6] = {0, 0, 0, 0, 0, 0};  // TF_HOST_TRACE=1: microseconds per phase of tf_integrate_frame_host, [5] = calls
-  tf::CopyPool* copy_pool = nullptr;  // helper threads of the staging copy (TF_COPY_THREADS, default 3)
   tf::FrameImages frame{nullptr, nullptr, nullptr};
   bool frame_bound = false;
   // host shadow of the device-resident visible list (int32[3*n]); -1 = device list unknown
@@ -293,25 +273,6 @@ struct tf_volume {
   uint32_t clear_floor = 0;  // stamps <= this were cleared (Chisel::CompressMeshes' chunksToUpdate.clear())
   uint32_t mesh_epoch = 0;   // meshing passes so far (MeshRec::epoch)
   int mesh_par = 0;          // parity of the next mesher launch (VolumeDev::mesh_cnt)
-  // frames tf_integrate_frame_host has staged but not integrated yet (it runs three frames behind: K-A of frame f - 3
-  // shares its launch with the selection stages of f - 2 and f - 1, like the streaming entry points; frame f itself is
-  // only being copied, so that no launch ever has to wait for a copy in the stream)
-  struct Pending {
-    const float* d = nullptr;
-    const uint8_t* c = nullptr;
-    float pose[12];
-    float pinv[16];
-    bool tex = false;
-    int32_t fid = 0;
-    int slot = 0;
-    bool copied = false;  // its H2D copy is known to be complete, or the handle's stream has been told to wait for it
-  };
-  static constexpr int kHostDefer = 4;  // frames tf_integrate_frame_host runs behind its caller (a launch reads the oldest three)
-  Pending pend[kHostDefer];
-  int n_pend = 0;
-  bool host_defer = true;  // tf_integrate_frame_host runs kHostDefer frames behind its caller (tf_host_frame_set_deferral)
-  bool host_async = false;           // tf_host_frame_set_async: a call out of registered buffers returns before its upload is through
-  hipEvent_t last_upload = nullptr;  // the newest frame's upload (tf_host_frame_fence waits for it)
   tf::DevMem group;  // staging of tf_integrate_depth_group_host: six depth images
   tf::Scratch scratch;  // on-demand staging of the entry points (uploads / downloads, device scratch)
   // profiling
@@ -380,12 +341,21 @@ int texture_stage_finish(tf_volume* v, const FrameImages& img, uint32_t frame_ep
 int xchg_band_counts(tf_volume* v, const FrameCtl* ctl, uint32_t tag, uint32_t cnt[4], hipStream_t s = nullptr);
 int xchg_words(tf_volume* v);  // tf_volume::h_xchg is there (allocated and zeroed on first use)
 uint32_t nbr_next_seq(tf_volume* v);  // neighbour table: the seq of the filter launch about to go out (tf_capi.cpp)
-int flush_deferred(tf_volume* v);
 // the dirty set (Chisel::meshesToUpdate) as a device list in scratch.d: [0,16) count word, ids from byte 16 (tf_mesh.hip)
 int dirty_list_enqueue(tf_volume* v);
 void launch_dirty_frame_store(const VolumeDev& v, int par, uint32_t stamp, const KfStoreArgs& a, hipStream_t s);  // tf_mesh.hip
 int patch_flush(tf_volume* v);
-bool host_defer_default();  // !(TF_HOST_DEFER=0 in the environment)
+// the pending patch stage has been put on the stream (as a role of a frame / filter launch or on its own)
+int patch_launched(tf_volume* v);
+// Software-pipelined enqueue of n frames (+ n_ahead selection-only ones) on the handle's stream, and the textured flow's
+// per-frame arguments (tf_capi.cpp); bind_frame: tf_frame_bind_device without the entry checks
+struct TexturedArgs {
+  const float* pose_inv16;  // per frame: f32(SE3d.inverse().matrix()) of the frame's pose
+  int32_t first_frame_id;
+};
+int enqueue_frames(tf_volume* v, int64_t n, int64_t n_ahead, const float* const* d_depth, const uint8_t* const* d_rgba,
+                   const float* poses12, const TexturedArgs* tex);
+int bind_frame(tf_volume* v, const float* d_depth, const uint8_t* d_rgba);
 int fused_arm(tf_volume* v);  // the fused flow's counter sets in their start state (no-op once armed)
 void prof_begin(tf_volume* v, int kind, hipStream_t s = nullptr);
 void prof_end(tf_volume* v, hipStream_t s = nullptr);
