@@ -139,7 +139,10 @@ __device__ __forceinline__ int cvt_rne_hw(float x) {
 // without v_div_scale / v_div_fmas' scaling / v_div_fixup, which only act on operands or quotients
 // outside the normal exponent range, zeros, infinities and NaNs.  `safe` (wave-uniform) tells
 // whether every lane is inside that range; otherwise the generic division is used, so results are
-// bit-identical to `/` in all cases.  Sharing the reciprocal saves one quarter-rate v_rcp_f32 and
+// bit-identical to `/` for every operand the projection can produce.  (Not for a numerator of -0 over
+// a positive denominator, which comes out +0: the numerators here are sums o + c, never -0, and the
+// sign of a zero quotient is lost in q * f + (c + 0.5) anyway -- tests/test_gpu_ka_math.py pins both.)
+// Sharing the reciprocal saves one quarter-rate v_rcp_f32 and
 // two FMAs per voxel in the projection (two quotients over p.z).
 struct Recip { float d, r; };
 __device__ __forceinline__ Recip recip_refined(float d) {
