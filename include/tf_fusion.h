@@ -568,7 +568,7 @@ TF_API int tf_raycast(tf_volume* v, const float pose[12], float near_plane, floa
                       float* depth, float* normal, uint8_t* rgba, float* vertex);
 TF_API int tf_raycast_device(tf_volume* v, const float pose[12], float near_plane, float far_plane, int32_t max_steps,
                              float* d_depth, float* d_normal, uint8_t* d_rgba, float* d_vertex);
-/* camera of the raycaster only (intrinsics truncated to int like tf_set_camera's; any width up to 32768); width = height
+/* camera of the raycaster, the renderer and the aligner only (intrinsics truncated to int like tf_set_camera's; any width up to 32768); width = height
  * = 0 goes back to the camera of tf_set_camera.  fx, fy >= 1; fx, fy, cx, cy finite and of magnitude below 2^31.  Every
  * output of tf_raycast(_device) holds the W x H of the camera active at the call. */
 TF_API int tf_raycast_camera(tf_volume* v, float fx, float fy, float cx, float cy, int width, int height);
@@ -591,6 +591,70 @@ TF_API int tf_distance_from_surface_device(tf_volume* v, const float* d_xyz, int
  * tf_integrate_frames_device with no host round trip). */
 TF_API int tf_refine_frame_in_voxel(tf_volume* v, float* depth, float* weight, const float pose[12]);
 TF_API int tf_refine_frame_in_voxel_device(tf_volume* v, float* d_depth, float* d_weight, const float pose[12]);
+
+/* ---- frame-to-model alignment (tf_align.hip) ---------------------------------------------
+ * Given a depth image (W x H and intrinsics of tf_raycast_camera if one is set, else of tf_set_camera) and an approximate camera-to-world pose, find the pose at which the frame
+ * lies on the fused surface: Gauss-Newton on the trilinear SDF at the back-projected pixels (the step the reference
+ * leaves commented out at GCFusion/MobileFusion.cpp:322; the method is this library's own, its order of operations is
+ * fixed in tf_align.hip and restated in tests/align_ref.py).  Read-only, as the calls above.
+ *
+ * Level l samples the pixels with x % stride[l] == 0 && y % stride[l] == 0 and takes up to iters[l] steps.  A sampled
+ * pixel whose depth z is finite and in [min_depth, max_depth] gives the camera point ((x - cx - 0.5) / fx * z,
+ * (y - cy - 0.5) / fy * z, z) (int-truncated intrinsics: the raycaster's ray), the world point pw = t + R pc, the
+ * trilinear SDF s at pw and at pw +- one voxel along each axis.  The pixel is valid when all seven samples are and
+ * |s| <= max_residual.  Residual r = s, gradient g by central differences, Jacobian [g, (R pc) x g] of a twist (v, w)
+ * about the camera centre (R <- exp([w]x) R, t <- t + v), weight 1 where huber == 0 or |r| <= huber, else huber / |r|.
+ * One evaluation sums A = sum w J J^T, b = sum w J r, sum r^2, sum w r^2 in f64 in an order that depends on (W, H, stride)
+ * alone; a step solves (A + damping diag(A)) xi = -b by Cholesky and updates the pose (carried in f64).
+ * Stops: n_valid < min_valid -> TF_ALIGN_TOO_FEW; a pivot <= 1e-12 * the largest diagonal entry -> TF_ALIGN_SINGULAR
+ * (a plane alone); on either the pose of that evaluation is the result and nothing further is sampled.  A level ends
+ * early when |v| < eps_t && |w| < eps_r; at the last level that is TF_ALIGN_CONVERGED, otherwise the call ends as
+ * TF_ALIGN_MAX_ITERS.  After the last step one closing evaluation records the final sums and makes no update.
+ * The status is a field of the result, not the return value: a call that stops returns TF_OK. */
+#define TF_ALIGN_CONVERGED 0
+#define TF_ALIGN_MAX_ITERS 1
+#define TF_ALIGN_TOO_FEW 2
+#define TF_ALIGN_SINGULAR 3
+#define TF_ALIGN_MAX_EVALUATIONS 65 /* 64 steps and the closing evaluation */
+typedef struct tf_align_params {
+  int32_t n_levels;               /* 1..4 */
+  int32_t stride[4], iters[4];    /* stride >= 1; iters >= 0, sum of iters <= 64 */
+  float min_depth, max_depth, max_residual, huber, damping, eps_t, eps_r;
+  int32_t min_valid;
+} tf_align_params;
+typedef struct tf_align_result {
+  int32_t status, evaluations, n_sampled, n_valid_first, n_valid_last; /* n_sampled: of the last evaluation */
+  float rms_first, rms_last;      /* sqrt(sum r^2 / n_valid), unweighted; 0 where n_valid == 0 */
+  float pose[12];
+} tf_align_result;
+typedef struct tf_align_iter {    /* one per evaluation, closing one included */
+  int32_t level, stride, n_sampled, n_valid;
+  double sum_r2, sum_wr2, A[21], b[6], xi[6], pose[12]; /* A: upper entries row by row; xi: the step taken (0: none);
+                                                           pose: the one the sums were taken at */
+} tf_align_iter;
+/* strides {4, 2, 1}, iters {4, 3, 2}, depth in [0.05, 5], max_residual 0.03, huber 0.01, damping 0, eps 1e-5 / 1e-5,
+ * min_valid 100 */
+TF_API int tf_align_default_params(tf_align_params* out);
+/* TF_ERR_INVALID (nothing launched) for n_levels outside 1..4, a stride < 1, a negative iters entry or a sum above 64,
+ * a non-finite parameter or pose entry, min_depth > max_depth, negative huber / damping / eps_t / eps_r, no camera.
+ * tf_align_frame: host image, synchronous (it waits once, for the result).  _device: device image and device result,
+ * asynchronous on the handle's stream: every launch of the call is enqueued up front, a launch behind a stop returns at
+ * once, nothing is read back. */
+TF_API int tf_align_frame(tf_volume* v, const float* depth, const float pose[12], const tf_align_params* params,
+                          tf_align_result* result);
+TF_API int tf_align_frame_device(tf_volume* v, const float* d_depth, const float pose[12], const tf_align_params* params,
+                                 tf_align_result* d_result);
+/* the records of the last tf_align_frame(_device) call of this handle (waits for it): up to cap of them to out (may be
+ * NULL with cap 0), *n = how many there are.  A of a record is the information matrix of the pose at that evaluation. */
+TF_API int tf_align_log(tf_volume* v, tf_align_iter* out, int64_t cap, int64_t* n);
+/* The residual map of one evaluation at stride[0] (iters are not read): r f32[H][W], grad3 f32 planar [3][H][W],
+ * flags u32[H][W]; any may be NULL.  flags: bit 0 depth in range, bit 1 centre sample valid, bit 2 all six taps valid,
+ * bit 3 |s| <= max_residual; each bit is set only where the ones below it are, a pixel is valid when flags == 15.
+ * r = s where bits 0 and 1 are set, else 0; grad where bits 0 to 2 are set, else 0; pixels not sampled get 0 everywhere. */
+TF_API int tf_align_residuals(tf_volume* v, const float* depth, const float pose[12], const tf_align_params* params,
+                              float* r, float* grad3, uint32_t* flags);
+TF_API int tf_align_residuals_device(tf_volume* v, const float* d_depth, const float pose[12],
+                                     const tf_align_params* params, float* d_r, float* d_grad3, uint32_t* d_flags);
 
 /* ---- meshing (the stage between the volume and the atlas) -----
  * Chisel::UpdateMeshes (Structure/Chisel.h:479-481) -> ChunkManager::RecomputeMeshes

@@ -53,10 +53,16 @@ SYMBOLS = (
     "tf_query_points", "tf_query_points_device", "tf_raycast", "tf_raycast_device", "tf_raycast_camera",
     "tf_distance_from_surface", "tf_distance_from_surface_device", "tf_refine_frame_in_voxel",
     "tf_refine_frame_in_voxel_device", "tf_view_select", "tf_view_select_device",
+    "tf_align_default_params", "tf_align_frame", "tf_align_frame_device", "tf_align_log", "tf_align_residuals",
+    "tf_align_residuals_device",
     "tf_texmap_set_keyframes", "tf_texmap_update", "tf_texmap_retract", "tf_texmap_remove_wrong_mapping",
     "tf_texmap_check_graph", "tf_texmap_view_selection", "tf_texmap_download", "tf_texmap_download_problem",
     "tf_texmap_clear", "tf_generate_patches_selected", "tf_texture_tail_device", "tf_texture_tail_list",
 )
+
+# tf_align_result.status
+TF_ALIGN_CONVERGED, TF_ALIGN_MAX_ITERS, TF_ALIGN_TOO_FEW, TF_ALIGN_SINGULAR = 0, 1, 2, 3
+TF_ALIGN_MAX_EVALUATIONS = 65
 
 # tf_query_points want_mask bits
 Q_SDF, Q_WEIGHT, Q_GRAD, Q_SDF_TRI, Q_RGB_TRI = 1, 2, 4, 8, 16
@@ -103,6 +109,48 @@ class UnitFrame(C.Structure):
 class UnitGroup(C.Structure):
     _fields_ = [("kf_id", C.c_int32), ("n_local", C.c_int32), ("keyframe", UnitFrame), ("local", UnitFrame * 6),
                 ("old_keyframe_pose", C.c_float * 12), ("old_local_pose", (C.c_float * 12) * 6)]
+
+
+class AlignParamsC(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("stride", C.c_int32 * 4), ("iters", C.c_int32 * 4), ("min_depth", C.c_float),
+                ("max_depth", C.c_float), ("max_residual", C.c_float), ("huber", C.c_float), ("damping", C.c_float),
+                ("eps_t", C.c_float), ("eps_r", C.c_float), ("min_valid", C.c_int32)]
+
+
+class AlignResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("evaluations", C.c_int32), ("n_sampled", C.c_int32), ("n_valid_first", C.c_int32),
+                ("n_valid_last", C.c_int32), ("rms_first", C.c_float), ("rms_last", C.c_float), ("pose", C.c_float * 12)]
+
+
+class AlignIter(C.Structure):
+    _fields_ = [("level", C.c_int32), ("stride", C.c_int32), ("n_sampled", C.c_int32), ("n_valid", C.c_int32),
+                ("sum_r2", C.c_double), ("sum_wr2", C.c_double), ("A", C.c_double * 21), ("b", C.c_double * 6),
+                ("xi", C.c_double * 6), ("pose", C.c_double * 12)]
+
+
+def AlignParams(**kw):
+    """tf_align_params: the library's defaults (tf_align_default_params) with fields replaced by keyword.  levels=[(stride,
+    iters), ...] sets n_levels, stride and iters together."""
+    p = AlignParamsC()
+    rc = lib().tf_align_default_params(C.byref(p))
+    if rc != TF_OK:
+        raise TFError(rc, lib().tf_last_error().decode())
+    levels = kw.pop("levels", None)
+    if levels is not None:
+        p.n_levels = len(levels)
+        for i, (st, it) in enumerate(levels[:4]):
+            p.stride[i], p.iters[i] = int(st), int(it)
+    for k, val in kw.items():
+        if k in ("stride", "iters"):
+            for i, x in enumerate(val):
+                getattr(p, k)[i] = int(x)
+        elif k in ("n_levels", "min_valid"):
+            setattr(p, k, int(val))
+        elif any(k == f[0] for f in AlignParamsC._fields_):
+            setattr(p, k, float(val))
+        else:
+            raise TypeError("tf_align_params has no field %r" % k)
+    return p
 
 
 class Profile(C.Structure):
@@ -259,6 +307,13 @@ def lib():
     L.tf_distance_from_surface_device.argtypes = [vp, vp, C.c_int64, vp, vp]
     L.tf_refine_frame_in_voxel.argtypes = [vp, fp, fp, fp]
     L.tf_refine_frame_in_voxel_device.argtypes = [vp, vp, vp, fp]
+    app = C.POINTER(AlignParamsC)
+    L.tf_align_default_params.argtypes = [app]
+    L.tf_align_frame.argtypes = [vp, fp, fp, app, C.POINTER(AlignResult)]
+    L.tf_align_frame_device.argtypes = [vp, vp, fp, app, vp]
+    L.tf_align_log.argtypes = [vp, C.POINTER(AlignIter), C.c_int64, i64p]
+    L.tf_align_residuals.argtypes = [vp, fp, fp, app, fp, fp, C.POINTER(C.c_uint32)]
+    L.tf_align_residuals_device.argtypes = [vp, vp, fp, app, vp, vp, vp]
     L.tf_view_select.argtypes = [vp, C.c_int64, i32p, i32p, i64p, i32p, fp, C.c_float, i32p, C.c_int32, i32p,
                                  C.POINTER(C.c_double), i32p]
     L.tf_view_select_device.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_float, vp, C.c_int32, vp, vp, vp]
@@ -750,6 +805,74 @@ class Volume:
     def refine_frame_device(self, d_depth, d_weight, pose):
         pose = _f32(pose).reshape(12)
         self._ck(self.L.tf_refine_frame_in_voxel_device(self.h, d_depth or None, d_weight or None, _p(pose, C.c_float)))
+
+    # -- frame-to-model alignment (tf_align_*; read-only)
+    def _align_depth(self, depth):
+        """(depth as a contiguous f32 array, H, W) of the camera the aligner reads: raycast_camera's if set, else the handle's"""
+        H, W = self._render_size()
+        d = _f32(depth)
+        if d.size != W * H:
+            raise TFError(TF_ERR_INVALID, "depth needs %dx%d pixels" % (W, H))
+        return d, H, W
+
+    def align_frame(self, depth, pose, params=None):
+        """The pose at which the depth image [H, W] lies on the fused surface, from an approximate camera-to-world pose ->
+        dict(status, evaluations, n_sampled, n_valid_first, n_valid_last, rms_first, rms_last, pose [3, 4] f32)."""
+        d, _, _ = self._align_depth(depth)
+        pose = _f32(pose).reshape(12)
+        params = params or AlignParams()
+        res = AlignResult()
+        self._ck(self.L.tf_align_frame(self.h, _p(d, C.c_float), _p(pose, C.c_float), C.byref(params), C.byref(res)))
+        return self.align_result(res)
+
+    @staticmethod
+    def align_result(res):
+        """an AlignResult (or its 76 bytes as read back from the device) as a dict"""
+        if not isinstance(res, AlignResult):
+            res = AlignResult.from_buffer_copy(bytes(bytearray(res)))
+        out = {k: getattr(res, k) for k, _ in AlignResult._fields_ if k != "pose"}
+        out["pose"] = np.array(res.pose, np.float32).reshape(3, 4)
+        return out
+
+    def align_frame_device(self, d_depth, pose, params, d_result):
+        """Asynchronous on the handle's stream: device depth image, the tf_align_result written to d_result"""
+        pose = _f32(pose).reshape(12)
+        self._ck(self.L.tf_align_frame_device(self.h, d_depth or None, _p(pose, C.c_float), C.byref(params), d_result or None))
+
+    def align_log(self):
+        """The records of the last align_frame(_device): a list of dicts (level, stride, n_sampled, n_valid, sum_r2, sum_wr2,
+        A [6, 6] f64 symmetric, A21 the upper entries as logged, b, xi [6] f64, pose [3, 4] f64), closing evaluation included."""
+        n = C.c_int64(0)
+        buf = (AlignIter * TF_ALIGN_MAX_EVALUATIONS)()
+        self._ck(self.L.tf_align_log(self.h, buf, TF_ALIGN_MAX_EVALUATIONS, C.byref(n)))
+        out = []
+        iu = np.triu_indices(6)
+        for k in range(min(n.value, TF_ALIGN_MAX_EVALUATIONS)):
+            it = buf[k]
+            A21 = np.array(it.A, np.float64)
+            A = np.zeros((6, 6), np.float64)
+            A[iu] = A21
+            A = A + np.triu(A, 1).T
+            out.append(dict(level=it.level, stride=it.stride, n_sampled=it.n_sampled, n_valid=it.n_valid, sum_r2=it.sum_r2,
+                            sum_wr2=it.sum_wr2, A=A, A21=A21, b=np.array(it.b, np.float64), xi=np.array(it.xi, np.float64),
+                            pose=np.array(it.pose, np.float64).reshape(3, 4)))
+        return out
+
+    def align_residuals(self, depth, pose, params=None):
+        """The residual map of one evaluation at params.stride[0] -> dict(r [H, W] f32, grad [3, H, W] f32, flags [H, W] u32;
+        a pixel is valid where flags == 15)"""
+        d, H, W = self._align_depth(depth)
+        pose = _f32(pose).reshape(12)
+        params = params or AlignParams()
+        out = {"r": np.zeros((H, W), np.float32), "grad": np.zeros((3, H, W), np.float32), "flags": np.zeros((H, W), np.uint32)}
+        self._ck(self.L.tf_align_residuals(self.h, _p(d, C.c_float), _p(pose, C.c_float), C.byref(params),
+                                           _p(out["r"], C.c_float), _p(out["grad"], C.c_float), _p(out["flags"], C.c_uint32)))
+        return out
+
+    def align_residuals_device(self, d_depth, pose, params, d_r=0, d_grad=0, d_flags=0):
+        pose = _f32(pose).reshape(12)
+        self._ck(self.L.tf_align_residuals_device(self.h, d_depth or None, _p(pose, C.c_float), C.byref(params),
+                                                  d_r or None, d_grad or None, d_flags or None))
 
     # -- view selection (the solve of TexMap::view_selection)
     def view_select(self, ids, nbr, col_off, labels, costs, edge_cost=0.5, init=None, max_rounds=0, out=None):

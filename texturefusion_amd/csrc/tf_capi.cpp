@@ -832,6 +832,7 @@ int tf_volume_reset(tf_volume* v) {
   TF_HIP(hipStreamSynchronize(v->stream));
   texmap_release(v);  // TexMap::clear, and its storage given back
   cc_release(v);
+  align_release(v);
   model_release(v);
   rc = init_device_state(v);
   if (rc) return rc;

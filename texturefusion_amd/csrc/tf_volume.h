@@ -64,7 +64,7 @@ void set_error(const std::string& msg);
 // The model generation (tf_volume::model_gen) decides whether the resident model stream (ModelState) is current.  It is
 // advanced by EVERY entry point -- TF_DEV_NOFLUSH above -- except the few that enter through TF_DEV_READER: calls that
 // provably change no mesh, no patch and no pool slot (tf_model_stream_*, tf_render_*, tf_raycast*, tf_query_points*,
-// tf_sync).  A reader that is not on that list costs one repack; a writer cannot be forgotten.  A reader that has to bring
+// tf_align_*, tf_sync).  A reader that is not on that list costs one repack; a writer cannot be forgotten.  A reader that has to bring
 // deferred frames or a pending patch stage onto the stream first is a writer for that call.
 #define TF_DEV_READER(v)                                                                    \
   do {                                                                                      \
@@ -180,6 +180,13 @@ struct CcState {
   DevMem block;
 };
 
+// Frame-to-model alignment (tf_align.hip): partial sums, the f64 pose, control words, the log -- one block sized for the
+// camera at stride 1, null until first use
+struct AlignState {
+  DevMem block;
+  size_t cap_tiles = 0;  // 8 x 8 pixel tiles the block has room for
+};
+
 // The model's DrawMeshes stream, resident in the handle (tf_model.hip): packed on the device, counts in device words,
 // kept until the model changes.  Everything is empty until first use; `ModelState{}` gives it all back.
 struct ModelState {
@@ -286,6 +293,7 @@ struct tf_volume {
   tf::TexMapDev tm{};   // TexMap resident on the device: null pointers until the first tf_texmap_* call
   tf::TexMapState tmx;
   tf::CcState cc;
+  tf::AlignState align;
   tf::ModelState model;
   uint64_t model_gen = 0;  // advanced by every entry point that is not a whitelisted reader (TF_DEV_READER)
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
@@ -388,6 +396,7 @@ int patch_stage_device(tf_volume* v, const int4* d_list, uint32_t n, uint32_t* d
 // Chisel::CompensateColor enqueued on the handle's stream, nothing read back (tf_cc.hip); cc_release frees its buffers
 int cc_enqueue(tf_volume* v, uint32_t* d_n_clusters);
 void cc_release(tf_volume* v);
+void align_release(tf_volume* v);  // frees tf_align.hip's state block
 // the resident model stream (tf_model.hip).  model_pack_enqueue: list, rank, scan and write on the handle's stream, nothing
 // read back (the buffers exist and have a capacity); model_stream_sync: the pack, one wait for the control block, the
 // buffers grown and the pack repeated on overflow -- ModelState::nv / ni are the counts afterwards; model_release frees all

@@ -839,6 +839,30 @@ class Chisel {
     tf_check(tf_refine_frame_in_voxel(vol, depthImage, weight, depthExtrinsic.data()), "RefineFrameInVoxel");
   }
 
+  // The step GCFusion/MobileFusion.cpp:322 leaves commented out (OptimizeKeyframeVoxelDomain): the pose at which depthImage
+  // (W x H and intrinsics of the readers' camera: tf_raycast_camera's if one is set -- a viewer camera set for RenderModel
+  // or a raycast counts! -- else the volume's camera) lies on the fused surface, from the approximate pose depthExtrinsic (tf_align_frame).
+  // params == nullptr: the library's defaults.  Returns result->status (TF_ALIGN_*); result->pose is the aligned pose.
+  int AlignFrameToModel(const float* depthImage, const Transform& depthExtrinsic, const tf_align_params* params,
+                        tf_align_result* result) {
+    tf_align_params def;
+    if (!params) {
+      tf_check(tf_align_default_params(&def), "AlignFrameToModel");
+      params = &def;
+    }
+    tf_check(tf_align_frame(vol, depthImage, depthExtrinsic.data(), params, result), "AlignFrameToModel");
+    return result->status;
+  }
+  // Every record of the last AlignFrameToModel in one ABI call (the closing evaluation included); A of a record is the
+  // information matrix of the pose at that evaluation.
+  std::vector<tf_align_iter> AlignLog() {
+    std::vector<tf_align_iter> log(TF_ALIGN_MAX_EVALUATIONS);
+    int64_t n = 0;
+    tf_check(tf_align_log(vol, log.data(), (int64_t)log.size(), &n), "AlignLog");
+    log.resize((size_t)n);
+    return log;
+  }
+
   // Structure/Chisel.h:103-140.  depthImage is borrowed for the call (uploaded to HBM and kept
   // bound for the IntegrateDepthScanColor calls that follow, like the reference keeps the cv::Mat).
   void PrepareIntersectChunks(ProjectionIntegrator& integrator, float* depthImage,
