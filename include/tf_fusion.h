@@ -656,6 +656,55 @@ TF_API int tf_align_residuals(tf_volume* v, const float* depth, const float pose
 TF_API int tf_align_residuals_device(tf_volume* v, const float* d_depth, const float pose[12],
                                      const tf_align_params* params, float* d_r, float* d_grad3, uint32_t* d_flags);
 
+/* ---- alignment by colour as well as depth (tf_align_color.hip) -----------------------------
+ * tf_align_frame with a photometric row beside each geometric one, so that the pose is also held inside a surface (a
+ * wall, a floor, a table top: there the geometric call ends TF_ALIGN_SINGULAR or at a pose that depends on its start).
+ * rgba is the frame's u8[H][W][4] image as the integrator takes it (alpha = colour valid), of the same camera as depth.
+ * The geometric row, its flag bits 0 to 3 and its sums are tf_align_frame's.  The model's intensity at a point is the
+ * trilinear mean of the eight corners' (0.299 R + 0.587 G + 0.114 B) / n / 255 (n: the voxel's colour count; valid where
+ * every corner has n > 0), the frame's the same combination of the pixel.  rc = L(pw) - Lf, its gradient gc by central
+ * differences over one voxel, Jacobian [gc, (R pc) x gc], Huber weight with huber_photo.  Flag bit 4: bits 0..3 set,
+ * alpha != 0 and L(pw) valid; bit 5: all six taps' intensities valid; bit 6: |rc| <= max_photo_residual; each bit is set only
+ * where the lower ones are, a pixel is photometrically valid when flags == 127 and geometrically when (flags & 15) == 15.
+ * A step solves (A + photo_weight^2 A_c + damping diag) xi = -(b + photo_weight^2 b_c); everything else -- levels, stops
+ * (TF_ALIGN_TOO_FEW goes by the geometric n_valid), the closing evaluation, the status -- is tf_align_frame's.  With
+ * photo_weight == 0 or on a volume without colour the pose, the status and the geometric sums are tf_align_frame's bit
+ * for bit.  No image gradients, no blurred pyramids, no exposure compensation.  Read-only; its state and log are its own:
+ * tf_align_log keeps meaning the last tf_align_frame call. */
+typedef struct tf_align_color_params {
+  tf_align_params geo;
+  float photo_weight, max_photo_residual, huber_photo; /* intensities in [0, 1]; all >= 0 */
+} tf_align_color_params;
+typedef struct tf_align_color_result {
+  tf_align_result geo;
+  int32_t n_photo_first, n_photo_last;     /* photometrically valid pixels of the first / last evaluation */
+  float rms_photo_first, rms_photo_last;   /* sqrt(sum rc^2 / n_photo), unweighted; 0 where n_photo == 0 */
+} tf_align_color_result;
+typedef struct tf_align_color_iter {       /* one per evaluation, closing one included */
+  tf_align_iter geo;                       /* geo.A, geo.b: the geometric sums alone; geo.xi: the step of the combined system */
+  int32_t n_photo, pad;
+  double sum_rc2, sum_wrc2, Ac[21], bc[6];
+} tf_align_color_iter;
+/* geo = tf_align_default_params', photo_weight 0.1, max_photo_residual 0.25, huber_photo 0.05 */
+TF_API int tf_align_color_default_params(tf_align_color_params* out);
+/* TF_ERR_INVALID (nothing launched) for what tf_align_frame rejects and for a negative or non-finite photo_weight,
+ * max_photo_residual or huber_photo.  tf_align_frame_color: host images, synchronous (it waits once, for the result).
+ * _device: device images (rgba 4-byte aligned) and device result, asynchronous on the handle's stream. */
+TF_API int tf_align_frame_color(tf_volume* v, const float* depth, const uint8_t* rgba, const float pose[12],
+                                const tf_align_color_params* params, tf_align_color_result* result);
+TF_API int tf_align_frame_color_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba, const float pose[12],
+                                       const tf_align_color_params* params, tf_align_color_result* d_result);
+/* the records of the last tf_align_frame_color(_device) call of this handle (waits for it), as tf_align_log */
+TF_API int tf_align_color_log(tf_volume* v, tf_align_color_iter* out, int64_t cap, int64_t* n);
+/* The maps of one evaluation at geo.stride[0]: r, grad3 and flags as tf_align_residuals', rc f32[H][W] (where bit 4 is
+ * set, else 0) and gradc3 f32 planar [3][H][W] (where bit 5 is set, else 0); any may be NULL; pixels not sampled get 0. */
+TF_API int tf_align_color_residuals(tf_volume* v, const float* depth, const uint8_t* rgba, const float pose[12],
+                                    const tf_align_color_params* params, float* r, float* grad3, float* rc, float* gradc3,
+                                    uint32_t* flags);
+TF_API int tf_align_color_residuals_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba, const float pose[12],
+                                           const tf_align_color_params* params, float* d_r, float* d_grad3, float* d_rc,
+                                           float* d_gradc3, uint32_t* d_flags);
+
 /* ---- meshing (the stage between the volume and the atlas) -----
  * Chisel::UpdateMeshes (Structure/Chisel.h:479-481) -> ChunkManager::RecomputeMeshes
  *   (Structure/ChunkManager.cpp:232-264): every chunk of meshesToUpdate that exists is re-meshed by

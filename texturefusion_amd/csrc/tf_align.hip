@@ -24,7 +24,7 @@
 //   A_ij = sum (double)wJ_i * (double)J_j (i <= j, the 21 upper entries row by row),  b_i = sum (double)wJ_i * (double)r,
 //   sum_r2 = sum (double)r * (double)r,  sum_wr2 = sum (double)wr * (double)r,  n_valid, n_sampled (pixels inside the image)
 // Order of summation, a function of (W, H, stride) alone: the 64 lanes of a tile by the tree of ccd_wave_sum (xor 32,
-// 16, .. 1; each node computed by one lane, see k_align_rows), the eight tiles of a workgroup in wave order, one plain-stored
+// 16, .. 1; each node computed by one lane, tf_align_tree.h), the eight tiles of a workgroup in wave order, one plain-stored
 // row per workgroup; in k_align_solve eight threads per sum add the rows g, g + 8, g + 16, .. in ascending order (g = 0..7),
 // then the eight in order.
 // No atomics, no counters, no polling: the launch boundary between k_align_rows and k_align_solve is the only hand-off.
@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "tf_align_solve.h"
+#include "tf_align_tree.h"
 #include "tf_ray_devfn.h"
 #include "tf_volume.h"
 
@@ -46,10 +47,6 @@
 namespace tf {
 namespace {
 
-constexpr int kAlSums = 31;  // A[21] b[6] sum_r2 sum_wr2 n_valid n_sampled
-constexpr int kAlA = 0, kAlB = 21, kAlR2 = 27, kAlWr2 = 28, kAlNv = 29, kAlNs = 30;
-constexpr int kAlRow = 32;  // doubles a tile's partial sums take (the 31 and one of padding)
-constexpr int kAlWaves = 8;  // tiles (waves) of a workgroup of k_align_rows
 constexpr int kAlignMaxIters = 64;
 
 struct AlignCtl {
@@ -96,37 +93,6 @@ __device__ __forceinline__ bool al_idle(const uint32_t* state, int level) {
   const uint32_t st = *state;
   return (st & 1u) || (uint32_t)level < (st >> 8);
 }
-// entry e of the sums = (double)left[kAlLeft[e]] * (double)right[kAlRight[e]] with
-// left = {wJ_0..5, wr, r, valid, in}, right = {J_0..5, r, 1}
-struct AlPairs { int l[32], r[32]; };
-constexpr AlPairs al_pairs() {
-  AlPairs p{};
-  int e = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j, ++e) { p.l[e] = i; p.r[e] = j; }
-  for (int i = 0; i < 6; ++i, ++e) { p.l[e] = i; p.r[e] = 6; }
-  p.l[kAlR2] = 7; p.r[kAlR2] = 6;
-  p.l[kAlWr2] = 6; p.r[kAlWr2] = 6;
-  p.l[kAlNv] = 8; p.r[kAlNv] = 7;
-  p.l[kAlNs] = 9; p.r[kAlNs] = 7;
-  p.l[31] = 9; p.r[31] = 7;
-  return p;
-}
-constexpr AlPairs kAlPairs = al_pairs();
-#define kAlLeft kAlPairs.l
-#define kAlRight kAlPairs.r
-// one level of the tree: a lane keeps the upper half of its N entries where bit o of its number is set, else the lower
-// half, and adds the partner's (lane ^ o) values of the same entries
-template <int N>
-__device__ __forceinline__ void al_halve(double (&v)[16], int o, int lane) {
-  const bool up = (lane & o) != 0;
-#pragma unroll
-  for (int i = 0; i < N / 2; ++i) {
-    const double keep = up ? v[i + N / 2] : v[i], send = up ? v[i] : v[i + N / 2];
-    v[i] = keep + __shfl_xor(send, o);
-  }
-}
-
 __global__ __launch_bounds__(64) void k_align_begin(AlignDev d, AlignPose p, int residuals_only) {
   const int i = threadIdx.x;
   if (residuals_only) {
@@ -207,36 +173,9 @@ __global__ __launch_bounds__(kAlWaves * 64) void k_align_rows(VolumeDev v, Align
 #pragma unroll
     for (int i = 0; i < 6; ++i) J[i] = 0.f;
   }
-  // the 31 sums of the tile (a 32nd entry repeats n_sampled and is dropped).  Entry e is the product of left operand
-  // kAlLeft[e] and right operand kAlRight[e], taken in f64.  Level 1 pairs lane l with l ^ 32: each of the two takes one
-  // half of the entries (bit 5 of the lane: entries 16..31) and adds its own term and its partner's, formed from the
-  // partner's operands.  Levels 2..5 (xor 16, 8, 4, 2) halve the entries a lane carries in the same way, level 6 (xor 1)
-  // adds the last pair: lane l ends up with entry (bits 5, 4, 3, 2, 1 of l, most significant first).  Per entry this is
-  // the tree of ccd_wave_sum, each node computed once.
-  const float inf = in ? 1.0f : 0.0f, vf = valid ? 1.0f : 0.0f;
-  float Lo[10], Ro[8], Lp[10], Rp[8];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) { Lo[i] = w * J[i]; Ro[i] = J[i]; }
-  Lo[6] = w * r; Lo[7] = r; Lo[8] = vf; Lo[9] = inf; Ro[6] = r; Ro[7] = 1.0f;
-#pragma unroll
-  for (int i = 0; i < 10; ++i) Lp[i] = __shfl_xor(Lo[i], 32);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) Rp[i] = __shfl_xor(Ro[i], 32);
-  Rp[6] = Lp[7]; Rp[7] = 1.0f;
-  const bool hi = (lane & 32) != 0;
-  double acc[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const float lo_own = hi ? Lo[kAlLeft[i + 16]] : Lo[kAlLeft[i]], ro_own = hi ? Ro[kAlRight[i + 16]] : Ro[kAlRight[i]];
-    const float lo_par = hi ? Lp[kAlLeft[i + 16]] : Lp[kAlLeft[i]], ro_par = hi ? Rp[kAlRight[i + 16]] : Rp[kAlRight[i]];
-    acc[i] = (double)lo_own * (double)ro_own + (double)lo_par * (double)ro_par;
-  }
-  al_halve<16>(acc, 16, lane);
-  al_halve<8>(acc, 8, lane);
-  al_halve<4>(acc, 4, lane);
-  al_halve<2>(acc, 2, lane);
-  const double total = acc[0] + __shfl_xor(acc[0], 1);
-  const int e = ((lane >> 5) & 1) << 4 | ((lane >> 4) & 1) << 3 | ((lane >> 3) & 1) << 2 | ((lane >> 2) & 1) << 1 | ((lane >> 1) & 1);
+  // the 31 sums of the tile through the wave tree (tf_align_tree.h): lane l ends up with entry al_entry(l)
+  const double total = al_tile_sum(J, w, r, valid ? 1.0f : 0.0f, in ? 1.0f : 0.0f, lane);
+  const int e = al_entry(lane);
   // the workgroup's eight tiles in wave order, one plain-stored row per workgroup
   __shared__ double wsum[kAlWaves][kAlRow];
   if (!(lane & 1)) wsum[wave][e] = total;
@@ -336,12 +275,6 @@ AlignDev align_carve(void* base, size_t cap_tiles, size_t* bytes) {
   return d;
 }
 
-// the camera of the depth image: the one tf_raycast_camera set (any size), else the handle's -- as the raycaster's
-struct AlignCam { float fx, fy, cx, cy; int W, H; };
-AlignCam align_cam(const tf_volume* v) {
-  if (v->ray_w > 0) return {v->ray_fx, v->ray_fy, v->ray_cx, v->ray_cy, v->ray_w, v->ray_h};
-  return {v->cam.fxi, v->cam.fyi, v->cam.cxi, v->cam.cyi, v->cam.W, v->cam.H};
-}
 size_t align_pixels(const tf_volume* v) { const AlignCam c = align_cam(v); return (size_t)c.W * (size_t)c.H; }
 size_t align_tiles(const tf_volume* v) {
   const AlignCam c = align_cam(v);
@@ -362,6 +295,15 @@ int align_ensure(tf_volume* v, AlignDev* d) {
   }
   *d = align_carve(v->align.block.p, v->align.cap_tiles, nullptr);
   return TF_OK;
+}
+
+}  // namespace
+
+// shared with tf_align_color.hip (tf_volume.h): the camera and the checks of a call's arguments
+// the camera of the depth image: the one tf_raycast_camera set (any size), else the handle's -- as the raycaster's
+AlignCam align_cam(const tf_volume* v) {
+  if (v->ray_w > 0) return {v->ray_fx, v->ray_fy, v->ray_cx, v->ray_cy, v->ray_w, v->ray_h};
+  return {v->cam.fxi, v->cam.fyi, v->cam.cxi, v->cam.cyi, v->cam.W, v->cam.H};
 }
 
 bool finite_all(const float* p, int n) {
@@ -397,6 +339,8 @@ int align_check(tf_volume* v, const float* depth, const float* pose, const tf_al
   }
   return TF_OK;
 }
+
+namespace {
 
 AlignRowsArgs rows_args(const tf_volume* v, const AlignDev& d, const tf_align_params& p, const float* d_depth, int level,
                         uint32_t* n_tiles) {

@@ -833,6 +833,7 @@ int tf_volume_reset(tf_volume* v) {
   texmap_release(v);  // TexMap::clear, and its storage given back
   cc_release(v);
   align_release(v);
+  align_color_release(v);
   model_release(v);
   rc = init_device_state(v);
   if (rc) return rc;

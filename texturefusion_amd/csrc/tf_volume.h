@@ -186,6 +186,11 @@ struct AlignState {
   DevMem block;
   size_t cap_tiles = 0;  // 8 x 8 pixel tiles the block has room for
 };
+// The colour-aided alignment's own block (tf_align_color.hip), laid out and owned the same way
+struct AlignColorState {
+  DevMem block;
+  size_t cap_tiles = 0;
+};
 
 // The model's DrawMeshes stream, resident in the handle (tf_model.hip): packed on the device, counts in device words,
 // kept until the model changes.  Everything is empty until first use; `ModelState{}` gives it all back.
@@ -294,6 +299,7 @@ struct tf_volume {
   tf::TexMapState tmx;
   tf::CcState cc;
   tf::AlignState align;
+  tf::AlignColorState align_color;
   tf::ModelState model;
   uint64_t model_gen = 0;  // advanced by every entry point that is not a whitelisted reader (TF_DEV_READER)
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
@@ -397,6 +403,13 @@ int patch_stage_device(tf_volume* v, const int4* d_list, uint32_t n, uint32_t* d
 int cc_enqueue(tf_volume* v, uint32_t* d_n_clusters);
 void cc_release(tf_volume* v);
 void align_release(tf_volume* v);  // frees tf_align.hip's state block
+// what tf_align.hip shares with tf_align_color.hip: the readers' camera, and the checks of a call's arguments (with_iters:
+// iters are read too); align_color_release frees tf_align_color.hip's state block
+struct AlignCam { float fx, fy, cx, cy; int W, H; };
+AlignCam align_cam(const tf_volume* v);
+bool finite_all(const float* p, int n);
+int align_check(tf_volume* v, const float* depth, const float* pose, const tf_align_params* p, bool with_iters);
+void align_color_release(tf_volume* v);
 // the resident model stream (tf_model.hip).  model_pack_enqueue: list, rank, scan and write on the handle's stream, nothing
 // read back (the buffers exist and have a capacity); model_stream_sync: the pack, one wait for the control block, the
 // buffers grown and the pack repeated on overflow -- ModelState::nv / ni are the counts afterwards; model_release frees all

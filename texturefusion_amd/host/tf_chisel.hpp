@@ -862,6 +862,28 @@ class Chisel {
     log.resize((size_t)n);
     return log;
   }
+  // AlignFrameToModel with a photometric term (tf_align_frame_color): colorImage is the frame's u8[H][W][4] image as the
+  // integrator takes it (alpha = colour valid), of the same camera as depthImage.  It holds the pose inside a surface too --
+  // a wall, a floor, a table top -- where AlignFrameToModel ends TF_ALIGN_SINGULAR or at a pose that depends on its start.
+  // params == nullptr: the library's defaults.  Returns result->geo.status; result->geo.pose is the aligned pose.
+  int AlignFrameToModelColor(const float* depthImage, const uint8_t* colorImage, const Transform& depthExtrinsic,
+                             const tf_align_color_params* params, tf_align_color_result* result) {
+    tf_align_color_params def;
+    if (!params) {
+      tf_check(tf_align_color_default_params(&def), "AlignFrameToModelColor");
+      params = &def;
+    }
+    tf_check(tf_align_frame_color(vol, depthImage, colorImage, depthExtrinsic.data(), params, result), "AlignFrameToModelColor");
+    return result->geo.status;
+  }
+  // Every record of the last AlignFrameToModelColor (AlignLog keeps meaning the last AlignFrameToModel).
+  std::vector<tf_align_color_iter> AlignColorLog() {
+    std::vector<tf_align_color_iter> log(TF_ALIGN_MAX_EVALUATIONS);
+    int64_t n = 0;
+    tf_check(tf_align_color_log(vol, log.data(), (int64_t)log.size(), &n), "AlignColorLog");
+    log.resize((size_t)n);
+    return log;
+  }
 
   // Structure/Chisel.h:103-140.  depthImage is borrowed for the call (uploaded to HBM and kept
   // bound for the IntegrateDepthScanColor calls that follow, like the reference keeps the cv::Mat).
