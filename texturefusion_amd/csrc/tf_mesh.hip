@@ -40,6 +40,14 @@ constexpr int kRV = kPS * kR;        // 1331 words at the natural stride
 constexpr int kEdgeSlots = 3 * 729;  // vertByEdge (ChunkManager.cpp:646-648)
 __device__ __forceinline__ uint32_t mesh_shard_rows_d(uint32_t max_chunks) { return max_chunks / kMeshShards + 258u; }  // = mesh_shard_rows()
 
+// LOAD BATCHES.  The loads a phase means to have in flight together are written as: addresses first, every
+// load unconditional (a lane without one reads a mapped dummy), selects behind the wait.  Where the optimiser still undoes
+// that -- it sinks a load whose only use sits in a later branch into that branch, merges the load ahead of a loop with the
+// one at the loop's end, splits a wide load whose parts are used under different conditions -- the load is a RELAXED ATOMIC
+// one of wave scope: the same instruction, no cache bits, but kept whole and where it is written.
+template <typename T>
+__device__ __forceinline__ T load_here(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+
 __device__ __forceinline__ int ridx(int x, int y, int z) { return (x + 1) + (y + 1) * kRS + (z + 1) * kPS; }
 
 // Index tables of the staging passes (the kernel is VALU-bound: no div / mod by 11 or 9 per voxel).
@@ -51,7 +59,8 @@ __device__ __forceinline__ int ridx(int x, int y, int z) { return (x + 1) + (y +
 //         region index of the pair's FIRST voxel | neighbour (0..26) << 11 | pair index in that chunk (voxel >> 1) << 16
 //         | use first << 24 | use second << 25 | corner index + 1 of the first (0 = not a corner) << 26 | ... of the
 //         second << 36   (the second voxel's region index is the first's + 1: x-adjacent)
-//   corner: region index of cell corner c = px + 9 py + 81 pz
+// (the region index of cell corner c = px + 9 py + 81 pz is computed where it is needed, ridx(): a table of them was a
+// cache round trip at the head of each of the corner pass's six rounds)
 constexpr bool halo_needed(int rx, int ry, int rz) {
   if (rx < -1 || rx > 9 || ry < -1 || ry > 9 || rz < -1 || rz > 9) return false;  // outside the staged region
   if (rx >= 0 && rx < 8 && ry >= 0 && ry < 8 && rz >= 0 && rz < 8) return false;  // the chunk's own voxels
@@ -74,7 +83,6 @@ constexpr int count_halo_pairs() {
 constexpr int kHalo = count_halo_pairs();
 struct MeshTabs {
   unsigned long long halo[kHalo];
-  uint16_t corner[729];
 };
 constexpr unsigned long long corner_of(int rx, int ry, int rz) {
   return (rx >= 0 && ry >= 0 && rz >= 0 && rx <= 8 && ry <= 8 && rz <= 8) ? (unsigned long long)(rx + ry * 9 + rz * 81 + 1) : 0ull;
@@ -100,10 +108,6 @@ constexpr MeshTabs make_mesh_tabs() {
         t.halo[n++] = (r0 & 2047ull) | (nb << 11) | (pair << 16) | ((use0 ? 1ull : 0ull) << 24) | ((use1 ? 1ull : 0ull) << 25) |
                       ((use0 ? corner_of(rx0, ry, rz) : 0ull) << 26) | ((use1 ? corner_of(rx0 + 1, ry, rz) : 0ull) << 36);
       }
-  for (int c = 0; c < 729; ++c) {
-    const int px = c % 9, py = (c / 9) % 9, pz = c / 81;
-    t.corner[c] = (uint16_t)((px + 1) + (py + 1) * kRS + (pz + 1) * kPS);
-  }
   return t;
 }
 __device__ const MeshTabs d_mesh_tabs = make_mesh_tabs();
@@ -324,7 +328,7 @@ __device__ __forceinline__ void filter_exact(const VolumeDev& v, const int4 id, 
   const uint32_t shard = own & (kMeshShards - 1u);
   const float4* T4 = reinterpret_cast<const float4*>(v.tsdf + (size_t)own * kChunkVoxels);
   uint32_t roww = 0u;  // (!HAVE_ROW: the row's word of this lane, requested ahead of the voxels, looked at behind them)
-  if (!HAVE_ROW && lane < kNbrWords) roww = v.nbr[(size_t)own * kNbrWords + lane];
+  if (!HAVE_ROW) roww = v.nbr[(size_t)own * kNbrWords + (lane & (kNbrWords - 1))];  // (unconditional: a batch with the voxels)
   float4 qv[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) qv[j] = T4[j * 64 + lane];  // voxels 2 i and 2 i + 1 of the chunk, i = 64 j + lane: {sdf, w, sdf, w}
@@ -339,14 +343,19 @@ __device__ __forceinline__ void filter_exact(const VolumeDev& v, const int4 id, 
   }
   fl = wave_or(fl);
   if (!HAVE_ROW) {
-    roww = nbr_row_checked(v, own, id, lane, roww, create_seq);
+    roww = nbr_row_checked(v, own, id, lane, lane < kNbrWords ? roww : 0u, create_seq);
     nslot = lane == 13 ? own : ((lane < 27 && roww) ? roww - 1u : kInvalidSlot);
   }
   if (use_summ && lane == 0) v.summ[own] = fl;  // the chunk's summary is exact again
   if (lane == 0) atomicAdd(&cnt[(kMeshShards + shard) * 16], 1u);  // statistic (tf_texture_stats::n_exact): chunks whose voxels the filter read
   bool empty = !(fl & 1u);
   if (!empty && (fl & 14u) != 14u) {
-    uint32_t f2 = 0;
+    // ONE batch of four scattered loads (LOAD BATCHES): a lane without a voxel (q >= 217) or without a
+    // neighbour chunk reads voxel 0 of the chunk itself -- mapped, and in cache since the pass above -- and is masked out
+    // behind the wait.  A load under a lane-dependent condition is not moved over that condition by the compiler: the four
+    // were four dependent round trips.
+    float2 cv[4];
+    bool chave[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {  // corner voxels with a coordinate 8: 3 faces of 64, 3 edges of 8, 1 corner
       const int q = j * 64 + lane;
@@ -359,11 +368,13 @@ __device__ __forceinline__ void filter_exact(const VolumeDev& v, const int4 id, 
       else if (q < 216) { cx = q & 7; cy = 8; cz = 8; }
       else { cx = 8; cy = 8; cz = 8; }
       const uint32_t s = (uint32_t)__shfl((int)nslot, 13 + (cx >> 3) + 3 * (cy >> 3) + 9 * (cz >> 3));
-      if (q < 217 && s != kInvalidSlot) {
-        const float2 val = v.tsdf[(size_t)s * kChunkVoxels + (cx & 7) + (cy & 7) * 8 + (cz & 7) * 64];
-        f2 |= classify_voxel(val.x, val.y);
-      }
+      chave[j] = q < 217 && s != kInvalidSlot;
+      const uint32_t at = chave[j] ? (uint32_t)((cx & 7) + (cy & 7) * 8 + (cz & 7) * 64) : 0u;
+      cv[j] = v.tsdf[(size_t)(chave[j] ? s : own) * kChunkVoxels + at];
     }
+    uint32_t f2 = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f2 |= chave[j] ? classify_voxel(cv[j].x, cv[j].y) : 0u;
     f2 = wave_or(f2);
     empty = ((fl | f2) & 14u) != 14u;
   }
@@ -502,9 +513,14 @@ __global__ __launch_bounds__(256, PATCH ? (WAVE_FORM ? TF_FILTER_PATCH_WAVES : T
       if (own == kInvalidSlot) return;
       // ONE hop: the chunk's row of the neighbour table (the 27 pool slots around it) and -- for an entry K-A claimed
       // (id.w = hash entry + 1), which may have been parked later in that launch -- the entry's alive word
-      uint32_t w = lane < kNbrWords ? v.nbr[(size_t)own * kNbrWords + lane] : 0u;
-      uint32_t alive = 1u;
-      if (have_own && id.w > 0) alive = v.hent[(uint32_t)id.w - 1u].alive & 1u;
+      // (both unconditional -- lanes beyond the row re-read its words, an entry without a hash entry reads entry 0 -- and
+      // selected afterwards: under their conditions the second was issued when the first had arrived)
+      const bool claimed = have_own && id.w > 0;
+      // (load_here: the row is looked at behind "if (!alive) return" only, and a plain load is sunk behind that branch)
+      const uint32_t roww = load_here(&v.nbr[(size_t)own * kNbrWords + (lane & (kNbrWords - 1))]);
+      const uint32_t alivew = v.hent[claimed ? (uint32_t)id.w - 1u : 0u].alive;
+      uint32_t w = lane < kNbrWords ? roww : 0u;
+      const uint32_t alive = claimed ? (alivew & 1u) : 1u;
       stamp(2, true);
       if (!alive) return;
       w = nbr_row_checked(v, own, id, lane, w, create_seq);
@@ -537,9 +553,13 @@ __global__ __launch_bounds__(256, PATCH ? (WAVE_FORM ? TF_FILTER_PATCH_WAVES : T
       const uint32_t stride = (nwaves - sd + kMeshShards - 1u) / kMeshShards;  // waves that share this shard
       uint32_t i = wave / kMeshShards;
       size_t at = wl_base + (size_t)sd * wl_rows + (i < wl_rows ? i : 0u);
-      int4 id = v.wl_ids[at];
-      uint32_t own_listed = v.wl_slot[at];
-      uint32_t cs = v.wl_cnt[((shards_par & 1) * kMeshShards + sd) * 16];
+      // (load_here: written as plain loads, the entry's two were merged with the reload at the loop's end into ONE site at
+      // the loop's head -- behind the wait for the counter -- and issued there one behind the other: three round trips)
+      const unsigned long long* const idq = reinterpret_cast<const unsigned long long*>(&v.wl_ids[at]);
+      const unsigned long long id_lo = load_here(idq), id_hi = load_here(idq + 1);
+      uint32_t own_listed = load_here(&v.wl_slot[at]);
+      uint32_t cs = load_here(&v.wl_cnt[((shards_par & 1) * kMeshShards + sd) * 16]);
+      int4 id = make_int4((int)(uint32_t)id_lo, (int)(uint32_t)(id_lo >> 32), (int)(uint32_t)id_hi, (int)(uint32_t)(id_hi >> 32));
       if (cs > wl_rows) cs = wl_rows;
       stamp(1, true);
       while (i < cs) {
@@ -697,6 +717,9 @@ __global__ __launch_bounds__(NT, TF_MESH_WAVES) void k_mesh(VolumeDev v, const u
     uint32_t shard, own;
     int4 id;
     float2 a[512 / NT];
+    unsigned long long htab[(kHalo + NT - 1) / NT];
+    uint32_t rstate0, rblock0, rpress0;
+    unsigned long long rtexloc0;
     {
       shard = incl_l;
       uint32_t idx = r - excl_l;
@@ -718,8 +741,29 @@ __global__ __launch_bounds__(NT, TF_MESH_WAVES) void k_mesh(VolumeDev v, const u
       id = make_int4((int)surv[32 * row + 27], (int)surv[32 * row + 28], (int)surv[32 * row + 29], 0);
 #pragma unroll
       for (int j = 0; j < 512 / NT; ++j) a[j] = v.tsdf[(size_t)own * kChunkVoxels + j * NT + t];
+      // the row's word of this thread lies in the 128 bytes own / id came from: requested here, unconditionally (a row
+      // has 32 words), stored behind the barrier -- not a round trip of its own behind it.  (load_here: an ordinary load
+      // from the read-only list, used under "t < 27" only, is sunk into that branch, behind the barrier.)
+      const uint32_t roww = load_here(&surv[32 * row + (t & 31)]);
+      // the thread's entries of the halo table travel with the own voxels: the staging pass below is then ONE hop of
+      // scattered loads instead of table -> voxel.  (ONE batch: the entry beyond the table's end is a clamped load and a
+      // select, not a load under a condition.  The thread index is opaque here: entries that depend on nothing else are
+      // hoisted out of the row loop and kept -- in private memory -- across the whole chunk.)
+      int th = threadIdx.x;
+      asm volatile("" : "+v"(th));
+#pragma unroll
+      for (int j = 0; j < (kHalo + NT - 1) / NT; ++j) {
+        const int at = j * NT + th;
+        const unsigned long long e = d_mesh_tabs.halo[(j + 1) * NT <= kHalo ? at : (at < kHalo ? at : kHalo - 1)];
+        htab[j] = ((j + 1) * NT <= kHalo || at < kHalo) ? e : ~0ull;
+      }
+      // the record's previous state travels with the first batch of loads, so that the tail of the chunk is stores only:
+      // every thread requests it (one line, no condition around the loads), one thread keeps it -- with the stores of the
+      // staging pass below, so that nothing ahead of that pass's barrier waits for it alone
+      const MeshRec* const rec0 = &v.mesh_rec[own];
+      rstate0 = rec0->state; rblock0 = rec0->block; rpress0 = blk_pressure(v); rtexloc0 = rec0->texloc;
       __syncthreads();  // the previous chunk of this workgroup is done with the shared tables
-      if (t < 27) sh.nslot[t] = surv[32 * row + t];
+      if (t < 27) sh.nslot[t] = roww;
     }
     // (what the rest of the chunk derives from the thread index is recomputed here, behind an opaque statement, instead
     // of living in registers across the row / voxel loads above: 88 instead of 96 VGPRs, no private memory)
@@ -727,15 +771,8 @@ __global__ __launch_bounds__(NT, TF_MESH_WAVES) void k_mesh(VolumeDev v, const u
     asm volatile("" : "+v"(t_));
     const int t = t_, lane = t & 63, w = t >> 6;
     MeshRec* rec = &v.mesh_rec[own];
-    // the thread's entries of the halo table travel with the own voxels: the staging pass below is then ONE hop of
-    // scattered loads instead of table -> voxel
-    unsigned long long htab[(kHalo + NT - 1) / NT];
-#pragma unroll
-    for (int j = 0; j < (kHalo + NT - 1) / NT; ++j) htab[j] = (j * NT + t < kHalo) ? d_mesh_tabs.halo[j * NT + t] : ~0ull;
     if (DBG && dbg == 9) mesh_stamp(v, r, 1);
     if (t == 0) { sh.nv = 0; sh.nt = 0; sh.adj = 0; sh.ncell = 0; }
-    // the record's previous state travels with the first batch of loads, so that the tail of the chunk is stores only
-    if (t == NT - 64) { sh.rstate = rec->state; sh.rblock = rec->block; sh.rtexloc = rec->texloc; sh.rpress = blk_pressure(v); }
     if (DBG && dbg == 1) continue;  // triage: filter only
     // ---- stage the 11^3 voxels of the neighbourhood (own ones from registers)
 #pragma unroll
@@ -744,23 +781,36 @@ __global__ __launch_bounds__(NT, TF_MESH_WAVES) void k_mesh(VolumeDev v, const u
       const int x0 = q & 7, y0 = (q >> 3) & 7, z0 = q >> 6;
       sh.S[ridx(x0, y0, z0)] = a[j].x; sh.cflag[x0 + y0 * 9 + z0 * 81] = (a[j].y > 50.0f) ? kCfHeavy : 0u;
     }
+    if (t == NT - 64) { sh.rstate = rstate0; sh.rblock = rblock0; sh.rtexloc = rtexloc0; sh.rpress = rpress0; }
     __syncthreads();
-    // (measured: issuing the row, the table entries and then own + halo voxels as two batches of loads -- two
-    // dependent hops instead of four -- is slower, 36 -> 46 us: the extra registers spill)
+    // (round 4 measured the row, the table entries and then own + halo voxels as two batches of loads as slower, 36 -> 46 us:
+    // its extra registers spilled.  The batches below hold the 80 VGPRs without private memory: profiles/load_batches.)
+    // ONE batch of scattered loads (LOAD BATCHES): addresses first, every load unconditional, selects behind
+    // the wait.  A thread without an entry (~0ull: its neighbour field reads 31, clamped into the 27 words) or whose
+    // neighbour chunk does not exist loads pair 0 of the chunk itself and takes the fresh state instead.  With the loads
+    // under those two conditions the compiler kept each behind the LDS stores of the one before: four dependent round
+    // trips to scattered lines per chunk.  (Different entries never write the same LDS word: their order is free.)
+    float4 hv[(kHalo + NT - 1) / NT];
+    bool hhave[(kHalo + NT - 1) / NT];
 #pragma unroll
     for (int j = 0; j < (kHalo + NT - 1) / NT; ++j) {
       const unsigned long long e = htab[j];
-      if (e == ~0ull) continue;
-      const uint32_t s = sh.nslot[(uint32_t)(e >> 11) & 31u];
-      float4 val = make_float4(999.0f, 0.0f, 999.0f, 0.0f);  // a missing chunk reads as the fresh state
-      if (s != kInvalidSlot) val = reinterpret_cast<const float4*>(v.tsdf + (size_t)s * kChunkVoxels)[(uint32_t)(e >> 16) & 255u];
+      const uint32_t nb = (uint32_t)(e >> 11) & 31u;
+      const uint32_t s = sh.nslot[nb < 26u ? nb : 26u];
+      hhave[j] = e != ~0ull && s != kInvalidSlot;
+      hv[j] = reinterpret_cast<const float4*>(v.tsdf + (size_t)(hhave[j] ? s : own) * kChunkVoxels)[hhave[j] ? (uint32_t)(e >> 16) & 255u : 0u];
+    }
+#pragma unroll
+    for (int j = 0; j < (kHalo + NT - 1) / NT; ++j) {
+      const unsigned long long e = htab[j];
+      const float4 val = hhave[j] ? hv[j] : make_float4(999.0f, 0.0f, 999.0f, 0.0f);  // a missing chunk reads as the fresh state
       const uint32_t r0 = (uint32_t)e & 2047u;
-      if ((e >> 24) & 1ull) {
+      if (e != ~0ull && ((e >> 24) & 1ull)) {
         sh.S[r0] = val.x;
         const uint32_t cf = (uint32_t)(e >> 26) & 1023u;
         if (cf) sh.cflag[cf - 1u] = (val.y > 50.0f) ? kCfHeavy : 0u;
       }
-      if ((e >> 25) & 1ull) {
+      if (e != ~0ull && ((e >> 25) & 1ull)) {
         sh.S[r0 + 1u] = val.z;
         const uint32_t cf = (uint32_t)(e >> 36) & 1023u;
         if (cf) sh.cflag[cf - 1u] = (val.w > 50.0f) ? kCfHeavy : 0u;
@@ -772,7 +822,7 @@ __global__ __launch_bounds__(NT, TF_MESH_WAVES) void k_mesh(VolumeDev v, const u
     // for the three neighbours OUTSIDE its cube (extractGradientFromCubic fetches those through
     // GetNeighborSDF, :320-447), so the answer per (cell, corner) is three of these bits.
     for (int c = t; c < 729; c += NT) {
-      const int r = d_mesh_tabs.corner[c];
+      const int r = ridx(c % 9, (c / 9) % 9, c / 81);  // (constant divisions: a few multiplies, no load)
       const float xm = sh.S[r - 1], xp = sh.S[r + 1], ym = sh.S[r - kRS], yp = sh.S[r + kRS];
       const float zm = sh.S[r - kPS], zp = sh.S[r + kPS];
       uint32_t f = (xm < 1.0f ? 1u : 0u) | (xp < 1.0f ? 2u : 0u) | (ym < 1.0f ? 4u : 0u) | (yp < 1.0f ? 8u : 0u) |
@@ -987,13 +1037,15 @@ __global__ __launch_bounds__(NT, TF_MESH_WAVES) void k_mesh(VolumeDev v, const u
       gradient_at(sh.S, px, py, pz, cox(k), coy(k), coz(k), res, g);
       // voxel colour of that corner (:808-824)
       const uint32_t cs = sh.nslot[((px + 8) >> 3) + ((py + 8) >> 3) * 3 + ((pz + 8) >> 3) * 9];
-      const ushort4 c4 = v.color[(size_t)cs * kChunkVoxels + (px & 7) + (py & 7) * 8 + (pz & 7) * 64];
+      // (load_here: ONE 8-byte load.  The plain ushort4 load is split into the count -- waited for -- and, under "count > 0",
+      // the three sums: two dependent round trips per vertex.)
+      const unsigned long long c4 = load_here(reinterpret_cast<const unsigned long long*>(v.color + (size_t)cs * kChunkVoxels + (px & 7) + (py & 7) * 8 + (pz & 7) * 64));
       float col[3] = {1.0f, 1.0f, 1.0f};
-      const float cw = (float)c4.w;
+      const float cw = (float)(uint16_t)(c4 >> 48);
       if (cw > 0.0f) {
-        col[0] = ((float)c4.x / 255.0f) / cw;
-        col[1] = ((float)c4.y / 255.0f) / cw;
-        col[2] = ((float)c4.z / 255.0f) / cw;
+        col[0] = ((float)(uint16_t)c4 / 255.0f) / cw;
+        col[1] = ((float)(uint16_t)(c4 >> 16) / 255.0f) / cw;
+        col[2] = ((float)(uint16_t)(c4 >> 32) / 255.0f) / cw;
       }
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
