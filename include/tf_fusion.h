@@ -705,6 +705,46 @@ TF_API int tf_align_color_residuals_device(tf_volume* v, const float* d_depth, c
                                            const tf_align_color_params* params, float* d_r, float* d_grad3, float* d_rc,
                                            float* d_gradc3, uint32_t* d_flags);
 
+/* ---- a keyframe group aligned in one call (tf_align_group.hip) -----------------------------
+ * OptimizeKeyframeVoxelDomain (GCFusion/MobileFusion.cpp:322) for the unit ReIntegrateKeyframe integrates: a keyframe and
+ * its up to six local frames, all of the readers' camera.  body[k] names the rigid body frame k belongs to (NULL: all
+ * frames are body 0); bodies are numbered by first appearance (body[0] == 0, body[k] <= 1 + max(body[0..k-1])) and a
+ * body's anchor is its first frame.  Every body has its own 6 x 6 system, its own twist per step and its own stops, by
+ * tf_align_frame's rules exactly (min_valid goes by the body's total n_valid); one body stopping does not stop the others.
+ * A frame's rows are tf_align_frame's, except that the twist of a body is taken about its anchor's camera centre: a
+ * later frame's Jacobian is [g, ((t_k - t_anchor) + R_k pc) x g].  A body's sums are its frames' sums (each formed as
+ * tf_align_frame forms them) added in ascending frame order; a step moves every frame of the body by the same rigid
+ * motion, R_k <- E R_k, t_k <- c + E (t_k - c) + v with c the anchor's centre before the step.  A body of one frame has
+ * tf_align_frame's result and log bit for bit.  A call is 1 + 2 launches per evaluation, as tf_align_frame, whatever
+ * the number of frames.  Read-only; its state and log are its own: tf_align_log and tf_align_color_log keep their meaning.
+ * Not here: a photometric row, more than seven frames, frames of different cameras, multi-rank alignment.
+ * TF_ERR_INVALID (nothing launched, the result untouched) for what tf_align_frame rejects, for any frame; n_frames
+ * outside 1..7; a null image pointer; a body array that breaks the numbering rule; a null result. */
+#define TF_ALIGN_GROUP_MAX_FRAMES 7   /* a keyframe and six local frames: tf_unit_group */
+typedef struct tf_align_group_result {
+  int32_t n_frames, n_bodies;
+  tf_align_result body[TF_ALIGN_GROUP_MAX_FRAMES];   /* one per body; .pose = the body's anchor frame; n_sampled, n_valid_*: summed over its frames */
+  float pose[TF_ALIGN_GROUP_MAX_FRAMES][12];         /* every frame's pose at the end */
+  int32_t frame_valid_first[TF_ALIGN_GROUP_MAX_FRAMES], frame_valid_last[TF_ALIGN_GROUP_MAX_FRAMES];  /* per frame: valid pixels of its body's first / last evaluation */
+} tf_align_group_result;
+/* d_depth / depth: host arrays of n_frames image pointers (device images for _device, host images for the other form);
+ * poses12: n_frames x 12 floats.  _device: device result, asynchronous on the handle's stream, every launch enqueued up
+ * front, nothing read back.  tf_align_group stages the images through the handle's scratch pool and waits once, for the
+ * result.  Entries of the result past n_bodies / n_frames are zero. */
+TF_API int tf_align_group_device(tf_volume* v, int32_t n_frames, const float* const* d_depth, const float* poses12,
+                                 const int32_t* body, const tf_align_params* params, tf_align_group_result* d_result);
+TF_API int tf_align_group(tf_volume* v, int32_t n_frames, const float* const* depth, const float* poses12,
+                          const int32_t* body, const tf_align_params* params, tf_align_group_result* result);
+/* the records of body `body` (0..6) of the handle's last group call (waits for it), as tf_align_log; a record's pose is
+ * the anchor's; a body that call did not have has no records */
+TF_API int tf_align_group_log(tf_volume* v, int32_t body, tf_align_iter* out, int64_t cap, int64_t* n);
+/* The same for the struct tf_keyframe_unit_device takes: frame 0 is group->keyframe, frames 1 + i are group->local[i]
+ * (i < n_local), the images are the struct's device depth pointers.  rigid != 0: one body; otherwise every frame is its
+ * own.  Waits once, then writes the aligned pose into the pose field of every frame whose body ended with status <=
+ * TF_ALIGN_MAX_ITERS; the other frames and old_* stay as they are. */
+TF_API int tf_align_unit_group(tf_volume* v, tf_unit_group* group, int rigid, const tf_align_params* params,
+                               tf_align_group_result* result);
+
 /* ---- meshing (the stage between the volume and the atlas) -----
  * Chisel::UpdateMeshes (Structure/Chisel.h:479-481) -> ChunkManager::RecomputeMeshes
  *   (Structure/ChunkManager.cpp:232-264): every chunk of meshesToUpdate that exists is re-meshed by

@@ -57,6 +57,7 @@ SYMBOLS = (
     "tf_align_residuals_device",
     "tf_align_color_default_params", "tf_align_frame_color", "tf_align_frame_color_device", "tf_align_color_log",
     "tf_align_color_residuals", "tf_align_color_residuals_device",
+    "tf_align_group", "tf_align_group_device", "tf_align_group_log", "tf_align_unit_group",
     "tf_texmap_set_keyframes", "tf_texmap_update", "tf_texmap_retract", "tf_texmap_remove_wrong_mapping",
     "tf_texmap_check_graph", "tf_texmap_view_selection", "tf_texmap_download", "tf_texmap_download_problem",
     "tf_texmap_clear", "tf_generate_patches_selected", "tf_texture_tail_device", "tf_texture_tail_list",
@@ -65,6 +66,7 @@ SYMBOLS = (
 # tf_align_result.status
 TF_ALIGN_CONVERGED, TF_ALIGN_MAX_ITERS, TF_ALIGN_TOO_FEW, TF_ALIGN_SINGULAR = 0, 1, 2, 3
 TF_ALIGN_MAX_EVALUATIONS = 65
+TF_ALIGN_GROUP_MAX_FRAMES = 7
 
 # tf_query_points want_mask bits
 Q_SDF, Q_WEIGHT, Q_GRAD, Q_SDF_TRI, Q_RGB_TRI = 1, 2, 4, 8, 16
@@ -182,6 +184,13 @@ def AlignColorParams(**kw):
             setattr(p, k, float(kw.pop(k)))
     p.geo = AlignParams(**kw)
     return p
+
+
+class AlignGroupResult(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("n_bodies", C.c_int32), ("body", AlignResult * TF_ALIGN_GROUP_MAX_FRAMES),
+                ("pose", (C.c_float * 12) * TF_ALIGN_GROUP_MAX_FRAMES),
+                ("frame_valid_first", C.c_int32 * TF_ALIGN_GROUP_MAX_FRAMES),
+                ("frame_valid_last", C.c_int32 * TF_ALIGN_GROUP_MAX_FRAMES)]
 
 
 class Profile(C.Structure):
@@ -352,6 +361,10 @@ def lib():
     L.tf_align_color_log.argtypes = [vp, C.POINTER(AlignColorIter), C.c_int64, i64p]
     L.tf_align_color_residuals.argtypes = [vp, fp, C.POINTER(C.c_uint8), fp, acp, fp, fp, fp, fp, C.POINTER(C.c_uint32)]
     L.tf_align_color_residuals_device.argtypes = [vp, vp, vp, fp, acp, vp, vp, vp, vp, vp]
+    L.tf_align_group.argtypes = [vp, C.c_int32, C.POINTER(vp), fp, i32p, app, C.POINTER(AlignGroupResult)]
+    L.tf_align_group_device.argtypes = [vp, C.c_int32, C.POINTER(vp), fp, i32p, app, vp]
+    L.tf_align_group_log.argtypes = [vp, C.c_int32, C.POINTER(AlignIter), C.c_int64, i64p]
+    L.tf_align_unit_group.argtypes = [vp, C.POINTER(UnitGroup), C.c_int, app, C.POINTER(AlignGroupResult)]
     L.tf_view_select.argtypes = [vp, C.c_int64, i32p, i32p, i64p, i32p, fp, C.c_float, i32p, C.c_int32, i32p,
                                  C.POINTER(C.c_double), i32p]
     L.tf_view_select_device.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_float, vp, C.c_int32, vp, vp, vp]
@@ -990,6 +1003,75 @@ class Volume:
         self._ck(self.L.tf_align_color_residuals_device(self.h, d_depth or None, d_rgba or None, _p(pose, C.c_float),
                                                         C.byref(params), d_r or None, d_grad or None, d_rc or None,
                                                         d_gradc or None, d_flags or None))
+
+    # -- a keyframe group aligned in one call (tf_align_group_*; read-only)
+    @staticmethod
+    def _align_group_args(poses, body):
+        poses = np.ascontiguousarray(_f32(poses).reshape(-1, 12))
+        b = None if body is None else np.ascontiguousarray(body, np.int32).reshape(-1)
+        if b is not None and len(b) != len(poses):
+            raise TFError(TF_ERR_INVALID, "body needs one entry per frame")
+        return poses, b
+
+    def align_group(self, depths, poses, body=None, params=None):
+        """Up to seven depth images [H, W] of the readers' camera aligned in one call; body[k] = the rigid body of frame k
+        (None: one body).  -> align_group_result's dict."""
+        ds = [self._align_depth(d)[0] for d in depths]
+        poses, b = self._align_group_args(poses, body)
+        if len(ds) != len(poses):
+            raise TFError(TF_ERR_INVALID, "one pose per depth image")
+        params = params or AlignParams()
+        ptrs = (C.c_void_p * max(1, len(ds)))(*[d.ctypes.data for d in ds])
+        res = AlignGroupResult()
+        self._ck(self.L.tf_align_group(self.h, len(ds), ptrs, _p(poses, C.c_float), _p(b, C.c_int32), C.byref(params),
+                                       C.byref(res)))
+        return self.align_group_result(res)
+
+    @staticmethod
+    def align_group_result(res):
+        """an AlignGroupResult (or its bytes as read back from the device) as a dict: n_frames, n_bodies, body = a list of
+        align_result's dicts (one per body), pose [n_frames, 3, 4] f32, frame_valid_first / _last [n_frames]"""
+        if not isinstance(res, AlignGroupResult):
+            res = AlignGroupResult.from_buffer_copy(bytes(bytearray(res)))
+        n = res.n_frames
+        return dict(n_frames=n, n_bodies=res.n_bodies, body=[Volume.align_result(res.body[i]) for i in range(res.n_bodies)],
+                    pose=np.array(res.pose, np.float32).reshape(TF_ALIGN_GROUP_MAX_FRAMES, 3, 4)[:n],
+                    frame_valid_first=np.array(res.frame_valid_first, np.int32)[:n],
+                    frame_valid_last=np.array(res.frame_valid_last, np.int32)[:n])
+
+    def align_group_device(self, d_depths, poses, body, params, d_result):
+        """Asynchronous on the handle's stream: device depth images (a list of pointers), the tf_align_group_result written
+        to d_result"""
+        poses, b = self._align_group_args(poses, body)
+        ptrs = (C.c_void_p * max(1, len(d_depths)))(*[p or None for p in d_depths])
+        self._ck(self.L.tf_align_group_device(self.h, len(d_depths), ptrs, _p(poses, C.c_float), _p(b, C.c_int32),
+                                              C.byref(params), d_result or None))
+
+    def align_group_log(self, body=0):
+        """The records of one body of the last align_group / align_group_device / align_unit_group: align_log's dicts; a
+        record's pose is the body's anchor frame's."""
+        n = C.c_int64(0)
+        buf = (AlignIter * TF_ALIGN_MAX_EVALUATIONS)()
+        self._ck(self.L.tf_align_group_log(self.h, int(body), buf, TF_ALIGN_MAX_EVALUATIONS, C.byref(n)))
+        return [self._align_iter(buf[k]) for k in range(min(n.value, TF_ALIGN_MAX_EVALUATIONS))]
+
+    @staticmethod
+    def _align_iter(it):
+        A21 = np.array(it.A, np.float64)
+        A = np.zeros((6, 6), np.float64)
+        A[np.triu_indices(6)] = A21
+        A = A + np.triu(A, 1).T
+        return dict(level=it.level, stride=it.stride, n_sampled=it.n_sampled, n_valid=it.n_valid, sum_r2=it.sum_r2,
+                    sum_wr2=it.sum_wr2, A=A, A21=A21, b=np.array(it.b, np.float64), xi=np.array(it.xi, np.float64),
+                    pose=np.array(it.pose, np.float64).reshape(3, 4))
+
+    def align_unit_group(self, group, rigid=True, params=None):
+        """OptimizeKeyframeVoxelDomain for a UnitGroup (unit_group): its frames aligned as one rigid body, or each on its
+        own, and the aligned poses written into the group where the body ended well.  -> align_group_result's dict."""
+        params = params or AlignParams()
+        res = AlignGroupResult()
+        self._ck(self.L.tf_align_unit_group(self.h, C.byref(group), int(bool(rigid)), C.byref(params), C.byref(res)))
+        return self.align_group_result(res)
 
     # -- view selection (the solve of TexMap::view_selection)
     def view_select(self, ids, nbr, col_off, labels, costs, edge_cost=0.5, init=None, max_rounds=0, out=None):

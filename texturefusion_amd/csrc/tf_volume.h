@@ -191,6 +191,11 @@ struct AlignColorState {
   DevMem block;
   size_t cap_tiles = 0;
 };
+// The group alignment's own block (tf_align_group.hip): the same for seven frames and seven bodies, and a result
+struct AlignGroupState {
+  DevMem block;
+  size_t cap_tiles = 0;
+};
 
 // The model's DrawMeshes stream, resident in the handle (tf_model.hip): packed on the device, counts in device words,
 // kept until the model changes.  Everything is empty until first use; `ModelState{}` gives it all back.
@@ -300,6 +305,7 @@ struct tf_volume {
   tf::CcState cc;
   tf::AlignState align;
   tf::AlignColorState align_color;
+  tf::AlignGroupState align_group;
   tf::ModelState model;
   uint64_t model_gen = 0;  // advanced by every entry point that is not a whitelisted reader (TF_DEV_READER)
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
@@ -410,6 +416,7 @@ AlignCam align_cam(const tf_volume* v);
 bool finite_all(const float* p, int n);
 int align_check(tf_volume* v, const float* depth, const float* pose, const tf_align_params* p, bool with_iters);
 void align_color_release(tf_volume* v);
+void align_group_release(tf_volume* v);  // frees tf_align_group.hip's state block
 // the resident model stream (tf_model.hip).  model_pack_enqueue: list, rank, scan and write on the handle's stream, nothing
 // read back (the buffers exist and have a capacity); model_stream_sync: the pack, one wait for the control block, the
 // buffers grown and the pack repeated on overflow -- ModelState::nv / ni are the counts afterwards; model_release frees all

@@ -884,6 +884,56 @@ class Chisel {
     log.resize((size_t)n);
     return log;
   }
+  // AlignFrameToModel for a keyframe group in one call (tf_align_group): up to seven host depth images of the readers'
+  // camera with their approximate poses; body[k] names the rigid body frame k belongs to (empty: all frames are one body;
+  // bodies are numbered by first appearance, a body's anchor is its first frame).  A body moves as one: a frame that
+  // faces a single plane is held by what the other frames of its body see.  params == nullptr: the library's defaults.
+  // Returns the largest status over the bodies; result->pose[k] is frame k's aligned pose, result->body[b] body b's result.
+  int AlignGroupToModel(const std::vector<const float*>& depthImages, const std::vector<Transform>& depthExtrinsics,
+                        const std::vector<int32_t>& body, const tf_align_params* params, tf_align_group_result* result) {
+    tf_align_params def;
+    if (!params) {
+      tf_check(tf_align_default_params(&def), "AlignGroupToModel");
+      params = &def;
+    }
+    if (depthImages.size() != depthExtrinsics.size() || (!body.empty() && body.size() != depthImages.size()))
+      throw std::runtime_error("AlignGroupToModel: one pose (and one body entry) per depth image");
+    std::vector<float> poses(12 * depthExtrinsics.size());
+    for (size_t k = 0; k < depthExtrinsics.size(); ++k) std::memcpy(&poses[12 * k], depthExtrinsics[k].data(), 12 * sizeof(float));
+    tf_check(tf_align_group(vol, (int32_t)depthImages.size(), depthImages.data(), poses.data(), body.empty() ? nullptr : body.data(),
+                            params, result), "AlignGroupToModel");
+    int worst = 0;
+    for (int b = 0; b < result->n_bodies; ++b) worst = result->body[b].status > worst ? result->body[b].status : worst;
+    return worst;
+  }
+  // Every record of one body of the last group call (AlignLog and AlignColorLog keep their meaning); a record's pose is
+  // the body's anchor frame's.
+  std::vector<tf_align_iter> AlignGroupLog(int32_t body) {
+    std::vector<tf_align_iter> log(TF_ALIGN_MAX_EVALUATIONS);
+    int64_t n = 0;
+    tf_check(tf_align_group_log(vol, body, log.data(), (int64_t)log.size(), &n), "AlignGroupLog");
+    log.resize((size_t)n);
+    return log;
+  }
+  // GCFusion/MobileFusion.cpp:322, for the struct the keyframe unit takes (tf_align_unit_group): the group's device depth
+  // images aligned at the group's poses -- rigid: the keyframe and its local frames as one body (the reference keeps local
+  // frames by their pose relative to the keyframe); otherwise every frame on its own -- and the aligned poses written
+  // into group.keyframe.pose / group.local[i].pose where the body ended TF_ALIGN_CONVERGED or TF_ALIGN_MAX_ITERS, ready
+  // for tf_keyframe_unit_device.  Returns the largest status over the bodies.
+  int OptimizeKeyframeVoxelDomain(tf_unit_group& group, bool rigid, const tf_align_params* params = nullptr,
+                                  tf_align_group_result* result = nullptr) {
+    tf_align_params def;
+    if (!params) {
+      tf_check(tf_align_default_params(&def), "OptimizeKeyframeVoxelDomain");
+      params = &def;
+    }
+    tf_align_group_result own;
+    if (!result) result = &own;
+    tf_check(tf_align_unit_group(vol, &group, rigid ? 1 : 0, params, result), "OptimizeKeyframeVoxelDomain");
+    int worst = 0;
+    for (int b = 0; b < result->n_bodies; ++b) worst = result->body[b].status > worst ? result->body[b].status : worst;
+    return worst;
+  }
 
   // Structure/Chisel.h:103-140.  depthImage is borrowed for the call (uploaded to HBM and kept
   // bound for the IntegrateDepthScanColor calls that follow, like the reference keeps the cv::Mat).
