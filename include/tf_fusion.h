@@ -745,6 +745,67 @@ TF_API int tf_align_group_log(tf_volume* v, int32_t body, tf_align_iter* out, in
 TF_API int tf_align_unit_group(tf_volume* v, tf_unit_group* group, int rigid, const tf_align_params* params,
                                tf_align_group_result* result);
 
+/* ---- tracking a frame from far off: projective ICP against the raycast model (tf_align_icp.hip) ---
+ * tf_align_frame samples the SDF at the frame's points, so it only captures a start within the truncation band (a couple
+ * of centimetres).  This is KinectFusion's projective point-to-plane ICP against the model's vertex and normal maps, as
+ * tf_raycast_device writes them (f32 planar [3][H][W], world frame, normal 0 on a miss), of the same camera as the depth
+ * image and rendered from model_pose: a pixel needs only to project onto a model pixel whose point lies within
+ * max_distance.  Per sampled pixel: pw as tf_align_frame's (flag bit 0: depth in range); pm = Rm^T (pw - tm), the model
+ * pixel (u, v) = floor(f * pm.xy / pm.z + (c + 0.5) + 0.5), the one whose raycast ray is the nearest (bit 1: pm.z > min_depth
+ * and (u, v) inside the image); vm, nm the maps there (bit 2: |nm|^2 > 0.5, a hit); e = pw - vm, r = nm . e (bit 3: |e|^2 <= max_distance^2
+ * and |r| <= geo.max_residual).  Each bit is set only where the lower ones are; a pixel is valid when flags == 15.
+ * Jacobian [nm, (R pc) x nm]: tf_align_frame's twist about the camera centre.  Huber weight, sums and their order, the
+ * solve, the pose update, levels, stops, statuses, the closing evaluation, tf_align_result and tf_align_iter are
+ * tf_align_frame's; a plane alone still ends TF_ALIGN_SINGULAR.  The order of operations is fixed in tf_align_icp.hip
+ * and restated in tests/align_icp_ref.py.  The maps and the model pose do not change during a call; re-rendering between
+ * levels is the caller's choice, through a second call.  A call is 1 + 2 launches per evaluation, all enqueued up front.
+ * Read-only; its state and log are its own: tf_align_log, tf_align_color_log and tf_align_group_log keep their meaning.
+ * Not here: frame normals and a normal-compatibility gate, a photometric row, a group form, multi-rank. */
+typedef struct tf_align_icp_params {
+  tf_align_params geo;     /* levels, depth range, huber, damping, eps, min_valid; max_residual gates |r| */
+  float max_distance;      /* gate on |pw - vm| */
+  float ray_near, ray_far; int32_t ray_max_steps;   /* for the forms that raycast themselves */
+} tf_align_icp_params;
+typedef struct tf_track_result {
+  tf_align_result icp, sdf;   /* sdf.status == -1 (the rest 0): the SDF stage was not run */
+  int32_t stage;              /* 0 none usable, 1 icp only, 2 sdf */
+  float pose[12];
+} tf_track_result;
+/* strides {4, 2, 1}, iters {6, 4, 3}, depth in [0.05, 5], max_distance 0.15, max_residual 0.15 (not binding: |r| <= |e|),
+ * huber 0.02, damping 0, eps 1e-5 / 1e-5, min_valid 100, ray 0.05 / 5 / 1024 */
+TF_API int tf_align_icp_default_params(tf_align_icp_params* out);
+/* TF_ERR_INVALID (nothing launched, the result untouched) for what tf_align_frame rejects; a negative or non-finite
+ * max_distance; a null map or result pointer; a non-finite model pose entry; in the forms that raycast themselves, ray
+ * parameters tf_raycast rejects.
+ * _device: everything in device memory (model_pose on the host, not NULL), asynchronous on the handle's stream, nothing
+ * read back.  tf_align_frame_icp: host depth image staged through the scratch pool; the model is raycast at model_pose
+ * (NULL: at pose) by tf_raycast_device's launch into maps the handle owns; it waits once, for the result. */
+TF_API int tf_align_frame_icp_device(tf_volume* v, const float* d_depth, const float pose[12], const float* d_model_vertex,
+                                     const float* d_model_normal, const float model_pose[12],
+                                     const tf_align_icp_params* params, tf_align_result* d_result);
+TF_API int tf_align_frame_icp(tf_volume* v, const float* depth, const float pose[12], const float* model_pose,
+                              const tf_align_icp_params* params, tf_align_result* result);
+/* the records of the last tf_align_frame_icp(_device) or tf_track_frame call of this handle (waits for it), as tf_align_log */
+TF_API int tf_align_icp_log(tf_volume* v, tf_align_iter* out, int64_t cap, int64_t* n);
+/* The maps of one evaluation at geo.stride[0] (iters are not read): r f32[H][W] (where bits 0 to 2 are set, else 0), flags
+ * u32[H][W], assoc i32[H][W] = v * W + u of the associated model pixel where bit 1 is set, else -1; any may be NULL;
+ * pixels not sampled get 0, 0 and -1.  The host form takes host maps, or raycasts the model at model_pose (NULL: at pose)
+ * where model_vertex and model_normal are both NULL. */
+TF_API int tf_align_icp_residuals(tf_volume* v, const float* depth, const float pose[12], const float* model_vertex,
+                                  const float* model_normal, const float* model_pose, const tf_align_icp_params* params,
+                                  float* r, uint32_t* flags, int32_t* assoc);
+TF_API int tf_align_icp_residuals_device(tf_volume* v, const float* d_depth, const float pose[12],
+                                         const float* d_model_vertex, const float* d_model_normal,
+                                         const float model_pose[12], const tf_align_icp_params* params, float* d_r,
+                                         uint32_t* d_flags, int32_t* d_assoc);
+/* The coarse-to-fine tracker in one call: tf_align_frame_icp with the model raycast at the start pose; where that ends
+ * with status <= TF_ALIGN_MAX_ITERS, tf_align_frame from the ICP's pose.  out->pose is the SDF stage's pose where its
+ * status <= TF_ALIGN_MAX_ITERS (stage 2), otherwise the ICP's where the ICP's was (stage 1), otherwise the caller's
+ * (stage 0).  It waits twice, once per stage: chaining the stages on the device would need tf_align_frame_device to
+ * start from a device pose.  TF_ERR_INVALID (nothing launched, out untouched) for what either stage rejects. */
+TF_API int tf_track_frame(tf_volume* v, const float* depth, const float pose[12], const tf_align_icp_params* icp_params,
+                          const tf_align_params* sdf_params, tf_track_result* out);
+
 /* ---- meshing (the stage between the volume and the atlas) -----
  * Chisel::UpdateMeshes (Structure/Chisel.h:479-481) -> ChunkManager::RecomputeMeshes
  *   (Structure/ChunkManager.cpp:232-264): every chunk of meshesToUpdate that exists is re-meshed by

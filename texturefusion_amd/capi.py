@@ -58,6 +58,8 @@ SYMBOLS = (
     "tf_align_color_default_params", "tf_align_frame_color", "tf_align_frame_color_device", "tf_align_color_log",
     "tf_align_color_residuals", "tf_align_color_residuals_device",
     "tf_align_group", "tf_align_group_device", "tf_align_group_log", "tf_align_unit_group",
+    "tf_align_icp_default_params", "tf_align_frame_icp", "tf_align_frame_icp_device", "tf_align_icp_log",
+    "tf_align_icp_residuals", "tf_align_icp_residuals_device", "tf_track_frame",
     "tf_texmap_set_keyframes", "tf_texmap_update", "tf_texmap_retract", "tf_texmap_remove_wrong_mapping",
     "tf_texmap_check_graph", "tf_texmap_view_selection", "tf_texmap_download", "tf_texmap_download_problem",
     "tf_texmap_clear", "tf_generate_patches_selected", "tf_texture_tail_device", "tf_texture_tail_list",
@@ -191,6 +193,45 @@ class AlignGroupResult(C.Structure):
                 ("pose", (C.c_float * 12) * TF_ALIGN_GROUP_MAX_FRAMES),
                 ("frame_valid_first", C.c_int32 * TF_ALIGN_GROUP_MAX_FRAMES),
                 ("frame_valid_last", C.c_int32 * TF_ALIGN_GROUP_MAX_FRAMES)]
+
+
+class AlignIcpParamsC(C.Structure):
+    _fields_ = [("geo", AlignParamsC), ("max_distance", C.c_float), ("ray_near", C.c_float), ("ray_far", C.c_float),
+                ("ray_max_steps", C.c_int32)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("icp", AlignResult), ("sdf", AlignResult), ("stage", C.c_int32), ("pose", C.c_float * 12)]
+
+
+def AlignIcpParams(**kw):
+    """tf_align_icp_params: the library's defaults (tf_align_icp_default_params) with fields replaced by keyword;
+    max_distance, ray_near, ray_far and ray_max_steps are its own, every other keyword is AlignParams' and goes to .geo."""
+    p = AlignIcpParamsC()
+    rc = lib().tf_align_icp_default_params(C.byref(p))
+    if rc != TF_OK:
+        raise TFError(rc, lib().tf_last_error().decode())
+    for k in ("max_distance", "ray_near", "ray_far"):
+        if k in kw:
+            setattr(p, k, float(kw.pop(k)))
+    if "ray_max_steps" in kw:
+        p.ray_max_steps = int(kw.pop("ray_max_steps"))
+    levels = kw.pop("levels", None)
+    if levels is not None:
+        p.geo.n_levels = len(levels)
+        for i, (st, it) in enumerate(levels[:4]):
+            p.geo.stride[i], p.geo.iters[i] = int(st), int(it)
+    for k, val in kw.items():
+        if k in ("stride", "iters"):
+            for i, x in enumerate(val):
+                getattr(p.geo, k)[i] = int(x)
+        elif k in ("n_levels", "min_valid"):
+            setattr(p.geo, k, int(val))
+        elif any(k == f[0] for f in AlignParamsC._fields_):
+            setattr(p.geo, k, float(val))
+        else:
+            raise TypeError("tf_align_icp_params has no field %r" % k)
+    return p
 
 
 class Profile(C.Structure):
@@ -365,6 +406,14 @@ def lib():
     L.tf_align_group_device.argtypes = [vp, C.c_int32, C.POINTER(vp), fp, i32p, app, vp]
     L.tf_align_group_log.argtypes = [vp, C.c_int32, C.POINTER(AlignIter), C.c_int64, i64p]
     L.tf_align_unit_group.argtypes = [vp, C.POINTER(UnitGroup), C.c_int, app, C.POINTER(AlignGroupResult)]
+    aip = C.POINTER(AlignIcpParamsC)
+    L.tf_align_icp_default_params.argtypes = [aip]
+    L.tf_align_frame_icp.argtypes = [vp, fp, fp, fp, aip, C.POINTER(AlignResult)]
+    L.tf_align_frame_icp_device.argtypes = [vp, vp, fp, vp, vp, fp, aip, vp]
+    L.tf_align_icp_log.argtypes = [vp, C.POINTER(AlignIter), C.c_int64, i64p]
+    L.tf_align_icp_residuals.argtypes = [vp, fp, fp, fp, fp, fp, aip, fp, C.POINTER(C.c_uint32), i32p]
+    L.tf_align_icp_residuals_device.argtypes = [vp, vp, fp, vp, vp, fp, aip, vp, vp, vp]
+    L.tf_track_frame.argtypes = [vp, fp, fp, aip, app, C.POINTER(TrackResult)]
     L.tf_view_select.argtypes = [vp, C.c_int64, i32p, i32p, i64p, i32p, fp, C.c_float, i32p, C.c_int32, i32p,
                                  C.POINTER(C.c_double), i32p]
     L.tf_view_select_device.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_float, vp, C.c_int32, vp, vp, vp]
@@ -1072,6 +1121,76 @@ class Volume:
         res = AlignGroupResult()
         self._ck(self.L.tf_align_unit_group(self.h, C.byref(group), int(bool(rigid)), C.byref(params), C.byref(res)))
         return self.align_group_result(res)
+
+    # -- tracking from far off: projective ICP against the raycast model (tf_align_icp_*, tf_track_frame; read-only)
+    def align_frame_icp(self, depth, pose, model_pose=None, params=None):
+        """Projective point-to-plane ICP of the depth image [H, W] against the model raycast at model_pose (None: at pose)
+        -> align_frame's dict."""
+        d, _, _ = self._align_depth(depth)
+        pose = _f32(pose).reshape(12)
+        mp = None if model_pose is None else _p(_f32(model_pose).reshape(12), C.c_float)
+        params = params or AlignIcpParams()
+        res = AlignResult()
+        self._ck(self.L.tf_align_frame_icp(self.h, _p(d, C.c_float), _p(pose, C.c_float), mp, C.byref(params), C.byref(res)))
+        return self.align_result(res)
+
+    def align_frame_icp_device(self, d_depth, pose, d_vertex, d_normal, model_pose, params, d_result):
+        """Asynchronous on the handle's stream: device depth image and device model maps (planar [3][H][W], as
+        raycast_device writes them, rendered from model_pose), the tf_align_result written to d_result"""
+        pose = _f32(pose).reshape(12)
+        mp = None if model_pose is None else _p(_f32(model_pose).reshape(12), C.c_float)
+        self._ck(self.L.tf_align_frame_icp_device(self.h, d_depth or None, _p(pose, C.c_float), d_vertex or None,
+                                                  d_normal or None, mp, C.byref(params), d_result or None))
+
+    def align_icp_log(self):
+        """The records of the last align_frame_icp(_device) or track_frame: align_log's dicts"""
+        n = C.c_int64(0)
+        buf = (AlignIter * TF_ALIGN_MAX_EVALUATIONS)()
+        self._ck(self.L.tf_align_icp_log(self.h, buf, TF_ALIGN_MAX_EVALUATIONS, C.byref(n)))
+        return [self._align_iter(buf[k]) for k in range(min(n.value, TF_ALIGN_MAX_EVALUATIONS))]
+
+    def align_icp_residuals(self, depth, pose, model_pose=None, params=None, vertex=None, normal=None):
+        """The maps of one ICP evaluation at params.geo.stride[0] -> dict(r [H, W] f32, flags [H, W] u32, assoc [H, W] i32;
+        a pixel is valid where flags == 15).  vertex, normal: host model maps [3, H, W] f32 rendered from model_pose; both
+        None: the model is raycast at model_pose (None: at pose)."""
+        d, H, W = self._align_depth(depth)
+        pose = _f32(pose).reshape(12)
+        mp = None if model_pose is None else _p(_f32(model_pose).reshape(12), C.c_float)
+        maps = []
+        for m in (vertex, normal):
+            if m is not None:
+                m = _f32(m)
+                if m.size != 3 * W * H:
+                    raise TFError(TF_ERR_INVALID, "a model map needs 3x%dx%d values" % (H, W))
+            maps.append(m)
+        params = params or AlignIcpParams()
+        out = {"r": np.zeros((H, W), np.float32), "flags": np.zeros((H, W), np.uint32), "assoc": np.zeros((H, W), np.int32)}
+        self._ck(self.L.tf_align_icp_residuals(self.h, _p(d, C.c_float), _p(pose, C.c_float),
+                                               None if maps[0] is None else _p(maps[0], C.c_float),
+                                               None if maps[1] is None else _p(maps[1], C.c_float), mp, C.byref(params),
+                                               _p(out["r"], C.c_float), _p(out["flags"], C.c_uint32),
+                                               _p(out["assoc"], C.c_int32)))
+        return out
+
+    def align_icp_residuals_device(self, d_depth, pose, d_vertex, d_normal, model_pose, params, d_r=0, d_flags=0, d_assoc=0):
+        pose = _f32(pose).reshape(12)
+        mp = None if model_pose is None else _p(_f32(model_pose).reshape(12), C.c_float)
+        self._ck(self.L.tf_align_icp_residuals_device(self.h, d_depth or None, _p(pose, C.c_float), d_vertex or None,
+                                                      d_normal or None, mp, C.byref(params), d_r or None, d_flags or None,
+                                                      d_assoc or None))
+
+    def track_frame(self, depth, pose, icp_params=None, sdf_params=None):
+        """The coarse-to-fine tracker: align_frame_icp with the model raycast at pose, then align_frame from its pose ->
+        dict(icp, sdf: align_frame's dicts (sdf["status"] == -1: not run), stage 0 / 1 / 2, pose [3, 4] f32)."""
+        d, _, _ = self._align_depth(depth)
+        pose = _f32(pose).reshape(12)
+        icp_params = icp_params or AlignIcpParams()
+        sdf_params = sdf_params or AlignParams()
+        res = TrackResult()
+        self._ck(self.L.tf_track_frame(self.h, _p(d, C.c_float), _p(pose, C.c_float), C.byref(icp_params),
+                                       C.byref(sdf_params), C.byref(res)))
+        return dict(icp=self.align_result(res.icp), sdf=self.align_result(res.sdf), stage=res.stage,
+                    pose=np.array(res.pose, np.float32).reshape(3, 4))
 
     # -- view selection (the solve of TexMap::view_selection)
     def view_select(self, ids, nbr, col_off, labels, costs, edge_cost=0.5, init=None, max_rounds=0, out=None):

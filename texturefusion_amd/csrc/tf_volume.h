@@ -196,6 +196,14 @@ struct AlignGroupState {
   DevMem block;
   size_t cap_tiles = 0;
 };
+// The projective ICP's own block (tf_align_icp.hip), laid out and owned as AlignState's, and the six planes of the model's
+// vertex and normal maps of the forms that raycast themselves (null until one of those is used)
+struct AlignIcpState {
+  DevMem block;
+  size_t cap_tiles = 0;
+  DevMem maps;
+  size_t map_pixels = 0;  // pixels each plane of `maps` has room for
+};
 
 // The model's DrawMeshes stream, resident in the handle (tf_model.hip): packed on the device, counts in device words,
 // kept until the model changes.  Everything is empty until first use; `ModelState{}` gives it all back.
@@ -306,6 +314,7 @@ struct tf_volume {
   tf::AlignState align;
   tf::AlignColorState align_color;
   tf::AlignGroupState align_group;
+  tf::AlignIcpState align_icp;
   tf::ModelState model;
   uint64_t model_gen = 0;  // advanced by every entry point that is not a whitelisted reader (TF_DEV_READER)
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
@@ -417,6 +426,7 @@ bool finite_all(const float* p, int n);
 int align_check(tf_volume* v, const float* depth, const float* pose, const tf_align_params* p, bool with_iters);
 void align_color_release(tf_volume* v);
 void align_group_release(tf_volume* v);  // frees tf_align_group.hip's state block
+void align_icp_release(tf_volume* v);    // frees tf_align_icp.hip's state block and its maps
 // the resident model stream (tf_model.hip).  model_pack_enqueue: list, rank, scan and write on the handle's stream, nothing
 // read back (the buffers exist and have a capacity); model_stream_sync: the pack, one wait for the control block, the
 // buffers grown and the pack repeated on overflow -- ModelState::nv / ni are the counts afterwards; model_release frees all

@@ -915,6 +915,47 @@ class Chisel {
     log.resize((size_t)n);
     return log;
   }
+  // AlignFrameToModel from far off (tf_align_frame_icp): projective point-to-plane ICP of depthImage against the model
+  // raycast at modelExtrinsic (nullptr: at depthExtrinsic).  It captures starts many centimetres and degrees away, where
+  // AlignFrameToModel finds no valid pixel; it does not polish as finely as the SDF does (TrackFrame runs both).
+  // params == nullptr: the library's defaults.  Returns result->status; result->pose is the aligned pose.
+  int AlignFrameToModelICP(const float* depthImage, const Transform& depthExtrinsic, const Transform* modelExtrinsic,
+                           const tf_align_icp_params* params, tf_align_result* result) {
+    tf_align_icp_params def;
+    if (!params) {
+      tf_check(tf_align_icp_default_params(&def), "AlignFrameToModelICP");
+      params = &def;
+    }
+    tf_check(tf_align_frame_icp(vol, depthImage, depthExtrinsic.data(), modelExtrinsic ? modelExtrinsic->data() : nullptr, params,
+                                result), "AlignFrameToModelICP");
+    return result->status;
+  }
+  // Every record of the last AlignFrameToModelICP or TrackFrame (the other logs keep their meaning).
+  std::vector<tf_align_iter> AlignIcpLog() {
+    std::vector<tf_align_iter> log(TF_ALIGN_MAX_EVALUATIONS);
+    int64_t n = 0;
+    tf_check(tf_align_icp_log(vol, log.data(), (int64_t)log.size(), &n), "AlignIcpLog");
+    log.resize((size_t)n);
+    return log;
+  }
+  // The tracker in one call (tf_track_frame): AlignFrameToModelICP with the model raycast at depthExtrinsic, then
+  // AlignFrameToModel from its pose.  nullptr parameters: the library's defaults.  Returns result->stage (0: neither stage
+  // usable, result->pose is depthExtrinsic; 1: the ICP's pose; 2: the SDF stage's pose).  It waits for the device twice.
+  int TrackFrame(const float* depthImage, const Transform& depthExtrinsic, const tf_align_icp_params* icpParams,
+                 const tf_align_params* sdfParams, tf_track_result* result) {
+    tf_align_icp_params idef;
+    tf_align_params sdef;
+    if (!icpParams) {
+      tf_check(tf_align_icp_default_params(&idef), "TrackFrame");
+      icpParams = &idef;
+    }
+    if (!sdfParams) {
+      tf_check(tf_align_default_params(&sdef), "TrackFrame");
+      sdfParams = &sdef;
+    }
+    tf_check(tf_track_frame(vol, depthImage, depthExtrinsic.data(), icpParams, sdfParams, result), "TrackFrame");
+    return result->stage;
+  }
   // GCFusion/MobileFusion.cpp:322, for the struct the keyframe unit takes (tf_align_unit_group): the group's device depth
   // images aligned at the group's poses -- rigid: the keyframe and its local frames as one body (the reference keeps local
   // frames by their pose relative to the keyframe); otherwise every frame on its own -- and the aligned poses written

@@ -1,0 +1,174 @@
+"""Device time of the projective ICP (tf_align_frame_icp_device) on the S-room, with tf_align_frame_device as the yardstick.
+
+S-room (640x480 @ 5 mm, 2^19-slot pool): one full orbit (the bench's pre-roll) is integrated, then one orbit depth image is
+tracked from a pose moved by 80 mm and turned by 5 degrees; the model maps are raycast once on the device at that start.
+Times are HIP events on the handle's stream around R back-to-back calls after W warm-up calls (enqueue only), or the
+host's clock around the forms that wait.  Reported:
+  us_per_evaluation[form][stride]  (a call of 8 steps - a call of none) / 8 at one level of that stride, eps 0: "icp" from the
+                                   far start, "frame" = tf_align_frame_device from a start 1 cm and 0.5 degrees away (the far
+                                   one is outside its capture range: it would stop at its first evaluation)
+  us_raycast_vertex_normal         one tf_raycast_device writing the two maps the ICP reads
+  us_icp_default_device            one tf_align_frame_icp_device call, default parameters, maps given
+  us_icp_default_host_wall         one tf_align_frame_icp call: upload, raycast, the ICP, one wait
+  us_track_frame_wall              one tf_track_frame call: the above, then tf_align_frame from the ICP's pose; two waits
+  what the calls did: status, evaluations, valid pixels, distance from the integration pose, cond(A) of the ICP's last
+  evaluation (a view of the plain yaw orbit sees one or two walls: the directions along a wall are not observed)
+One JSON line.  Needs the GPU; run it under a time limit:
+
+    timeout -k 10 900 python tools/align_icp_time.py [--orbit 200] [--reps 20]
+
+--counter-run N times nothing: it issues N one-evaluation ICP calls per stride (1, 2, 4), then N one-evaluation
+tf_align_frame_device calls per stride, and ends, for a run under a profiler (kernel durations of k_icp_rows, k_icp_solve
+and k_align_rows).
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from texturefusion_amd import capi, synth  # noqa: E402
+from align_time import _perturb  # noqa: E402
+from raycast_time import Hip, timed  # noqa: E402
+
+
+def _far(pose, metres, degrees):
+    """pose moved by `metres` along (0.6, 0.53, 0.6) and turned by `degrees` about (0.6, -0.64, 0.48), about the camera centre"""
+    t = np.array([0.6, 0.53, 0.6])
+    w = np.array([0.6, -0.64, 0.48])
+    t, w = metres * t / np.linalg.norm(t), np.radians(degrees) * w / np.linalg.norm(w)
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    th = np.linalg.norm(w)
+    E = np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * (K @ K)
+    P = np.asarray(pose, np.float64).reshape(3, 4).copy()
+    P[:, :3] = E @ P[:, :3]
+    P[:, 3] += t
+    return P.astype(np.float32)
+
+
+def _distance(a, b):
+    a, b = np.asarray(a, np.float64).reshape(3, 4), np.asarray(b, np.float64).reshape(3, 4)
+    R = a[:, :3] @ b[:, :3].T
+    return [float(np.linalg.norm(a[:, 3] - b[:, 3])), float(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1)))]
+
+
+def _wall(fn, warm, reps):
+    for _ in range(warm):
+        fn()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    return (time.perf_counter() - t0) / reps * 1e6
+
+
+def run(hip, orbit, reps, counter_run=0):
+    cam = synth.Camera()
+    res = np.float32(0.005)
+    pool = 1 << 19
+    stream = hip.stream()
+    vol = capi.Volume(res, cam, max_chunks=pool, max_list=1 << 18, mesh_blocks=pool // 4, stream=stream)
+    try:
+        first = orbit // 2
+        frame = None
+        for k in range(orbit):
+            d, rgba, _, pose = synth.room_frame(k, cam, with_quality=False)
+            vol.integrate_frame_host(d, rgba, pose.reshape(12), None, k)
+            if k == first:
+                frame = (d, pose)
+        vol.update_meshes()  # the neighbour table: the sampler reads it
+        vol.sync()
+        n_chunks = int(vol.stats().n_chunks)
+        P = cam.width * cam.height
+        depth, truth = frame
+        far = _far(truth, 0.080, 5.0)
+        near = _perturb(truth, np.random.default_rng(0))
+        d_depth, d_v, d_n = hip.malloc(4 * P), hip.malloc(12 * P), hip.malloc(12 * P)
+        hip.upload(d_depth, depth)
+        d_res = hip.malloc(C.sizeof(capi.AlignResult))
+        bufs = [d_depth, d_v, d_n, d_res]
+        icp_default = capi.AlignIcpParams()
+
+        def raycast():
+            vol.raycast_device(far, icp_default.ray_near, icp_default.ray_far, icp_default.ray_max_steps, d_normal=d_n, d_vertex=d_v)
+
+        def icp_call(params):
+            return lambda: vol.align_frame_icp_device(d_depth, far, d_v, d_n, far, params, d_res)
+
+        def frame_call(params):
+            return lambda: vol.align_frame_device(d_depth, near, params, d_res)
+
+        raycast()
+        if counter_run:
+            for stride in (1, 2, 4):
+                one = capi.AlignIcpParams(levels=[(stride, 0)])
+                for _ in range(counter_run):
+                    icp_call(one)()
+            for stride in (1, 2, 4):
+                one = capi.AlignParams(levels=[(stride, 0)])
+                for _ in range(counter_run):
+                    frame_call(one)()
+            vol.sync()
+            for p in bufs:
+                hip.h.hipFree(p)
+            return {"counter_run": counter_run, "n_chunks": n_chunks,
+                    "launch_order": "icp at strides 1, 2, 4, then tf_align_frame_device at strides 1, 2, 4; N calls each"}
+        per_eval = {"icp": {}, "frame": {}}
+        for stride in (1, 2, 4):
+            lv = dict(eps_t=0.0, eps_r=0.0)
+            per_eval["icp"][str(stride)] = round((timed(hip, stream, icp_call(capi.AlignIcpParams(levels=[(stride, 8)], **lv)), 3, reps) -
+                                                  timed(hip, stream, icp_call(capi.AlignIcpParams(levels=[(stride, 0)], **lv)), 3, reps)) / 8, 2)
+            per_eval["frame"][str(stride)] = round((timed(hip, stream, frame_call(capi.AlignParams(levels=[(stride, 8)], **lv)), 3, reps) -
+                                                    timed(hip, stream, frame_call(capi.AlignParams(levels=[(stride, 0)], **lv)), 3, reps)) / 8, 2)
+        us_ray = timed(hip, stream, raycast, 3, reps)
+        us_icp = timed(hip, stream, icp_call(icp_default), 3, reps)
+        vol.sync()
+        raw = np.empty(C.sizeof(capi.AlignResult), np.uint8)
+        hip.download(d_res, raw)
+        icp = vol.align_result(raw)
+        last = vol.align_icp_log()[-1]
+        us_host = _wall(lambda: vol.align_frame_icp(depth, far, None, icp_default), 2, reps)
+        us_track = _wall(lambda: vol.track_frame(depth, far), 2, reps)
+        trk = vol.track_frame(depth, far)
+        alone = vol.align_frame(depth, far)
+        for p in bufs:
+            hip.h.hipFree(p)
+        return {"scene": "room", "image": [cam.width, cam.height], "res_m": float(res), "orbit_frames": orbit, "frame": first,
+                "n_chunks": n_chunks, "start": "80 mm / 5 deg", "us_per_evaluation": per_eval,
+                "us_raycast_vertex_normal": round(us_ray, 1), "us_icp_default_device": round(us_icp, 1),
+                "us_icp_default_host_wall": round(us_host, 1), "us_track_frame_wall": round(us_track, 1),
+                "icp_status": icp["status"], "icp_evaluations": icp["evaluations"],
+                "icp_valid": [icp["n_valid_first"], icp["n_valid_last"], icp["n_sampled"]],
+                "icp_rms": [float(icp["rms_first"]), float(icp["rms_last"])], "icp_from_truth_m_rad": _distance(icp["pose"], truth),
+                "icp_cond_A_last": float(np.linalg.cond(last["A"])),
+                "track_stage": trk["stage"], "track_sdf_status": trk["sdf"]["status"],
+                "track_sdf_evaluations": trk["sdf"]["evaluations"], "track_from_truth_m_rad": _distance(trk["pose"], truth),
+                "align_frame_alone_status": alone["status"], "align_frame_alone_valid_first": alone["n_valid_first"],
+                "align_frame_alone_from_truth_m_rad": _distance(alone["pose"], truth),
+                "reps": reps}
+    finally:
+        vol.close()
+        hip.h.hipStreamDestroy(stream)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--orbit", type=int, default=200, help="frames integrated before timing (the bench's pre-roll)")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--counter-run", type=int, default=0, metavar="N",
+                    help="no timing: N one-evaluation calls per stride of the ICP, then of tf_align_frame_device, for a profiler")
+    args = ap.parse_args()
+    hip = Hip()
+    if capi.lib().tf_device_count() <= 0:
+        sys.exit("no HIP device: this tool measures the MI355X and has no CPU path")
+    print(json.dumps(run(hip, args.orbit, args.reps, args.counter_run)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
