@@ -806,6 +806,94 @@ TF_API int tf_align_icp_residuals_device(tf_volume* v, const float* d_depth, con
 TF_API int tf_track_frame(tf_volume* v, const float* depth, const float pose[12], const tf_align_icp_params* icp_params,
                           const tf_align_params* sdf_params, tf_track_result* out);
 
+/* ---- relocalising a lost camera against the cached keyframes (tf_reloc.hip) -------------------
+ * tf_track_frame needs a start within the ICP's capture range (about 12 cm / 8 degrees).  A caller that has none asks the
+ * keyframes the handle already holds (tf_keyframe_cache(_device), tf_keyframe_set_pose): which of them look like this
+ * frame (retrieval over small images, on the device), and does the tracker hold from one of their poses (verification,
+ * tf_track_frame as it is).
+ * Descriptor of an image of the integrator's camera (tf_set_camera, W x H): tiny_w x tiny_h blocks of bw x bh =
+ * (W / tiny_w) x (H / tiny_h) pixels, n = tiny_w * tiny_h, block i = by * tiny_w + bx.  All integers:
+ *   G[i] = sum over the block of 77 R + 150 G + 29 B (u32);  S = sum of G (u64)
+ *   a pixel counts where its depth z is finite and min_depth <= z <= max_depth; mm = (u32)rintf(z * 1000.0f), both f32;
+ *   c = pixels that count;  Z[i] = (sum of mm) / c (integer division) where 2 c >= bw bh, else -1 (i32)
+ * Score of a query q against a row k (texturefusion_amd/csrc/tf_reloc_score.h holds the f64 expressions):
+ *   D_i = G_i(q) - G_i(k);  N = n sum D_i^2 - (sum D_i)^2, an exact integer;  s_grey = N / (n^2 (256 bw bh)^2): the
+ *   zero-mean SSD in grey levels squared, unchanged exactly by a uniform brightness offset that saturates nowhere
+ *   m = blocks with Z >= 0 in both;  s_depth = sum over them of (Z_i(q) - Z_i(k))^2 / m * 1e-6 (metres squared)
+ *   score = grey_weight s_grey + depth_weight s_depth;  m < min_overlap: +inf, not a candidate
+ * Candidates are ranked by ascending score, then ascending kf_id.  The index lives in the handle.  A row is the image as it
+ * was when added: a caller who caches a keyframe again, or changes images it owns, adds it again.  A row whose keyframe
+ * has been released since, or has no pose (tf_keyframe_set_pose), is skipped by a query.  tf_volume_reset frees the index
+ * and its configuration.  Read-only on the volume, the atlas and the keyframe table.
+ * Not here: invariance to a rotation about the optical axis, features of any kind, a multi-rank form. */
+typedef struct tf_reloc_params {
+  int32_t tiny_w, tiny_h;          /* blocks across and down; W % tiny_w == 0 and H % tiny_h == 0 */
+  float min_depth, max_depth;      /* max_depth <= 60 */
+  float grey_weight, depth_weight; /* >= 0 */
+  int32_t min_overlap;             /* >= 0 */
+} tf_reloc_params;
+/* 40 x 30 blocks, depth in [0.05, 5], weights 1 and 2.55e4, min_overlap 300 (n / 4) */
+TF_API int tf_reloc_default_params(tf_reloc_params* out);
+/* Sets the descriptor and the score, and empties the index.  TF_ERR_INVALID where the grid does not divide the camera, a
+ * block holds more than 65536 pixels, a parameter is out of range or there is no camera.  The configuration belongs to the
+ * camera it was made for: after a tf_set_camera to another size every call below is refused until it is made again. */
+TF_API int tf_reloc_configure(tf_volume* v, const tf_reloc_params* params);
+/* Describes the named cached keyframes in one launch and puts them into the index; a keyframe that is there already gets
+ * its row replaced.  An id that is not cached: TF_ERR_INVALID, nothing changes.  Asynchronous. */
+TF_API int tf_reloc_index_add(tf_volume* v, const int32_t* kf_ids, int64_t n);
+/* ids that are not in the index are passed over */
+TF_API int tf_reloc_index_remove(tf_volume* v, const int32_t* kf_ids, int64_t n);
+TF_API int tf_reloc_index_clear(tf_volume* v);
+TF_API int tf_reloc_index_count(tf_volume* v, int64_t* n);
+/* The descriptor of host images (depth f32[H][W], rgb u8[H][W][rgb_pixel_stride], stride 3 or 4) -> G u32[n], Z i32[n], *S;
+ * and the row of an indexed keyframe (TF_ERR_INVALID where it is not in the index).  Both wait once. */
+TF_API int tf_reloc_describe(tf_volume* v, const float* depth, const uint8_t* rgb, int32_t rgb_pixel_stride, uint32_t* G,
+                             int32_t* Z, uint64_t* S);
+TF_API int tf_reloc_descriptor_download(tf_volume* v, int32_t kf_id, uint32_t* G, int32_t* Z, uint64_t* S);
+/* The candidates for a frame, ranked: *n = how many there are, the first min(*n, cap) written (any output may be NULL).
+ * One describe launch, one score launch over every row, one download of 12 bytes per row, one wait; the host ranks. */
+TF_API int tf_reloc_query(tf_volume* v, const float* depth, const uint8_t* rgb, int32_t rgb_pixel_stride,
+                          int32_t* out_kf_ids, double* out_scores, int32_t* out_overlap, int64_t cap, int64_t* n);
+TF_API int tf_reloc_query_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgb, int32_t rgb_pixel_stride,
+                                 int32_t* out_kf_ids, double* out_scores, int32_t* out_overlap, int64_t cap, int64_t* n);
+
+#define TF_RELOC_FOUND 0
+#define TF_RELOC_NOT_FOUND 1     /* candidates, but no try passed */
+#define TF_RELOC_NO_CANDIDATE 2  /* an empty index, or no row with a finite score */
+#define TF_RELOC_MAX_TRIES 8
+typedef struct tf_relocalise_params {
+  int32_t max_tries;          /* 1 .. TF_RELOC_MAX_TRIES */
+  int32_t min_stage;          /* 1 or 2: the tf_track_result.stage a try has to reach */
+  float min_valid_fraction;   /* of n_valid_last / n_sampled of the stage that gave the pose, in [0, 1] */
+  float max_rms;              /* of that stage's rms_last, metres */
+  tf_align_icp_params icp;    /* tf_track_frame's */
+  tf_align_params sdf;
+} tf_relocalise_params;
+typedef struct tf_reloc_try {
+  int32_t kf_id, overlap;
+  double score;
+  tf_track_result track;
+} tf_reloc_try;
+typedef struct tf_relocalise_result {
+  int32_t status;    /* TF_RELOC_* */
+  int32_t kf_id;     /* FOUND: the keyframe the accepted try started from; NOT_FOUND: the best-ranked one; else -1 */
+  int32_t rank;      /* FOUND: that keyframe's rank among the candidates (0 = best); else -1 */
+  int32_t n_tried;
+  float pose[12];    /* FOUND: the tracker's pose; NOT_FOUND: the best-ranked keyframe's pose; else 0 */
+  tf_reloc_try tries[TF_RELOC_MAX_TRIES];
+} tf_relocalise_result;
+/* max_tries 3, min_stage 2, min_valid_fraction 0.5, max_rms 0.01, the stages' own defaults */
+TF_API int tf_relocalise_default_params(tf_relocalise_params* out);
+/* tf_reloc_query, then tf_track_frame(depth, pose_k, icp, sdf) for the candidates in rank order, at most max_tries of them,
+ * until one is accepted: stage >= min_stage, and of the stage that gave its pose n_valid_last >= min_valid_fraction *
+ * n_sampled and rms_last <= max_rms.  pose_k is the rigid inverse of the keyframe's pose_inv16, [R^T | -R^T t], computed
+ * in f64 and rounded to f32.  The status is a field of the result: a call that finds nothing returns TF_OK.  It waits
+ * once for the query and twice per try.  TF_ERR_INVALID (nothing launched, the result untouched) for what either tracker
+ * stage rejects, a parameter out of range, no configured index, or a raycast camera (tf_raycast_camera) whose size is not
+ * tf_set_camera's: the tracker would read the frame at that size. */
+TF_API int tf_relocalise(tf_volume* v, const float* depth, const uint8_t* rgb, int32_t rgb_pixel_stride,
+                         const tf_relocalise_params* params, tf_relocalise_result* result);
+
 /* ---- meshing (the stage between the volume and the atlas) -----
  * Chisel::UpdateMeshes (Structure/Chisel.h:479-481) -> ChunkManager::RecomputeMeshes
  *   (Structure/ChunkManager.cpp:232-264): every chunk of meshesToUpdate that exists is re-meshed by

@@ -60,6 +60,9 @@ SYMBOLS = (
     "tf_align_group", "tf_align_group_device", "tf_align_group_log", "tf_align_unit_group",
     "tf_align_icp_default_params", "tf_align_frame_icp", "tf_align_frame_icp_device", "tf_align_icp_log",
     "tf_align_icp_residuals", "tf_align_icp_residuals_device", "tf_track_frame",
+    "tf_reloc_default_params", "tf_reloc_configure", "tf_reloc_index_add", "tf_reloc_index_remove", "tf_reloc_index_clear",
+    "tf_reloc_index_count", "tf_reloc_describe", "tf_reloc_descriptor_download", "tf_reloc_query", "tf_reloc_query_device",
+    "tf_relocalise_default_params", "tf_relocalise",
     "tf_texmap_set_keyframes", "tf_texmap_update", "tf_texmap_retract", "tf_texmap_remove_wrong_mapping",
     "tf_texmap_check_graph", "tf_texmap_view_selection", "tf_texmap_download", "tf_texmap_download_problem",
     "tf_texmap_clear", "tf_generate_patches_selected", "tf_texture_tail_device", "tf_texture_tail_list",
@@ -69,6 +72,9 @@ SYMBOLS = (
 TF_ALIGN_CONVERGED, TF_ALIGN_MAX_ITERS, TF_ALIGN_TOO_FEW, TF_ALIGN_SINGULAR = 0, 1, 2, 3
 TF_ALIGN_MAX_EVALUATIONS = 65
 TF_ALIGN_GROUP_MAX_FRAMES = 7
+# tf_relocalise_result.status
+TF_RELOC_FOUND, TF_RELOC_NOT_FOUND, TF_RELOC_NO_CANDIDATE = 0, 1, 2
+TF_RELOC_MAX_TRIES = 8
 
 # tf_query_points want_mask bits
 Q_SDF, Q_WEIGHT, Q_GRAD, Q_SDF_TRI, Q_RGB_TRI = 1, 2, 4, 8, 16
@@ -231,6 +237,62 @@ def AlignIcpParams(**kw):
             setattr(p.geo, k, float(val))
         else:
             raise TypeError("tf_align_icp_params has no field %r" % k)
+    return p
+
+
+class RelocParamsC(C.Structure):
+    _fields_ = [("tiny_w", C.c_int32), ("tiny_h", C.c_int32), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("grey_weight", C.c_float), ("depth_weight", C.c_float), ("min_overlap", C.c_int32)]
+
+
+def RelocParams(**kw):
+    """tf_reloc_params: the library's defaults (tf_reloc_default_params) with fields replaced by keyword"""
+    p = RelocParamsC()
+    rc = lib().tf_reloc_default_params(C.byref(p))
+    if rc != TF_OK:
+        raise TFError(rc, lib().tf_last_error().decode())
+    for k, val in kw.items():
+        if k in ("tiny_w", "tiny_h", "min_overlap"):
+            setattr(p, k, int(val))
+        elif any(k == f[0] for f in RelocParamsC._fields_):
+            setattr(p, k, float(val))
+        else:
+            raise TypeError("tf_reloc_params has no field %r" % k)
+    return p
+
+
+class RelocaliseParamsC(C.Structure):
+    _fields_ = [("max_tries", C.c_int32), ("min_stage", C.c_int32), ("min_valid_fraction", C.c_float),
+                ("max_rms", C.c_float), ("icp", AlignIcpParamsC), ("sdf", AlignParamsC)]
+
+
+class RelocTry(C.Structure):
+    _fields_ = [("kf_id", C.c_int32), ("overlap", C.c_int32), ("score", C.c_double), ("track", TrackResult)]
+
+
+class RelocaliseResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("kf_id", C.c_int32), ("rank", C.c_int32), ("n_tried", C.c_int32),
+                ("pose", C.c_float * 12), ("tries", RelocTry * TF_RELOC_MAX_TRIES)]
+
+
+def RelocaliseParams(icp=None, sdf=None, **kw):
+    """tf_relocalise_params: the library's defaults (tf_relocalise_default_params); icp / sdf: the tracker's parameters
+    (AlignIcpParams / AlignParams), the other fields by keyword"""
+    p = RelocaliseParamsC()
+    rc = lib().tf_relocalise_default_params(C.byref(p))
+    if rc != TF_OK:
+        raise TFError(rc, lib().tf_last_error().decode())
+    if icp is not None:
+        p.icp = icp
+    if sdf is not None:
+        p.sdf = sdf
+    for k, val in kw.items():
+        if k in ("max_tries", "min_stage"):
+            setattr(p, k, int(val))
+        elif k in ("min_valid_fraction", "max_rms"):
+            setattr(p, k, float(val))
+        else:
+            raise TypeError("tf_relocalise_params has no field %r" % k)
     return p
 
 
@@ -414,6 +476,19 @@ def lib():
     L.tf_align_icp_residuals.argtypes = [vp, fp, fp, fp, fp, fp, aip, fp, C.POINTER(C.c_uint32), i32p]
     L.tf_align_icp_residuals_device.argtypes = [vp, vp, fp, vp, vp, fp, aip, vp, vp, vp]
     L.tf_track_frame.argtypes = [vp, fp, fp, aip, app, C.POINTER(TrackResult)]
+    rlp, u32p, f64p = C.POINTER(RelocParamsC), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    L.tf_reloc_default_params.argtypes = [rlp]
+    L.tf_reloc_configure.argtypes = [vp, rlp]
+    L.tf_reloc_index_add.argtypes = [vp, i32p, C.c_int64]
+    L.tf_reloc_index_remove.argtypes = [vp, i32p, C.c_int64]
+    L.tf_reloc_index_clear.argtypes = [vp]
+    L.tf_reloc_index_count.argtypes = [vp, i64p]
+    L.tf_reloc_describe.argtypes = [vp, fp, u8p, C.c_int32, u32p, i32p, u64p]
+    L.tf_reloc_descriptor_download.argtypes = [vp, C.c_int32, u32p, i32p, u64p]
+    L.tf_reloc_query.argtypes = [vp, fp, u8p, C.c_int32, i32p, f64p, i32p, C.c_int64, i64p]
+    L.tf_reloc_query_device.argtypes = [vp, vp, vp, C.c_int32, i32p, f64p, i32p, C.c_int64, i64p]
+    L.tf_relocalise_default_params.argtypes = [C.POINTER(RelocaliseParamsC)]
+    L.tf_relocalise.argtypes = [vp, fp, u8p, C.c_int32, C.POINTER(RelocaliseParamsC), C.POINTER(RelocaliseResult)]
     L.tf_view_select.argtypes = [vp, C.c_int64, i32p, i32p, i64p, i32p, fp, C.c_float, i32p, C.c_int32, i32p,
                                  C.POINTER(C.c_double), i32p]
     L.tf_view_select_device.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_float, vp, C.c_int32, vp, vp, vp]
@@ -1191,6 +1266,94 @@ class Volume:
                                        C.byref(sdf_params), C.byref(res)))
         return dict(icp=self.align_result(res.icp), sdf=self.align_result(res.sdf), stage=res.stage,
                     pose=np.array(res.pose, np.float32).reshape(3, 4))
+
+    # -- relocalisation against the cached keyframes (tf_reloc_*, tf_relocalise; read-only)
+    def reloc_configure(self, params=None):
+        """Sets the descriptor grid and the score's weights (RelocParams) and empties the index"""
+        params = params or RelocParams()
+        self._ck(self.L.tf_reloc_configure(self.h, C.byref(params)))
+        self._reloc = params
+
+    def reloc_index_add(self, kf_ids):
+        ids = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        self._ck(self.L.tf_reloc_index_add(self.h, _p(ids, C.c_int32), len(ids)))
+
+    def reloc_index_remove(self, kf_ids):
+        ids = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        self._ck(self.L.tf_reloc_index_remove(self.h, _p(ids, C.c_int32), len(ids)))
+
+    def reloc_index_clear(self):
+        self._ck(self.L.tf_reloc_index_clear(self.h))
+
+    def reloc_index_count(self):
+        n = C.c_int64(0)
+        self._ck(self.L.tf_reloc_index_count(self.h, C.byref(n)))
+        return n.value
+
+    def _reloc_images(self, depth, rgb):
+        H, W = self.cam.height, self.cam.width  # the integrator's camera, whatever raycast_camera says
+        d = _f32(depth)
+        if d.size != W * H:
+            raise TFError(TF_ERR_INVALID, "depth needs %dx%d pixels" % (W, H))
+        c = np.ascontiguousarray(rgb, np.uint8)
+        if c.ndim != 3 or c.shape[:2] != (H, W) or c.shape[2] not in (3, 4):
+            raise TFError(TF_ERR_INVALID, "rgb must be [%d, %d, 3 or 4] u8" % (H, W))
+        return d, c, c.shape[2]
+
+    def _reloc_blocks(self):
+        p = getattr(self, "_reloc", None)
+        if p is None:
+            raise TFError(TF_ERR_INVALID, "reloc_configure first")
+        return p.tiny_w * p.tiny_h
+
+    def reloc_describe(self, depth, rgb):
+        """The descriptor of host images -> (G u32[n], Z i32[n], S int)"""
+        n = self._reloc_blocks()
+        d, c, stride = self._reloc_images(depth, rgb)
+        G, Z, S = np.zeros(n, np.uint32), np.zeros(n, np.int32), C.c_uint64(0)
+        self._ck(self.L.tf_reloc_describe(self.h, _p(d, C.c_float), _p(c, C.c_uint8), stride, _p(G, C.c_uint32),
+                                          _p(Z, C.c_int32), C.byref(S)))
+        return G, Z, S.value
+
+    def reloc_descriptor(self, kf_id):
+        """The indexed row of a keyframe -> (G, Z, S)"""
+        n = self._reloc_blocks()
+        G, Z, S = np.zeros(n, np.uint32), np.zeros(n, np.int32), C.c_uint64(0)
+        self._ck(self.L.tf_reloc_descriptor_download(self.h, int(kf_id), _p(G, C.c_uint32), _p(Z, C.c_int32), C.byref(S)))
+        return G, Z, S.value
+
+    def _reloc_query(self, fn, a, b, stride, cap):
+        cap = self.reloc_index_count() if cap is None else int(cap)
+        ids, sc, ov = np.zeros(cap, np.int32), np.zeros(cap, np.float64), np.zeros(cap, np.int32)
+        n = C.c_int64(0)
+        self._ck(fn(self.h, a, b, stride, _p(ids, C.c_int32), _p(sc, C.c_double), _p(ov, C.c_int32), cap, C.byref(n)))
+        m = min(n.value, cap)
+        return dict(kf_ids=ids[:m], scores=sc[:m], overlap=ov[:m], n=n.value)
+
+    def reloc_query(self, depth, rgb, cap=None):
+        """The ranked candidates for host images -> dict(kf_ids, scores, overlap: the first min(n, cap); n: how many there
+        are); cap None: room for the whole index"""
+        d, c, stride = self._reloc_images(depth, rgb)
+        return self._reloc_query(self.L.tf_reloc_query, _p(d, C.c_float), _p(c, C.c_uint8), stride, cap)
+
+    def reloc_query_device(self, d_depth, d_rgb, stride=3, cap=None):
+        return self._reloc_query(self.L.tf_reloc_query_device, d_depth or None, d_rgb or None, stride, cap)
+
+    def relocalise(self, depth, rgb, params=None):
+        """Retrieval over the indexed keyframes, then track_frame from the candidates' poses in rank order ->
+        dict(status, kf_id, rank, n_tried, pose [3, 4] f32, tries: [dict(kf_id, score, overlap, track: track_frame's dict)])"""
+        d, c, stride = self._reloc_images(depth, rgb)
+        params = params or RelocaliseParams()
+        res = RelocaliseResult()
+        self._ck(self.L.tf_relocalise(self.h, _p(d, C.c_float), _p(c, C.c_uint8), stride, C.byref(params), C.byref(res)))
+        tries = []
+        for k in range(res.n_tried):
+            t = res.tries[k]
+            tr = dict(icp=self.align_result(t.track.icp), sdf=self.align_result(t.track.sdf), stage=t.track.stage,
+                      pose=np.array(t.track.pose, np.float32).reshape(3, 4))
+            tries.append(dict(kf_id=t.kf_id, score=t.score, overlap=t.overlap, track=tr, raw=bytes(t.track)))
+        return dict(status=res.status, kf_id=res.kf_id, rank=res.rank, n_tried=res.n_tried,
+                    pose=np.array(res.pose, np.float32).reshape(3, 4), tries=tries)
 
     # -- view selection (the solve of TexMap::view_selection)
     def view_select(self, ids, nbr, col_off, labels, costs, edge_cost=0.5, init=None, max_rounds=0, out=None):

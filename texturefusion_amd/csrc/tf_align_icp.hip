@@ -422,6 +422,12 @@ int icp_raycast(tf_volume* v, const float* model_pose, const tf_align_icp_params
 
 void align_icp_release(tf_volume* v) { v->align_icp = AlignIcpState{}; }
 
+int track_check(tf_volume* v, const float* depth, const float* pose, const tf_align_icp_params* icp_params,
+                const tf_align_params* sdf_params) {
+  const int rc = icp_check(v, depth, pose, nullptr, icp_params, true, true);
+  return rc ? rc : align_check(v, depth, pose, sdf_params, true);
+}
+
 }  // namespace tf
 
 using namespace tf;
@@ -537,9 +543,8 @@ int tf_align_icp_residuals(tf_volume* v, const float* depth, const float pose[12
 
 int tf_track_frame(tf_volume* v, const float* depth, const float pose[12], const tf_align_icp_params* icp_params,
                    const tf_align_params* sdf_params, tf_track_result* out) {
-  int rc = icp_check(v, depth, pose, nullptr, icp_params, true, true);
+  int rc = track_check(v, depth, pose, icp_params, sdf_params);
   if (rc) return rc;
-  if ((rc = align_check(v, depth, pose, sdf_params, true))) return rc;
   if (!out) { set_error("null argument"); return TF_ERR_INVALID; }
   tf_track_result t{};
   t.sdf.status = -1;  // not run

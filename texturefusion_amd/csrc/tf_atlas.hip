@@ -610,6 +610,7 @@ int tf_keyframe_set_pose(tf_volume* v, int32_t kf_id, const float pose_inv16[16]
   int rc = kf_slot_for(v, kf_id, false, &slot);
   if (rc) return rc;
   memcpy(v->atlas.h_kf[(size_t)slot].T, pose_inv16, 64);
+  v->atlas.keyframes[kf_id].has_pose = true;
   return kf_push(v, slot);
 }
 

@@ -836,6 +836,7 @@ int tf_volume_reset(tf_volume* v) {
   align_color_release(v);
   align_group_release(v);
   align_icp_release(v);
+  reloc_release(v);
   model_release(v);
   rc = init_device_state(v);
   if (rc) return rc;

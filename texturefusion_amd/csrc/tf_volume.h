@@ -123,6 +123,7 @@ struct ProfEvent {
 struct KeyframeSlot {
   DevMem rgb, depth;  // tf_keyframe_cache's copies, u8[H][W][3] and f32[H][W], fitted to the camera; empty: the caller's images
   int slot = -1;      // entry of the device keyframe table
+  bool has_pose = false;  // tf_keyframe_set_pose has been called (the table's pose is the identity until then)
 };
 
 struct AtlasState {
@@ -203,6 +204,18 @@ struct AlignIcpState {
   size_t cap_tiles = 0;
   DevMem maps;
   size_t map_pixels = 0;  // pixels each plane of `maps` has room for
+};
+
+// Relocalisation against the cached keyframes (tf_reloc.hip): the configuration, and the index -- one block holding every
+// row's descriptor, the query's and the scores; the host keeps which keyframe a row belongs to.  Empty until configured.
+struct RelocState {
+  bool on = false;
+  tf_reloc_params p{};
+  int W = 0, H = 0;      // the camera the configuration was made for
+  DevMem block;
+  size_t cap_rows = 0;   // rows the block has room for
+  std::vector<int32_t> kf_ids;                   // row -> keyframe id
+  std::unordered_map<int32_t, int32_t> row_of;   // keyframe id -> row
 };
 
 // The model's DrawMeshes stream, resident in the handle (tf_model.hip): packed on the device, counts in device words,
@@ -315,6 +328,7 @@ struct tf_volume {
   tf::AlignColorState align_color;
   tf::AlignGroupState align_group;
   tf::AlignIcpState align_icp;
+  tf::RelocState reloc;
   tf::ModelState model;
   uint64_t model_gen = 0;  // advanced by every entry point that is not a whitelisted reader (TF_DEV_READER)
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
@@ -427,6 +441,10 @@ int align_check(tf_volume* v, const float* depth, const float* pose, const tf_al
 void align_color_release(tf_volume* v);
 void align_group_release(tf_volume* v);  // frees tf_align_group.hip's state block
 void align_icp_release(tf_volume* v);    // frees tf_align_icp.hip's state block and its maps
+// what tf_track_frame refuses a call for (tf_align_icp.hip), for tf_relocalise to refuse it ahead of its first launch
+int track_check(tf_volume* v, const float* depth, const float* pose, const tf_align_icp_params* icp_params,
+                const tf_align_params* sdf_params);
+void reloc_release(tf_volume* v);        // frees tf_reloc.hip's index and forgets its configuration
 // the resident model stream (tf_model.hip).  model_pack_enqueue: list, rank, scan and write on the handle's stream, nothing
 // read back (the buffers exist and have a capacity); model_stream_sync: the pack, one wait for the control block, the
 // buffers grown and the pack repeated on overflow -- ModelState::nv / ni are the counts afterwards; model_release frees all

@@ -956,6 +956,35 @@ class Chisel {
     tf_check(tf_track_frame(vol, depthImage, depthExtrinsic.data(), icpParams, sdfParams, result), "TrackFrame");
     return result->stage;
   }
+  // A lost camera found again (tf_relocalise): the cached keyframes that were put into the index (RelocConfigure, then
+  // RelocIndexAdd for keyframes that have been through CacheKeyframe-style tf_keyframe_cache and tf_keyframe_set_pose)
+  // are ranked by their small images against this frame's, and TrackFrame runs from the best ones' poses until one holds.
+  // The caller gives no pose.  nullptr parameters: the library's defaults.  Returns result->status (TF_RELOC_FOUND:
+  // result->pose is the tracker's pose).
+  void RelocConfigure(const tf_reloc_params* params = nullptr) {
+    tf_reloc_params def;
+    if (!params) {
+      tf_check(tf_reloc_default_params(&def), "RelocConfigure");
+      params = &def;
+    }
+    tf_check(tf_reloc_configure(vol, params), "RelocConfigure");
+  }
+  void RelocIndexAdd(const std::vector<int32_t>& keyframeIds) {
+    tf_check(tf_reloc_index_add(vol, keyframeIds.data(), (int64_t)keyframeIds.size()), "RelocIndexAdd");
+  }
+  void RelocIndexRemove(const std::vector<int32_t>& keyframeIds) {
+    tf_check(tf_reloc_index_remove(vol, keyframeIds.data(), (int64_t)keyframeIds.size()), "RelocIndexRemove");
+  }
+  int Relocalise(const float* depthImage, const uint8_t* rgbImage, int rgbPixelStride, const tf_relocalise_params* params,
+                 tf_relocalise_result* result) {
+    tf_relocalise_params def;
+    if (!params) {
+      tf_check(tf_relocalise_default_params(&def), "Relocalise");
+      params = &def;
+    }
+    tf_check(tf_relocalise(vol, depthImage, rgbImage, rgbPixelStride, params, result), "Relocalise");
+    return result->status;
+  }
   // GCFusion/MobileFusion.cpp:322, for the struct the keyframe unit takes (tf_align_unit_group): the group's device depth
   // images aligned at the group's poses -- rigid: the keyframe and its local frames as one body (the reference keeps local
   // frames by their pose relative to the keyframe); otherwise every frame on its own -- and the aligned poses written
