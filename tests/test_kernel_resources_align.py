@@ -1,10 +1,11 @@
 """Register / private-memory budget of the alignment kernels (texturefusion_amd/csrc/tf_align.hip), checked at build time
 like tests/test_kernel_resources_render.py.  k_align_rows carries seven trilinear samples and the tile's 31 sums: the
 budget is the raycaster's, no private memory and VGPRs at or below what gives six waves per SIMD (512 / 6 = 85, in
-granules of 8: 80).  k_align_solve is one workgroup of 256 threads whose lane 0 holds the 6 x 6 system in registers.  The
-compiler reports 256 VGPRs for it, which is also the most a 256-thread workgroup can be given: that figure bounds nothing,
-what is checked for this kernel is that nothing of lane 0's arrays went to private memory.  Its LDS, 5120 B as built, is the
-8 x 32 f64 table the eight groups' sums meet in (2048 B) plus the small arrays of lane 0 the compiler moves there."""
+granules of 8: 80; it builds at 77).  k_align_solve is one workgroup of 256 threads whose lane 0 holds the 6 x 6 system in
+registers (88 VGPRs as built; the budget of 256 is the most a 256-thread workgroup can be given and bounds nothing): what is
+checked for this kernel is that nothing of lane 0's arrays went to private memory.  Its LDS, 5120 B as built, is the
+8 x 32 f64 table the eight groups' sums meet in (2048 B) plus the small arrays of lane 0 the compiler moves there.
+The kernels are calls into tf_align_rows.h, which all four aligners share: that its pieces exist once is checked here too."""
 import os
 import re
 import shutil
@@ -53,9 +54,36 @@ def test_align_kernels_stay_within_their_budget():
     assert rows["Occupancy"] >= 6, rows
 
 
+ALIGNERS = ("tf_align.hip", "tf_align_color.hip", "tf_align_group.hip", "tf_align_icp.hip")
+SHARED = ("tf_align_rows.h", "tf_align_tree.h", "tf_align_solve.h", "tf_align_group_solve.h", "tf_ray_devfn.h", "tf_volume.h")
+# a distinctive line of every shared piece: the tree's level and its table, the sampler, the 6 x 6 solve, the idle test,
+# the level-finished mark, the stop rules, the solve launch's stride over the partial rows, the wave-order combine, the carver
+PIECES = ("void al_halve(", "AlPairs al_pairs()", "bool tri_sample(", "bool align_solve6(", "(st & 1u) ||", "c.state & 0xFFu",
+          "TF_ALIGN_SINGULAR", "TF_ALIGN_TOO_FEW", "TF_ALIGN_CONVERGED", "t += 8u", "k < kAlWaves; ++k", "L.take(count * sizeof(")
+
+
+def _code(name):
+    """the file's text without its // comments"""
+    return re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, name)).read())
+
+
 def test_the_sampler_is_shared_not_copied():
     ray = open(os.path.join(CSRC, "tf_ray.hip")).read()
     align = open(os.path.join(CSRC, "tf_align.hip")).read()
+    assert '#include "tf_ray_devfn.h"' in ray and '#include "tf_align_rows.h"' in align
+    assert '#include "tf_ray_devfn.h"' in open(os.path.join(CSRC, "tf_align_rows.h")).read()
     for text in (ray, align):
-        assert '#include "tf_ray_devfn.h"' in text and "bool tri_sample(" not in text
+        assert "bool tri_sample(" not in text
     assert "atomic" not in align.split("#include <hip/hip_runtime.h>")[1]  # no atomics of any kind in the code
+    assert "atomic" not in open(os.path.join(CSRC, "tf_align_rows.h")).read().split("#include <hip/hip_runtime.h>")[1]
+
+
+def test_the_aligners_machinery_is_written_once():
+    """every shared piece once in the headers, in no aligner's own file"""
+    shared = "".join(_code(h) for h in SHARED)
+    for piece in PIECES:
+        assert shared.count(piece) == 1, piece
+        for name in ALIGNERS:
+            assert _code(name).count(piece) == 0, (name, piece)
+    for name in ALIGNERS:
+        assert '#include "tf_align_rows.h"' in _code(name), name

@@ -1,9 +1,9 @@
 """Register / private-memory budget of the colour-aided alignment kernels (texturefusion_amd/csrc/tf_align_color.hip),
 checked at build time like tests/test_kernel_resources_align.py.  k_calign_rows carries seven samples of SDF and intensity
 (sixteen loads each) and two tiles' worth of sums: it is bound by chains of dependent loads and needs its waves, so the
-budget is no private memory and at least four waves per SIMD (at most 128 VGPRs); the compiler reports 116, in granules of
-8: 120.  Its LDS is two rows of 32 f64 per wave.  k_calign_solve is one workgroup of 256 threads whose lane 0 holds the
-joined 6 x 6 system in registers (174 VGPRs as built, which bounds nothing: what is checked is that none of lane 0's arrays
+budget is no private memory and at least four waves per SIMD (at most 128 VGPRs); the compiler reports 120 (116 before the row moved
+into tf_align_rows.h: the same granule of 8).  Its LDS is two rows of 32 f64 per wave.  k_calign_solve is one workgroup of 256 threads whose lane 0 holds the
+joined 6 x 6 system in registers (176 VGPRs as built, which bounds nothing: what is checked is that none of lane 0's arrays
 went to private memory); its LDS is the 8 x 64 f64 table the eight groups' sums meet in."""
 import os
 import re
@@ -57,7 +57,13 @@ def test_align_color_kernels_stay_within_their_budget():
 def test_the_sampler_and_the_tree_are_shared_not_copied():
     geo = open(os.path.join(CSRC, "tf_align.hip")).read()
     col = open(os.path.join(CSRC, "tf_align_color.hip")).read()
-    for text in (geo, col):
-        assert '#include "tf_ray_devfn.h"' in text and '#include "tf_align_tree.h"' in text
+    rows = open(os.path.join(CSRC, "tf_align_rows.h")).read()
+    assert '#include "tf_ray_devfn.h"' in rows and '#include "tf_align_tree.h"' in rows
+    for text in (geo, col, rows):
         assert "bool tri_sample" not in text and "void al_halve(" not in text and "al_pairs()" not in text
-    assert "atomic" not in col.split("#include <hip/hip_runtime.h>")[1]  # no atomics of any kind in the code
+    for text in (geo, col):
+        assert '#include "tf_align_rows.h"' in text
+        assert "al_row_sums(" in text and "al_tile_sum(" not in text  # through the one function that forms a row's sums
+    code = col.split("#include <hip/hip_runtime.h>")[1]
+    assert code.count("al_sdf_row<true>(") == 1 and "tri_sample_lum" not in code  # the SDF row's text, not a second copy
+    assert "atomic" not in code  # no atomics of any kind in the code

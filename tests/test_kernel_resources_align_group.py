@@ -1,7 +1,7 @@
 """Register / private-memory budget of the group alignment kernels (texturefusion_amd/csrc/tf_align_group.hip), checked at
-build time in the manner of tests/test_kernel_resources_align.py.  k_galign_rows is k_align_rows' body plus the frame's
+build time in the manner of tests/test_kernel_resources_align.py.  k_galign_rows is k_align_rows' row (tf_align_rows.h) plus the frame's
 table lookup and the three adds of the lever: the same budget, no private memory and at most 80 VGPRs, six waves per SIMD
-(it builds at 79).  k_galign_solve is one workgroup of 256 threads per body whose lane 0 holds the 6 x 6 system in
+(it builds at 76).  k_galign_solve is one workgroup of 256 threads per body whose lane 0 holds the 6 x 6 system in
 registers; what is checked is that nothing of it went to private memory.  Its LDS is the 8 x 32 f64 table the eight
 groups' sums meet in, the 32 f64 of the body's sums, and the small arrays of lane 0 the compiler moves there (5376 B as
 built).  Only the figures the compiler reports are read."""
@@ -56,7 +56,11 @@ def test_align_group_kernels_stay_within_their_budget():
 
 def test_the_group_file_shares_the_sampler_the_tree_and_the_solve():
     text = open(os.path.join(CSRC, "tf_align_group.hip")).read()
-    for inc in ('#include "tf_ray_devfn.h"', '#include "tf_align_tree.h"', '#include "tf_align_group_solve.h"'):
+    for inc in ('#include "tf_align_rows.h"', '#include "tf_align_group_solve.h"'):
         assert inc in text
-    assert "bool tri_sample(" not in text and "al_tile_sum(" in text and "align_solve6(" in text
+    assert "bool tri_sample(" not in text and "tri_sample<" not in text and "al_sdf_row<false>(" in text
+    # the row's sums, the solve launch's additions and the stop rules are called, not restated
+    for call in ("al_row_sums(", "al_store_rows(", "al_add_rows(", "al_decide(", "align_update_about("):
+        assert call in text, call
+    assert "al_tile_sum(" not in text and "align_solve6(" not in text
     assert "atomic" not in text.split("#include <hip/hip_runtime.h>")[1]  # no atomics of any kind in the code

@@ -1,8 +1,8 @@
 """Register / private-memory budget of the projective-ICP kernels (texturefusion_amd/csrc/tf_align_icp.hip), checked at build
 time in the manner of tests/test_kernel_resources_align_group.py.  k_icp_rows has no chunk cache and no eight-corner
 samples: six scattered loads and the wave tree, so it has to stay inside k_align_rows' budget with room to spare -- at most
-80 VGPRs, no private memory, six waves per SIMD (it builds at 61 VGPRs and eight waves).  k_icp_solve is k_align_solve's
-text: one workgroup whose lane 0 holds the 6 x 6 system in registers; what is checked is that nothing of it went to private
+80 VGPRs, no private memory, six waves per SIMD (it builds at 63 VGPRs and eight waves).  k_icp_solve is k_align_solve's
+function (al_solve_pose, tf_align_rows.h): one workgroup whose lane 0 holds the 6 x 6 system in registers; what is checked is that nothing of it went to private
 memory.  Only the figures the compiler reports, and the file's includes, are read."""
 import os
 import re
@@ -55,10 +55,15 @@ def test_align_icp_kernels_stay_within_their_budget():
 
 def test_the_icp_file_shares_the_tree_and_the_solve():
     text = open(os.path.join(CSRC, "tf_align_icp.hip")).read()
+    assert '#include "tf_align_rows.h"' in text
+    rows = open(os.path.join(CSRC, "tf_align_rows.h")).read()
     for inc in ('#include "tf_align_tree.h"', '#include "tf_align_solve.h"'):
-        assert inc in text
-    assert "al_tile_sum(" in text and "align_solve6(" in text and "align_update(" in text
-    assert "al_halve" not in text and "bool align_solve6" not in text  # used, not restated
+        assert inc in rows
+    # used, not restated: the row's sums, and the whole solve launch k_align_solve runs
+    for call in ("al_point(", "al_row_sums(", "al_store_rows(", "al_solve_pose("):
+        assert call in text, call
+    assert "al_solve_pose(" in open(os.path.join(CSRC, "tf_align.hip")).read()
+    assert "al_halve" not in text and "align_solve6" not in text and "al_tile_sum(" not in text and "align_update(" not in text
     assert "atomic" not in text.split("#include <hip/hip_runtime.h>")[1]  # no atomics of any kind in the code
     for name in ("tf_align.hip", "tf_align_color.hip", "tf_align_group.hip"):  # the other aligners do not know this one
         assert "icp" not in open(os.path.join(CSRC, name)).read().lower()

@@ -9,6 +9,8 @@
 //                  residual map of tf_align_residuals -- one body
 //   k_align_solve  one workgroup: the partials combined in tile order, the 6 x 6 solve and the pose update by one lane
 //                  (tf_align_solve.h), a log record, the result
+// The kernels are calls into tf_align_rows.h, the machinery all four aligners share; what is this file's own is the row of
+// a pixel as stated below (al_sdf_row), and the host side every aligner uses (tf_volume.h: align_cam .. align_log).
 //
 // Per sampled pixel (x, y), all f32, every operation rounded on its own (-ffp-contract=off):
 //   z = depth[y][x], in range iff finite and min_depth <= z <= max_depth                                       (bit 0)
@@ -23,23 +25,16 @@
 // Sums over the valid pixels, every term a product of two f32 values taken in f64 (exact), accumulated in f64:
 //   A_ij = sum (double)wJ_i * (double)J_j (i <= j, the 21 upper entries row by row),  b_i = sum (double)wJ_i * (double)r,
 //   sum_r2 = sum (double)r * (double)r,  sum_wr2 = sum (double)wr * (double)r,  n_valid, n_sampled (pixels inside the image)
-// Order of summation, a function of (W, H, stride) alone: the 64 lanes of a tile by the tree of ccd_wave_sum (xor 32,
-// 16, .. 1; each node computed by one lane, tf_align_tree.h), the eight tiles of a workgroup in wave order, one plain-stored
-// row per workgroup; in k_align_solve eight threads per sum add the rows g, g + 8, g + 16, .. in ascending order (g = 0..7),
-// then the eight in order.
+// Order of summation, a function of (W, H, stride) alone, and the stop rules: tf_align_rows.h's header (the tree of
+// tf_align_tree.h per tile, the eight tiles of a workgroup in wave order, the rows g, g + 8, .. ascending, then the eight).
 // No atomics, no counters, no polling: the launch boundary between k_align_rows and k_align_solve is the only hand-off.
-// Every launch of a call is enqueued up front; a launch first reads the state word (bit 0: stopped, bits 8..: levels that
-// are finished) and returns if it has nothing to do.
+// Every launch of a call is enqueued up front; a launch first reads the state word and returns if it has nothing to do.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <string.h>
 
-#include <type_traits>
-
-#include "tf_align_solve.h"
-#include "tf_align_tree.h"
-#include "tf_ray_devfn.h"
+#include "tf_align_rows.h"
 #include "tf_volume.h"
 
 #pragma clang fp contract(off)
@@ -49,14 +44,6 @@ namespace {
 
 constexpr int kAlignMaxIters = 64;
 
-struct AlignCtl {
-  uint32_t state;  // bit 0: stopped (too few / singular), bits 8..: levels finished
-  int32_t status;
-  int32_t n_eval;
-  int32_t n_valid_first;
-  float rms_first;
-  uint32_t pad[3];
-};
 struct AlignDev {
   AlignCtl* ctl;
   double* pose_d;       // [12] the pose between iterations
@@ -64,17 +51,14 @@ struct AlignDev {
   float* pose_r;        // [12] tf_align_residuals' pose (the last alignment's state stays as it is)
   double* part;         // [ceil(cap_tiles / kAlWaves)][kAlRow]: a row per workgroup of k_align_rows
   tf_align_iter* log;   // [TF_ALIGN_MAX_EVALUATIONS]
-  uint32_t cap_tiles;   // tiles of the camera at stride 1
 };
-struct AlignPose { float p[12]; };
 
 struct AlignRowsArgs {
+  AlignRowsCommon c;
   const float* depth;
   const float* pose;      // 12 floats in the state block
   const uint32_t* state;  // null: always run (tf_align_residuals)
-  float fx, fy, cxs, cys;
-  int W, H, tiles_x, stride, level;
-  float min_depth, max_depth, max_residual, huber, res;
+  float res;
   size_t plane;
   float* r;
   float* grad;
@@ -82,225 +66,61 @@ struct AlignRowsArgs {
   double* part;  // null: no sums
 };
 struct AlignSolveArgs {
-  int level, log_level, stride, closing, last_level;
-  uint32_t n_rows;  // workgroups of the rows launch
-  float damping, eps_t, eps_r;
-  int min_valid;
+  AlignSolveCommon c;
   tf_align_result* out;
 };
 
-__device__ __forceinline__ bool al_idle(const uint32_t* state, int level) {
-  const uint32_t st = *state;
-  return (st & 1u) || (uint32_t)level < (st >> 8);
-}
 __global__ __launch_bounds__(64) void k_align_begin(AlignDev d, AlignPose p, int residuals_only) {
-  const int i = threadIdx.x;
-  if (residuals_only) {
-    if (i < 12) d.pose_r[i] = p.p[i];
-    return;
-  }
-  if (i < 12) { d.pose_d[i] = (double)p.p[i]; d.pose_f[i] = p.p[i]; }
-  if (i == 0) {
-    AlignCtl c{};
-    c.status = TF_ALIGN_MAX_ITERS;
-    *d.ctl = c;
-  }
+  al_begin(d.ctl, d.pose_d, d.pose_f, d.pose_r, p, residuals_only);
 }
 
-// (80 VGPRs, six waves per SIMD, no private memory: tests/test_kernel_resources_align.py)
+// (six waves per SIMD, no private memory: tests/test_kernel_resources_align.py)
 __global__ __launch_bounds__(kAlWaves * 64) void k_align_rows(VolumeDev v, AlignRowsArgs a) {
-  if (a.state && al_idle(a.state, a.level)) return;
-  // (a tile beyond the last one of the level lies below the image: none of its lanes is inside)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int tile = blockIdx.x * kAlWaves + wave;
-  const long long X = (long long)((tile % a.tiles_x) * 8 + (lane & 7)) * a.stride;
-  const long long Y = (long long)((tile / a.tiles_x) * 8 + (lane >> 3)) * a.stride;
-  const bool in = X < a.W && Y < a.H;
-  uint32_t fl = 0;
-  float s = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, qx = 0.f, qy = 0.f, qz = 0.f;
-  if (in) {
-    const size_t o = (size_t)Y * a.W + (size_t)X;
-    const float z = a.depth[o];
-    if (isfinite(z) && z >= a.min_depth && z <= a.max_depth) {
-      fl = 1u;
-      const float res = a.res, ir = 1.0f / res;
-      const float dcx = ((float)(int)X - a.cxs) / a.fx, dcy = ((float)(int)Y - a.cys) / a.fy;
-      const float pcx = dcx * z, pcy = dcy * z;
-      const float* P = a.pose;
-      qx = (P[0] * pcx + P[1] * pcy) + P[2] * z;
-      qy = (P[4] * pcx + P[5] * pcy) + P[6] * z;
-      qz = (P[8] * pcx + P[9] * pcy) + P[10] * z;
-      const float wx = P[3] + qx, wy = P[7] + qy, wz = P[11] + qz;
-      ChunkCache cc{INT_MIN, INT_MIN, INT_MIN, kInvalidSlot};
-      float sc = 0.f;
-      if (tri_sample<false>(v, cc, wx, wy, wz, ir, &sc)) {
-        fl |= 2u;
-        s = sc;
-        // tap k: axis k >> 1, minus / plus by k & 1 (as the raycaster's normal; no one-sided fallback here)
-        float sp0 = 0.f, sp1 = 0.f, sp2 = 0.f, sm0 = 0.f, sm1 = 0.f, sm2 = 0.f;
-        bool ok = true;
-#pragma unroll 1
-        for (int k = 0; k < 6; ++k) {
-          const int ax = k >> 1;
-          float t = 0.f;
-          const float h = (k & 1) ? res : -res;  // (a + (-b) is a - b)
-          ChunkCache ct = cc;  // every tap starts from the centre's chunk: a tap that leaves it costs one probe, none to come back
-          const bool okk = tri_sample<false>(v, ct, ax == 0 ? wx + h : wx, ax == 1 ? wy + h : wy, ax == 2 ? wz + h : wz, ir, &t);
-          ok = ok && okk;
-          if (k == 0) sm0 = t; else if (k == 1) sp0 = t; else if (k == 2) sm1 = t; else if (k == 3) sp1 = t;
-          else if (k == 4) sm2 = t; else sp2 = t;
-        }
-        if (ok) {
-          fl |= 4u;
-          const float h2 = 0.5f / res;
-          gx = (sp0 - sm0) * h2; gy = (sp1 - sm1) * h2; gz = (sp2 - sm2) * h2;
-          if (fabsf(s) <= a.max_residual) fl |= 8u;
-        }
-      }
-    }
-    if (a.r) a.r[o] = s;
-    if (a.grad) { a.grad[o] = gx; a.grad[a.plane + o] = gy; a.grad[2 * a.plane + o] = gz; }
-    if (a.flags) a.flags[o] = fl;
+  if (a.state && al_idle(a.state, a.c.level)) return;
+  const AlPixel px = al_pixel(a.c);
+  AlSdfRow row{};
+  if (px.in) {
+    const size_t o = (size_t)px.Y * a.c.W + (size_t)px.X;
+    row = al_sdf_row<false>(v, a.c, a.res, px, a.depth[o], a.pose);
+    if (a.r) a.r[o] = row.s;
+    if (a.grad) { a.grad[o] = row.gx; a.grad[a.plane + o] = row.gy; a.grad[2 * a.plane + o] = row.gz; }
+    if (a.flags) a.flags[o] = row.fl;
   }
   if (!a.part) return;
-  const bool valid = fl == 15u;
-  float J[6] = {gx, gy, gz, qy * gz - qz * gy, qz * gx - qx * gz, qx * gy - qy * gx};
-  const float ar = fabsf(s);
-  float w = (a.huber == 0.f || ar <= a.huber) ? 1.0f : a.huber / ar;
-  float r = s;
-  if (!valid) {  // an exact zero in every term
-    w = 0.f; r = 0.f;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) J[i] = 0.f;
-  }
-  // the 31 sums of the tile through the wave tree (tf_align_tree.h): lane l ends up with entry al_entry(l)
-  const double total = al_tile_sum(J, w, r, valid ? 1.0f : 0.0f, in ? 1.0f : 0.0f, lane);
-  const int e = al_entry(lane);
-  // the workgroup's eight tiles in wave order, one plain-stored row per workgroup
   __shared__ double wsum[kAlWaves][kAlRow];
-  if (!(lane & 1)) wsum[wave][e] = total;
-  __syncthreads();
-  if (threadIdx.x < (unsigned)kAlSums) {
-    double t = wsum[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < kAlWaves; ++k) t += wsum[k][threadIdx.x];
-    a.part[(size_t)blockIdx.x * kAlRow + threadIdx.x] = t;
-  }
+  al_row_sums(wsum, 0, px, row.gx, row.gy, row.gz, row.qx, row.qy, row.qz, row.s, a.c.huber, row.fl == 15u, px.in);
+  al_store_rows(wsum, a.part + (size_t)blockIdx.x * kAlRow);
 }
 
 __global__ __launch_bounds__(256) void k_align_solve(AlignDev d, AlignSolveArgs a) {
-  if (al_idle(&d.ctl->state, a.level)) return;
-  // thread (e = tid & 31, g = tid >> 5) adds entry e of the rows g, g + 8, g + 16, .. in ascending order (a row's 32
-  // entries lie side by side: the 32 threads of a group read one 256-byte row); then the eight groups in order
-  __shared__ double red[8][kAlRow];
-  const uint32_t tid = threadIdx.x, e = tid & 31u, g = tid >> 5;
-  double acc = 0.0;
-  if (e < (uint32_t)kAlSums)
-#pragma unroll 8
-    for (uint32_t t = g; t < a.n_rows; t += 8u) acc += d.part[(size_t)t * kAlRow + e];
-  red[g][e] = acc;
-  __syncthreads();
-  if (tid != 0) return;
-  double S[kAlSums];
-#pragma unroll
-  for (int i = 0; i < kAlSums; ++i) {
-    double t = red[0][i];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) t += red[k][i];
-    S[i] = t;
-  }
-  AlignCtl c = *d.ctl;
-  const int n_valid = (int)S[kAlNv], n_sampled = (int)S[kAlNs];
-  const float rms = n_valid > 0 ? (float)sqrt(S[kAlR2] / (double)n_valid) : 0.f;
-  tf_align_iter* rec = d.log + (c.n_eval < TF_ALIGN_MAX_EVALUATIONS ? c.n_eval : TF_ALIGN_MAX_EVALUATIONS - 1);
-  rec->level = a.log_level; rec->stride = a.stride; rec->n_sampled = n_sampled; rec->n_valid = n_valid;
-  rec->sum_r2 = S[kAlR2]; rec->sum_wr2 = S[kAlWr2];
-#pragma unroll
-  for (int i = 0; i < 21; ++i) rec->A[i] = S[kAlA + i];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) { rec->b[i] = S[kAlB + i]; rec->xi[i] = 0.0; }
-  double pose[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) { pose[i] = d.pose_d[i]; rec->pose[i] = pose[i]; }
-  if (c.n_eval == 0) { c.n_valid_first = n_valid; c.rms_first = rms; }
-  c.n_eval += 1;
-  if (n_valid < a.min_valid) {
-    c.status = TF_ALIGN_TOO_FEW;
-    c.state |= 1u;
-  } else if (!a.closing) {
-    double xi[6];
-    if (!align_solve6(S + kAlA, S + kAlB, (double)a.damping, xi)) {
-      c.status = TF_ALIGN_SINGULAR;
-      c.state |= 1u;
-    } else {
-      align_update(pose, xi);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) { d.pose_d[i] = pose[i]; d.pose_f[i] = (float)pose[i]; }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) rec->xi[i] = xi[i];
-      const double nt = sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]);
-      const double nr = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
-      if (nt < (double)a.eps_t && nr < (double)a.eps_r) {
-        c.state = (c.state & 0xFFu) | ((uint32_t)(a.level + 1) << 8);
-        if (a.last_level) c.status = TF_ALIGN_CONVERGED;
-      }
-    }
-  }
-  *d.ctl = c;
-  tf_align_result* out = a.out;
-  out->status = c.status; out->evaluations = c.n_eval; out->n_sampled = n_sampled;
-  out->n_valid_first = c.n_valid_first; out->n_valid_last = n_valid;
-  out->rms_first = c.rms_first; out->rms_last = rms;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) out->pose[i] = (float)pose[i];
+  al_solve_pose(d.ctl, d.log, d.pose_d, d.pose_f, d.part, a.c, a.out);
 }
 
-// the state block as it lies in AlignState::block (base == null: its size)
+// the state block as it lies in tf_volume::align (base == null: its size)
 AlignDev align_carve(void* base, size_t cap_tiles, size_t* bytes) {
   AlignDev d{};
-  d.cap_tiles = (uint32_t)cap_tiles;
-  Layout L;
-  uint8_t* b = static_cast<uint8_t*>(base);
-  const auto take = [&](auto*& p, size_t count) {
-    const size_t at = L.take(count * sizeof(*p));
-    p = b ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(b + at) : nullptr;
-  };
-  take(d.ctl, 1);
-  take(d.pose_d, 12);
-  take(d.pose_f, 12);
-  take(d.pose_r, 12);
-  take(d.log, TF_ALIGN_MAX_EVALUATIONS);
-  take(d.part, (size_t)kAlRow * ((cap_tiles + kAlWaves - 1) / kAlWaves));
-  if (bytes) *bytes = L.size;
+  Carver c(base);
+  c.take(d.ctl, 1);
+  c.take(d.pose_d, 12);
+  c.take(d.pose_f, 12);
+  c.take(d.pose_r, 12);
+  c.take(d.log, TF_ALIGN_MAX_EVALUATIONS);
+  c.take(d.part, (size_t)kAlRow * ((cap_tiles + kAlWaves - 1) / kAlWaves));
+  if (bytes) *bytes = c.L.size;
   return d;
 }
-
-size_t align_pixels(const tf_volume* v) { const AlignCam c = align_cam(v); return (size_t)c.W * (size_t)c.H; }
-size_t align_tiles(const tf_volume* v) {
-  const AlignCam c = align_cam(v);
-  return (size_t)((c.W + 7) / 8) * (size_t)((c.H + 7) / 8);
-}
-
-// first use, or a larger camera since: the block sized for the camera at stride 1
-int align_ensure(tf_volume* v, AlignDev* d) {
-  const size_t tiles = align_tiles(v);
-  if (!v->align.block || v->align.cap_tiles < tiles) {
-    size_t bytes = 0;
-    align_carve(nullptr, tiles, &bytes);
-    if (v->align.block) TF_HIP(hipStreamSynchronize(v->stream));
-    const int rc = v->align.block.alloc(bytes);
-    if (rc) { v->align.cap_tiles = 0; return rc; }
-    TF_HIP(hipMemsetAsync(v->align.block.p, 0, sizeof(AlignCtl), v->stream));
-    v->align.cap_tiles = tiles;
-  }
+int align_dev(tf_volume* v, AlignDev* d) {
+  const auto bytes_of = [](size_t tiles) { size_t n = 0; align_carve(nullptr, tiles, &n); return n; };
+  const int rc = align_ensure(v, v->align, bytes_of, sizeof(AlignCtl));
+  if (rc) return rc;
   *d = align_carve(v->align.block.p, v->align.cap_tiles, nullptr);
   return TF_OK;
 }
 
 }  // namespace
 
-// shared with tf_align_color.hip (tf_volume.h): the camera and the checks of a call's arguments
-// the camera of the depth image: the one tf_raycast_camera set (any size), else the handle's -- as the raycaster's
+// ---- what the four aligners' host sides share (tf_volume.h) ----
+
 AlignCam align_cam(const tf_volume* v) {
   if (v->ray_w > 0) return {v->ray_fx, v->ray_fy, v->ray_cx, v->ray_cy, v->ray_w, v->ray_h};
   return {v->cam.fxi, v->cam.fyi, v->cam.cxi, v->cam.cyi, v->cam.W, v->cam.H};
@@ -340,48 +160,103 @@ int align_check(tf_volume* v, const float* depth, const float* pose, const tf_al
   return TF_OK;
 }
 
+size_t align_pixels(const tf_volume* v) { const AlignCam c = align_cam(v); return (size_t)c.W * (size_t)c.H; }
+size_t align_tiles(const tf_volume* v) {
+  const AlignCam c = align_cam(v);
+  return (size_t)((c.W + 7) / 8) * (size_t)((c.H + 7) / 8);
+}
+
+int align_ensure(tf_volume* v, AlignBlock& b, size_t (*bytes_of)(size_t tiles), size_t clear_bytes) {
+  const size_t tiles = align_tiles(v);
+  if (b.block && b.cap_tiles >= tiles) return TF_OK;
+  if (b.block) TF_HIP(hipStreamSynchronize(v->stream));
+  const int rc = b.block.alloc(bytes_of(tiles));
+  if (rc) { b.cap_tiles = 0; return rc; }
+  TF_HIP(hipMemsetAsync(b.block.p, 0, clear_bytes, v->stream));
+  b.cap_tiles = tiles;
+  return TF_OK;
+}
+
+void align_level(const tf_volume* v, const tf_align_params& p, int level, AlignRowsCommon* rc, AlignSolveCommon* sc) {
+  const bool closing = level == p.n_levels;
+  const int s = p.stride[closing ? p.n_levels - 1 : level];
+  const AlignCam c = align_cam(v);
+  AlignRowsCommon r{};
+  r.fx = c.fx; r.fy = c.fy; r.cxs = c.cx + 0.5f; r.cys = c.cy + 0.5f;
+  r.W = c.W; r.H = c.H; r.stride = s; r.level = level;
+  const int nx = (int)(((long long)r.W + s - 1) / s), ny = (int)(((long long)r.H + s - 1) / s);
+  r.tiles_x = (nx + 7) / 8;
+  const uint32_t n_tiles = (uint32_t)r.tiles_x * (uint32_t)((ny + 7) / 8);  // <= the tiles at stride 1
+  r.min_depth = p.min_depth; r.max_depth = p.max_depth; r.max_residual = p.max_residual; r.huber = p.huber;
+  AlignSolveCommon q{};
+  q.level = level; q.log_level = closing ? p.n_levels - 1 : level; q.stride = s; q.closing = closing;
+  q.last_level = level == p.n_levels - 1; q.n_rows = (n_tiles + kAlWaves - 1) / kAlWaves;
+  q.damping = p.damping; q.eps_t = p.eps_t; q.eps_r = p.eps_r; q.min_valid = p.min_valid;
+  *rc = r;
+  *sc = q;
+}
+
+void align_walk(const tf_volume* v, const tf_align_params& p,
+                const std::function<void(const AlignRowsCommon&, const AlignSolveCommon&)>& evaluate) {
+  for (int l = 0; l <= p.n_levels; ++l) {
+    AlignRowsCommon rc;
+    AlignSolveCommon sc;
+    align_level(v, p, l, &rc, &sc);
+    const int n = sc.closing ? 1 : p.iters[l];
+    for (int it = 0; it < n; ++it) evaluate(rc, sc);
+  }
+}
+
+int align_log(tf_volume* v, const void* d_ctl, const void* d_log, size_t rec_bytes, void* out, int64_t cap, int64_t* n) {
+  if (!n || cap < 0 || (cap > 0 && !out)) { set_error("null argument"); return TF_ERR_INVALID; }
+  *n = 0;
+  TF_DEV_READER(v);
+  if (!d_ctl) return TF_OK;
+  TF_HIP(hipStreamSynchronize(v->stream));
+  AlignCtl c;
+  TF_HIP(hipMemcpy(&c, d_ctl, sizeof(c), hipMemcpyDeviceToHost));
+  const int64_t have = c.n_eval < 0 ? 0 : (c.n_eval > TF_ALIGN_MAX_EVALUATIONS ? TF_ALIGN_MAX_EVALUATIONS : c.n_eval);
+  *n = have;
+  const int64_t m = have < cap ? have : cap;
+  if (m > 0) TF_HIP(hipMemcpy(out, d_log, (size_t)m * rec_bytes, hipMemcpyDeviceToHost));
+  return TF_OK;
+}
+
+int stage_out(tf_volume* v, const Stage& st, size_t at, size_t bytes, void* out) {
+  TF_HIP(hipMemcpyAsync(st.h + at, st.d + at, bytes, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipStreamSynchronize(v->stream));
+  if (out) memcpy(out, st.h + at, bytes);
+  return TF_OK;
+}
+
+void align_release(tf_volume* v) { v->align = AlignBlock{}; }
+
 namespace {
 
-AlignRowsArgs rows_args(const tf_volume* v, const AlignDev& d, const tf_align_params& p, const float* d_depth, int level,
-                        uint32_t* n_tiles) {
+AlignRowsArgs rows_args(const tf_volume* v, const AlignRowsCommon& rc, const float* d_depth) {
   AlignRowsArgs a{};
-  const int s = p.stride[level < p.n_levels ? level : p.n_levels - 1];
+  a.c = rc;
   a.depth = d_depth;
-  const AlignCam c = align_cam(v);
-  a.fx = c.fx; a.fy = c.fy; a.cxs = c.cx + 0.5f; a.cys = c.cy + 0.5f;
-  a.W = c.W; a.H = c.H; a.stride = s; a.level = level;
-  const int nx = (int)(((long long)a.W + s - 1) / s), ny = (int)(((long long)a.H + s - 1) / s);
-  a.tiles_x = (nx + 7) / 8;
-  *n_tiles = (uint32_t)a.tiles_x * (uint32_t)((ny + 7) / 8);  // <= the tiles at stride 1
-  a.min_depth = p.min_depth; a.max_depth = p.max_depth; a.max_residual = p.max_residual; a.huber = p.huber; a.res = v->res;
-  a.plane = (size_t)a.W * a.H;
+  a.res = v->res;
+  a.plane = (size_t)rc.W * rc.H;
   return a;
 }
 
 // every launch of one alignment: begin, then (rows, solve) per step and once more to close
 int align_enqueue(tf_volume* v, const float* d_depth, const float* pose, const tf_align_params& p, tf_align_result* d_result) {
   AlignDev d;
-  int rc = align_ensure(v, &d);
+  int rc = align_dev(v, &d);
   if (rc) return rc;
   hipStream_t st = v->stream;
   AlignPose P;
   memcpy(P.p, pose, sizeof(P.p));
   hipLaunchKernelGGL(k_align_begin, dim3(1), dim3(64), 0, st, d, P, 0);
-  for (int l = 0; l <= p.n_levels; ++l) {
-    const bool closing = l == p.n_levels;
-    uint32_t n_tiles = 0;
-    AlignRowsArgs ra = rows_args(v, d, p, d_depth, l, &n_tiles);
+  align_walk(v, p, [&](const AlignRowsCommon& c, const AlignSolveCommon& sc) {
+    AlignRowsArgs ra = rows_args(v, c, d_depth);
     ra.pose = d.pose_f; ra.state = &d.ctl->state; ra.part = d.part;
-    AlignSolveArgs sa{};
-    sa.level = l; sa.log_level = closing ? p.n_levels - 1 : l; sa.stride = ra.stride; sa.closing = closing;
-    sa.last_level = l == p.n_levels - 1; sa.n_rows = (n_tiles + kAlWaves - 1) / kAlWaves;
-    sa.damping = p.damping; sa.eps_t = p.eps_t; sa.eps_r = p.eps_r; sa.min_valid = p.min_valid; sa.out = d_result;
-    const int n = closing ? 1 : p.iters[l];
-    for (int it = 0; it < n; ++it) {
-      hipLaunchKernelGGL(k_align_rows, dim3((n_tiles + kAlWaves - 1) / kAlWaves), dim3(kAlWaves * 64), 0, st, v->dev, ra);
-      hipLaunchKernelGGL(k_align_solve, dim3(1), dim3(256), 0, st, d, sa);
-    }
-  }
+    hipLaunchKernelGGL(k_align_rows, dim3(sc.n_rows), dim3(kAlWaves * 64), 0, st, v->dev, ra);
+    hipLaunchKernelGGL(k_align_solve, dim3(1), dim3(256), 0, st, d, AlignSolveArgs{sc, d_result});
+  });
   TF_HIP(hipGetLastError());
   return TF_OK;
 }
@@ -389,13 +264,15 @@ int align_enqueue(tf_volume* v, const float* d_depth, const float* pose, const t
 int residuals_enqueue(tf_volume* v, const float* d_depth, const float* pose, const tf_align_params& p, float* d_r,
                       float* d_grad3, uint32_t* d_flags) {
   AlignDev d;
-  int rc = align_ensure(v, &d);
+  int rc = align_dev(v, &d);
   if (rc) return rc;
   hipStream_t st = v->stream;
-  uint32_t n_tiles = 0;
-  AlignRowsArgs ra = rows_args(v, d, p, d_depth, 0, &n_tiles);
+  AlignRowsCommon c;
+  AlignSolveCommon sc;
+  align_level(v, p, 0, &c, &sc);
+  AlignRowsArgs ra = rows_args(v, c, d_depth);
   ra.pose = d.pose_r; ra.r = d_r; ra.grad = d_grad3; ra.flags = d_flags;
-  if (ra.stride > 1) {  // pixels that are not sampled
+  if (c.stride > 1) {  // pixels that are not sampled
     if (d_r) TF_HIP(hipMemsetAsync(d_r, 0, 4 * ra.plane, st));
     if (d_grad3) TF_HIP(hipMemsetAsync(d_grad3, 0, 12 * ra.plane, st));
     if (d_flags) TF_HIP(hipMemsetAsync(d_flags, 0, 4 * ra.plane, st));
@@ -403,14 +280,12 @@ int residuals_enqueue(tf_volume* v, const float* d_depth, const float* pose, con
   AlignPose P;
   memcpy(P.p, pose, sizeof(P.p));
   hipLaunchKernelGGL(k_align_begin, dim3(1), dim3(64), 0, st, d, P, 1);
-  hipLaunchKernelGGL(k_align_rows, dim3((n_tiles + kAlWaves - 1) / kAlWaves), dim3(kAlWaves * 64), 0, st, v->dev, ra);
+  hipLaunchKernelGGL(k_align_rows, dim3(sc.n_rows), dim3(kAlWaves * 64), 0, st, v->dev, ra);
   TF_HIP(hipGetLastError());
   return TF_OK;
 }
 
 }  // namespace
-
-void align_release(tf_volume* v) { v->align = AlignState{}; }
 
 }  // namespace tf
 
@@ -452,26 +327,13 @@ int tf_align_frame(tf_volume* v, const float* depth, const float pose[12], const
   Stage sg;
   if ((rc = stage_begin(v, v->scratch, L.size, L.size, &sg)) || (rc = stage_in(v, sg, o_d, depth, 4 * P))) return rc;
   if ((rc = align_enqueue(v, sg.dp<const float>(o_d), pose, *params, sg.dp<tf_align_result>(o_r)))) return rc;
-  TF_HIP(hipMemcpyAsync(sg.h + o_r, sg.d + o_r, sizeof(tf_align_result), hipMemcpyDeviceToHost, v->stream));
-  TF_HIP(hipStreamSynchronize(v->stream));
-  memcpy(result, sg.h + o_r, sizeof(tf_align_result));
-  return TF_OK;
+  return stage_out(v, sg, o_r, sizeof(tf_align_result), result);
 }
 
 int tf_align_log(tf_volume* v, tf_align_iter* out, int64_t cap, int64_t* n) {
-  if (!v || !n || cap < 0 || (cap > 0 && !out)) { set_error("null argument"); return TF_ERR_INVALID; }
-  *n = 0;
-  TF_DEV_READER(v);
-  if (!v->align.block) return TF_OK;
-  const AlignDev d = align_carve(v->align.block.p, v->align.cap_tiles, nullptr);
-  TF_HIP(hipStreamSynchronize(v->stream));
-  AlignCtl c;
-  TF_HIP(hipMemcpy(&c, d.ctl, sizeof(c), hipMemcpyDeviceToHost));
-  const int64_t have = c.n_eval < 0 ? 0 : (c.n_eval > TF_ALIGN_MAX_EVALUATIONS ? TF_ALIGN_MAX_EVALUATIONS : c.n_eval);
-  *n = have;
-  const int64_t m = have < cap ? have : cap;
-  if (m > 0) TF_HIP(hipMemcpy(out, d.log, (size_t)m * sizeof(tf_align_iter), hipMemcpyDeviceToHost));
-  return TF_OK;
+  if (!v) { set_error("null argument"); return TF_ERR_INVALID; }
+  const AlignDev d = v->align.block ? align_carve(v->align.block.p, v->align.cap_tiles, nullptr) : AlignDev{};
+  return align_log(v, d.ctl, d.log, sizeof(tf_align_iter), out, cap, n);
 }
 
 int tf_align_residuals_device(tf_volume* v, const float* d_depth, const float pose[12], const tf_align_params* params,
@@ -497,8 +359,7 @@ int tf_align_residuals(tf_volume* v, const float* depth, const float pose[12], c
   rc = residuals_enqueue(v, sg.dp<const float>(o_d), pose, *params, r ? sg.dp<float>(o_r) : nullptr,
                          grad3 ? sg.dp<float>(o_g) : nullptr, flags ? sg.dp<uint32_t>(o_f) : nullptr);
   if (rc) return rc;
-  TF_HIP(hipMemcpyAsync(sg.h + o_r, sg.d + o_r, L.size - o_r, hipMemcpyDeviceToHost, v->stream));
-  TF_HIP(hipStreamSynchronize(v->stream));
+  if ((rc = stage_out(v, sg, o_r, L.size - o_r, nullptr))) return rc;
   if (r) memcpy(r, sg.h + o_r, 4 * P);
   if (grad3) memcpy(grad3, sg.h + o_g, 12 * P);
   if (flags) memcpy(flags, sg.h + o_f, 4 * P);

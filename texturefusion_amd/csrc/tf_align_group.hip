@@ -11,16 +11,15 @@
 //                   the frames added in ascending order, the 6 x 6 solve by one lane (tf_align_solve.h), the update of
 //                   every frame of the body (tf_align_group_solve.h), a log record, the result
 //
-// Per sampled pixel of frame k everything up to g, q and the flags is k_align_rows' text, operation for operation (the
-// per-pixel body is copied from tf_align.hip, whose header comment is the specification; -ffp-contract=off).  The one
-// difference is the lever of the rotational part: the twist of a body is taken about its anchor's camera centre (the
+// Per sampled pixel of frame k everything up to g, q and the flags is k_align_rows' row (al_sdf_row, tf_align_rows.h;
+// tf_align.hip's header comment is the specification; -ffp-contract=off).  The one difference is the lever of the
+// rotational part: the twist of a body is taken about its anchor's camera centre (the
 // anchor is the body's first frame).
 //   anchor:        J = [g, q x g]                                             -- tf_align_frame's row
 //   another frame: a = (t_k - t_anchor) + q componentwise in f32, from the two f32 poses the rows are sampled at,
 //                  J = (g.x, g.y, g.z, a.y g.z - a.z g.y, a.z g.x - a.x g.z, a.x g.y - a.y g.x)
 //   w, wJ, wr as tf_align.hip's.
-// Sums: a frame's 31 sums are formed exactly as k_align_rows + k_align_solve form them (the wave tree of tf_align_tree.h,
-// the eight tiles of a workgroup in wave order, the rows g, g + 8, .. ascending, then the eight groups in order); a body's
+// Sums: a frame's 31 sums are formed by the functions k_align_rows and k_align_solve form them with (tf_align_rows.h); a body's
 // sums are its frames' sums added in ascending frame order, starting from the first frame's.  A body of one frame has
 // tf_align_frame's sums, steps, log and result bit for bit.
 // Step of a body with anchor centre c (the anchor's t before the step), xi = -(A + damping diag A)^-1 b = (v, w),
@@ -35,11 +34,8 @@
 #include <math.h>
 #include <string.h>
 
-#include <type_traits>
-
 #include "tf_align_group_solve.h"
-#include "tf_align_tree.h"
-#include "tf_ray_devfn.h"
+#include "tf_align_rows.h"
 #include "tf_volume.h"
 
 #pragma clang fp contract(off)
@@ -51,16 +47,8 @@ constexpr int kGaMax = TF_ALIGN_GROUP_MAX_FRAMES;
 constexpr int kGaResultWords = (int)(sizeof(tf_align_group_result) / 4);
 static_assert(sizeof(tf_align_group_result) % 4 == 0 && kGaResultWords <= 256 && 12 * kGaMax <= 256, "k_galign_begin");
 
-struct GAlignCtl {  // one per body
-  uint32_t state;   // bit 0: stopped (too few / singular), bits 8..: levels finished
-  int32_t status;
-  int32_t n_eval;
-  int32_t n_valid_first;
-  float rms_first;
-  uint32_t pad[3];
-};
 struct GAlignDev {
-  GAlignCtl* ctl;               // [kGaMax]
+  AlignCtl* ctl;                // [kGaMax], one per body
   double* pose_d;               // [kGaMax][12] every frame's pose between iterations
   float* pose_f;                // [kGaMax][12] the same rounded: what k_galign_rows samples at
   tf_align_group_result* res;   // the result of tf_align_unit_group (the other forms bring their own)
@@ -76,35 +64,26 @@ struct GAlignTable {
 struct GAlignPoses { float p[kGaMax * 12]; };
 
 struct GAlignRowsArgs {
+  AlignRowsCommon c;
   const float* depth[kGaMax];
   GAlignTable tab;
   const float* pose;      // pose_f of the state block
-  const GAlignCtl* ctl;
-  float fx, fy, cxs, cys;
-  int W, H, tiles_x, stride, level;
-  float min_depth, max_depth, max_residual, huber, res;
+  const AlignCtl* ctl;
+  float res;
   double* part;
   uint32_t rows_cap;
 };
 struct GAlignSolveArgs {
+  AlignSolveCommon c;  // n_rows: workgroups of a frame in the rows launch
   GAlignTable tab;
-  int level, log_level, stride, closing, last_level;
-  uint32_t n_rows;  // workgroups of a frame in the rows launch
-  float damping, eps_t, eps_r;
-  int min_valid;
   tf_align_group_result* out;
 };
-
-__device__ __forceinline__ bool gal_idle(const uint32_t* state, int level) {
-  const uint32_t st = *state;
-  return (st & 1u) || (uint32_t)level < (st >> 8);
-}
 
 __global__ __launch_bounds__(256) void k_galign_begin(GAlignDev d, GAlignPoses p, GAlignTable tab, tf_align_group_result* out) {
   const int i = threadIdx.x;
   if (i < 12 * tab.n_frames) { const float x = p.p[i]; d.pose_d[i] = (double)x; d.pose_f[i] = x; }
   if (i < kGaMax) {
-    GAlignCtl c{};
+    AlignCtl c{};
     c.status = TF_ALIGN_MAX_ITERS;
     d.ctl[i] = c;
   }
@@ -115,114 +94,41 @@ __global__ __launch_bounds__(256) void k_galign_begin(GAlignDev d, GAlignPoses p
 // (resources: tests/test_kernel_resources_align_group.py)
 __global__ __launch_bounds__(kAlWaves * 64) void k_galign_rows(VolumeDev v, GAlignRowsArgs a) {
   const int fk = blockIdx.y, fa = a.tab.anchor[fk];
-  if (gal_idle(&a.ctl[a.tab.body[fk]].state, a.level)) return;
-  // (a tile beyond the last one of the level lies below the image: none of its lanes is inside)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int tile = blockIdx.x * kAlWaves + wave;
-  const long long X = (long long)((tile % a.tiles_x) * 8 + (lane & 7)) * a.stride;
-  const long long Y = (long long)((tile / a.tiles_x) * 8 + (lane >> 3)) * a.stride;
-  const bool in = X < a.W && Y < a.H;
+  if (al_idle(&a.ctl[a.tab.body[fk]].state, a.c.level)) return;
+  const AlPixel px = al_pixel(a.c);
   const float* P = a.pose + 12 * fk;
-  uint32_t fl = 0;
-  float s = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, qx = 0.f, qy = 0.f, qz = 0.f;
-  if (in) {
-    const float z = a.depth[fk][(size_t)Y * a.W + (size_t)X];
-    if (isfinite(z) && z >= a.min_depth && z <= a.max_depth) {
-      fl = 1u;
-      const float res = a.res, ir = 1.0f / res;
-      const float dcx = ((float)(int)X - a.cxs) / a.fx, dcy = ((float)(int)Y - a.cys) / a.fy;
-      const float pcx = dcx * z, pcy = dcy * z;
-      qx = (P[0] * pcx + P[1] * pcy) + P[2] * z;
-      qy = (P[4] * pcx + P[5] * pcy) + P[6] * z;
-      qz = (P[8] * pcx + P[9] * pcy) + P[10] * z;
-      const float wx = P[3] + qx, wy = P[7] + qy, wz = P[11] + qz;
-      ChunkCache cc{INT_MIN, INT_MIN, INT_MIN, kInvalidSlot};
-      float sc = 0.f;
-      if (tri_sample<false>(v, cc, wx, wy, wz, ir, &sc)) {
-        fl |= 2u;
-        s = sc;
-        // tap k: axis k >> 1, minus / plus by k & 1, as k_align_rows
-        float sp0 = 0.f, sp1 = 0.f, sp2 = 0.f, sm0 = 0.f, sm1 = 0.f, sm2 = 0.f;
-        bool ok = true;
-#pragma unroll 1
-        for (int k = 0; k < 6; ++k) {
-          const int ax = k >> 1;
-          float t = 0.f;
-          const float h = (k & 1) ? res : -res;  // (a + (-b) is a - b)
-          ChunkCache ct = cc;  // every tap starts from the centre's chunk
-          const bool okk = tri_sample<false>(v, ct, ax == 0 ? wx + h : wx, ax == 1 ? wy + h : wy, ax == 2 ? wz + h : wz, ir, &t);
-          ok = ok && okk;
-          if (k == 0) sm0 = t; else if (k == 1) sp0 = t; else if (k == 2) sm1 = t; else if (k == 3) sp1 = t;
-          else if (k == 4) sm2 = t; else sp2 = t;
-        }
-        if (ok) {
-          fl |= 4u;
-          const float h2 = 0.5f / res;
-          gx = (sp0 - sm0) * h2; gy = (sp1 - sm1) * h2; gz = (sp2 - sm2) * h2;
-          if (fabsf(s) <= a.max_residual) fl |= 8u;
-        }
-      }
-    }
-  }
-  const bool valid = fl == 15u;
+  AlSdfRow row{};
+  if (px.in) row = al_sdf_row<false>(v, a.c, a.res, px, a.depth[fk][(size_t)px.Y * a.c.W + (size_t)px.X], P);
   // the lever: q for the anchor, (t_k - t_anchor) + q for a later frame of the body (uniform over the workgroup)
-  float lx = qx, ly = qy, lz = qz;
+  float lx = row.qx, ly = row.qy, lz = row.qz;
   if (fa != fk) {
     const float* PA = a.pose + 12 * fa;
-    lx = (P[3] - PA[3]) + qx; ly = (P[7] - PA[7]) + qy; lz = (P[11] - PA[11]) + qz;
+    lx = (P[3] - PA[3]) + row.qx; ly = (P[7] - PA[7]) + row.qy; lz = (P[11] - PA[11]) + row.qz;
   }
-  float J[6] = {gx, gy, gz, ly * gz - lz * gy, lz * gx - lx * gz, lx * gy - ly * gx};
-  const float ar = fabsf(s);
-  float w = (a.huber == 0.f || ar <= a.huber) ? 1.0f : a.huber / ar;
-  float r = s;
-  if (!valid) {  // an exact zero in every term
-    w = 0.f; r = 0.f;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) J[i] = 0.f;
-  }
-  // the 31 sums of the tile through the wave tree (tf_align_tree.h): lane l ends up with entry al_entry(l)
-  const double total = al_tile_sum(J, w, r, valid ? 1.0f : 0.0f, in ? 1.0f : 0.0f, lane);
-  const int e = al_entry(lane);
-  // the workgroup's eight tiles in wave order, one plain-stored row per workgroup
   __shared__ double wsum[kAlWaves][kAlRow];
-  if (!(lane & 1)) wsum[wave][e] = total;
-  __syncthreads();
-  if (threadIdx.x < (unsigned)kAlSums) {
-    double t = wsum[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < kAlWaves; ++k) t += wsum[k][threadIdx.x];
-    a.part[((size_t)fk * a.rows_cap + blockIdx.x) * kAlRow + threadIdx.x] = t;
-  }
+  al_row_sums(wsum, 0, px, row.gx, row.gy, row.gz, lx, ly, lz, row.s, a.c.huber, row.fl == 15u, px.in);
+  al_store_rows(wsum, a.part + ((size_t)fk * a.rows_cap + blockIdx.x) * kAlRow);
 }
 
 __global__ __launch_bounds__(256) void k_galign_solve(GAlignDev d, GAlignSolveArgs a) {
   const int body = blockIdx.x;
-  GAlignCtl* ctl = d.ctl + body;
-  if (gal_idle(&ctl->state, a.level)) return;
+  AlignCtl* ctl = d.ctl + body;
+  if (al_idle(&ctl->state, a.c.level)) return;
   const bool first_eval = ctl->n_eval == 0;  // (read by every thread ahead of the barriers; lane 0 writes behind them)
-  // per frame of the body, in ascending order: thread (e = tid & 31, g = tid >> 5) adds entry e of the frame's rows g, g + 8,
-  // g + 16, .. in ascending order, thread e then the eight groups in order -- k_align_solve's additions -- and adds the
+  // per frame of the body, in ascending order: the frame's rows through k_align_solve's additions, thread e then adds the
   // frame's sum to the body's.  (One frame after the other: seven accumulators side by side in one loop over the rows
   // were measured slower, 66 against 47 us for an evaluation of one frame at stride 1.)
   __shared__ double red[8][kAlRow];
   __shared__ double tot[kAlRow];
-  const uint32_t tid = threadIdx.x, e = tid & 31u, g = tid >> 5;
+  const uint32_t tid = threadIdx.x;
   double sum = 0.0;
   bool have = false;
 #pragma unroll 1
   for (int k = 0; k < a.tab.n_frames; ++k) {
     if (a.tab.body[k] != body) continue;
-    const double* part = d.part + (size_t)k * d.rows_cap * kAlRow;
-    double acc = 0.0;
-    if (e < (uint32_t)kAlSums)
-#pragma unroll 8
-      for (uint32_t t = g; t < a.n_rows; t += 8u) acc += part[(size_t)t * kAlRow + e];
-    red[g][e] = acc;
-    __syncthreads();
+    al_add_rows(d.part + (size_t)k * d.rows_cap * kAlRow, a.c.n_rows, red);
     if (tid < (uint32_t)kAlSums) {
-      double t = red[0][tid];
-#pragma unroll
-      for (int j = 1; j < 8; ++j) t += red[j][tid];
+      const double t = al_total(red, (int)tid);
       sum = have ? sum + t : t;
       if (tid == (uint32_t)kAlNv) {
         a.out->frame_valid_last[k] = (int)t;
@@ -235,57 +141,19 @@ __global__ __launch_bounds__(256) void k_galign_solve(GAlignDev d, GAlignSolveAr
   if (tid < (uint32_t)kAlRow) tot[tid] = sum;
   __syncthreads();
   if (tid != 0) return;
-  double S[kAlSums];
-#pragma unroll
-  for (int i = 0; i < kAlSums; ++i) S[i] = tot[i];
-  GAlignCtl c = *ctl;
-  const int n_valid = (int)S[kAlNv], n_sampled = (int)S[kAlNs];
-  const float rms = n_valid > 0 ? (float)sqrt(S[kAlR2] / (double)n_valid) : 0.f;
-  tf_align_iter* rec = d.log + (size_t)body * TF_ALIGN_MAX_EVALUATIONS +
-                       (c.n_eval < TF_ALIGN_MAX_EVALUATIONS ? c.n_eval : TF_ALIGN_MAX_EVALUATIONS - 1);
-  rec->level = a.log_level; rec->stride = a.stride; rec->n_sampled = n_sampled; rec->n_valid = n_valid;
-  rec->sum_r2 = S[kAlR2]; rec->sum_wr2 = S[kAlWr2];
-#pragma unroll
-  for (int i = 0; i < 21; ++i) rec->A[i] = S[kAlA + i];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) { rec->b[i] = S[kAlB + i]; rec->xi[i] = 0.0; }
+  AlignCtl c = *ctl;
+  tf_align_iter* rec = al_record(d.log + (size_t)body * TF_ALIGN_MAX_EVALUATIONS, c);
   const int anchor = a.tab.first[body];
-  double cen[3];
-  {
-    const double* pa = d.pose_d + 12 * anchor;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) rec->pose[i] = pa[i];
-    cen[0] = pa[3]; cen[1] = pa[7]; cen[2] = pa[11];
-  }
-  if (c.n_eval == 0) { c.n_valid_first = n_valid; c.rms_first = rms; }
-  c.n_eval += 1;
-  bool step = false;
-  double xi[6], E[9];
-  if (n_valid < a.min_valid) {
-    c.status = TF_ALIGN_TOO_FEW;
-    c.state |= 1u;
-  } else if (!a.closing) {
-    if (!align_solve6(S + kAlA, S + kAlB, (double)a.damping, xi)) {
-      c.status = TF_ALIGN_SINGULAR;
-      c.state |= 1u;
-    } else {
-      step = true;
-      align_rodrigues(xi + 3, E);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) rec->xi[i] = xi[i];
-      const double nt = sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]);
-      const double nr = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
-      if (nt < (double)a.eps_t && nr < (double)a.eps_r) {
-        c.state = (c.state & 0xFFu) | ((uint32_t)(a.level + 1) << 8);
-        if (a.last_level) c.status = TF_ALIGN_CONVERGED;
-      }
-    }
-  }
+  const double* pa = d.pose_d + 12 * anchor;
+  const double cen[3] = {pa[3], pa[7], pa[11]};
+  double A[21], b[6], xi[6], E[9];
+  const AlEval ev = al_fill_iter(rec, a.c, [&](int i) { return tot[i]; }, pa, A, b);
+  al_count(c, ev);
+  const bool step = al_decide(c, a.c, ev.n_valid, A, b, rec, xi);
+  if (step) align_rodrigues(xi + 3, E);
   *ctl = c;
   tf_align_result* out = a.out->body + body;
-  out->status = c.status; out->evaluations = c.n_eval; out->n_sampled = n_sampled;
-  out->n_valid_first = c.n_valid_first; out->n_valid_last = n_valid;
-  out->rms_first = c.rms_first; out->rms_last = rms;
+  al_fill_result(out, c, ev);
   // every frame of the body: the step about the anchor's centre of before the step, the pose to the result
 #pragma unroll 1
   for (int k = anchor; k < a.tab.n_frames; ++k) {
@@ -295,54 +163,33 @@ __global__ __launch_bounds__(256) void k_galign_solve(GAlignDev d, GAlignSolveAr
     for (int i = 0; i < 12; ++i) pose[i] = d.pose_d[12 * k + i];
     if (step) {
       align_update_about(pose, E, cen, xi);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) { d.pose_d[12 * k + i] = pose[i]; d.pose_f[12 * k + i] = (float)pose[i]; }
+      al_keep_pose(d.pose_d + 12 * k, d.pose_f + 12 * k, pose);
     }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) a.out->pose[k][i] = (float)pose[i];
-    if (k == anchor)
-#pragma unroll
-      for (int i = 0; i < 12; ++i) out->pose[i] = (float)pose[i];
+    al_put_pose(a.out->pose[k], pose);
+    if (k == anchor) al_put_pose(out->pose, pose);
   }
 }
 
-// the state block as it lies in AlignGroupState::block (base == null: its size)
+// the state block as it lies in tf_volume::align_group (base == null: its size)
 GAlignDev galign_carve(void* base, size_t cap_tiles, size_t* bytes) {
   GAlignDev d{};
   d.rows_cap = (uint32_t)((cap_tiles + kAlWaves - 1) / kAlWaves);
-  Layout L;
-  uint8_t* b = static_cast<uint8_t*>(base);
-  const auto take = [&](auto*& p, size_t count) {
-    const size_t at = L.take(count * sizeof(*p));
-    p = b ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(b + at) : nullptr;
-  };
-  take(d.ctl, kGaMax);
-  take(d.pose_d, 12 * kGaMax);
-  take(d.pose_f, 12 * kGaMax);
-  take(d.res, 1);
-  take(d.log, (size_t)kGaMax * TF_ALIGN_MAX_EVALUATIONS);
-  take(d.part, (size_t)kGaMax * d.rows_cap * kAlRow);
-  if (bytes) *bytes = L.size;
+  Carver c(base);
+  c.take(d.ctl, kGaMax);
+  c.take(d.pose_d, 12 * kGaMax);
+  c.take(d.pose_f, 12 * kGaMax);
+  c.take(d.res, 1);
+  c.take(d.log, (size_t)kGaMax * TF_ALIGN_MAX_EVALUATIONS);
+  c.take(d.part, (size_t)kGaMax * d.rows_cap * kAlRow);
+  if (bytes) *bytes = c.L.size;
   return d;
 }
-
-size_t galign_pixels(const tf_volume* v) { const AlignCam c = align_cam(v); return (size_t)c.W * (size_t)c.H; }
-
-// first use, or a larger camera since: the block sized for seven frames of the camera at stride 1
+// the block sized for seven frames of the camera at stride 1
 int galign_ensure(tf_volume* v, GAlignDev* d) {
-  const AlignCam c = align_cam(v);
-  const size_t tiles = (size_t)((c.W + 7) / 8) * (size_t)((c.H + 7) / 8);
-  AlignGroupState& s = v->align_group;
-  if (!s.block || s.cap_tiles < tiles) {
-    size_t bytes = 0;
-    galign_carve(nullptr, tiles, &bytes);
-    if (s.block) TF_HIP(hipStreamSynchronize(v->stream));
-    const int rc = s.block.alloc(bytes);
-    if (rc) { s.cap_tiles = 0; return rc; }
-    TF_HIP(hipMemsetAsync(s.block.p, 0, kGaMax * sizeof(GAlignCtl), v->stream));
-    s.cap_tiles = tiles;
-  }
-  *d = galign_carve(s.block.p, s.cap_tiles, nullptr);
+  const auto bytes_of = [](size_t tiles) { size_t n = 0; galign_carve(nullptr, tiles, &n); return n; };
+  const int rc = align_ensure(v, v->align_group, bytes_of, kGaMax * sizeof(AlignCtl));
+  if (rc) return rc;
+  *d = galign_carve(v->align_group.block.p, v->align_group.cap_tiles, nullptr);
   return TF_OK;
 }
 
@@ -376,38 +223,21 @@ int galign_enqueue(tf_volume* v, const GAlignDev& d, const GAlignTable& tab, con
   GAlignPoses P{};
   memcpy(P.p, poses12, sizeof(float) * 12 * (size_t)tab.n_frames);
   hipLaunchKernelGGL(k_galign_begin, dim3(1), dim3(256), 0, st, d, P, tab, d_result);
-  const AlignCam c = align_cam(v);
-  for (int l = 0; l <= p.n_levels; ++l) {
-    const bool closing = l == p.n_levels;
-    GAlignRowsArgs ra{};
-    for (int k = 0; k < tab.n_frames; ++k) ra.depth[k] = d_depth[k];
-    ra.tab = tab; ra.pose = d.pose_f; ra.ctl = d.ctl; ra.part = d.part; ra.rows_cap = d.rows_cap;
-    const int s = p.stride[closing ? p.n_levels - 1 : l];
-    ra.fx = c.fx; ra.fy = c.fy; ra.cxs = c.cx + 0.5f; ra.cys = c.cy + 0.5f;
-    ra.W = c.W; ra.H = c.H; ra.stride = s; ra.level = l;
-    const int nx = (int)(((long long)ra.W + s - 1) / s), ny = (int)(((long long)ra.H + s - 1) / s);
-    ra.tiles_x = (nx + 7) / 8;
-    const uint32_t n_tiles = (uint32_t)ra.tiles_x * (uint32_t)((ny + 7) / 8);  // <= the tiles at stride 1
-    ra.min_depth = p.min_depth; ra.max_depth = p.max_depth; ra.max_residual = p.max_residual; ra.huber = p.huber;
-    ra.res = v->res;
-    GAlignSolveArgs sa{};
-    sa.tab = tab;
-    sa.level = l; sa.log_level = closing ? p.n_levels - 1 : l; sa.stride = s; sa.closing = closing;
-    sa.last_level = l == p.n_levels - 1; sa.n_rows = (n_tiles + kAlWaves - 1) / kAlWaves;
-    sa.damping = p.damping; sa.eps_t = p.eps_t; sa.eps_r = p.eps_r; sa.min_valid = p.min_valid; sa.out = d_result;
-    const int n = closing ? 1 : p.iters[l];
-    for (int it = 0; it < n; ++it) {
-      hipLaunchKernelGGL(k_galign_rows, dim3(sa.n_rows, (uint32_t)tab.n_frames), dim3(kAlWaves * 64), 0, st, v->dev, ra);
-      hipLaunchKernelGGL(k_galign_solve, dim3((uint32_t)tab.n_bodies), dim3(256), 0, st, d, sa);
-    }
-  }
+  GAlignRowsArgs ra{};
+  for (int k = 0; k < tab.n_frames; ++k) ra.depth[k] = d_depth[k];
+  ra.tab = tab; ra.pose = d.pose_f; ra.ctl = d.ctl; ra.res = v->res; ra.part = d.part; ra.rows_cap = d.rows_cap;
+  align_walk(v, p, [&](const AlignRowsCommon& c, const AlignSolveCommon& sc) {
+    ra.c = c;
+    hipLaunchKernelGGL(k_galign_rows, dim3(sc.n_rows, (uint32_t)tab.n_frames), dim3(kAlWaves * 64), 0, st, v->dev, ra);
+    hipLaunchKernelGGL(k_galign_solve, dim3((uint32_t)tab.n_bodies), dim3(256), 0, st, d, GAlignSolveArgs{sc, tab, d_result});
+  });
   TF_HIP(hipGetLastError());
   return TF_OK;
 }
 
 }  // namespace
 
-void align_group_release(tf_volume* v) { v->align_group = AlignGroupState{}; }
+void align_group_release(tf_volume* v) { v->align_group = AlignBlock{}; }
 
 }  // namespace tf
 
@@ -432,7 +262,7 @@ int tf_align_group(tf_volume* v, int32_t n_frames, const float* const* depth, co
   int rc = galign_check(v, n_frames, depth, poses12, body, params, result, &tab);
   if (rc) return rc;
   TF_DEV_READER(v);
-  const size_t P = galign_pixels(v);
+  const size_t P = align_pixels(v);
   Layout L;
   size_t o_d[kGaMax] = {};
   for (int k = 0; k < n_frames; ++k) o_d[k] = L.take(4 * P);
@@ -447,29 +277,17 @@ int tf_align_group(tf_volume* v, int32_t n_frames, const float* const* depth, co
   GAlignDev d;
   if ((rc = galign_ensure(v, &d))) return rc;
   if ((rc = galign_enqueue(v, d, tab, d_depth, poses12, *params, sg.dp<tf_align_group_result>(o_r)))) return rc;
-  TF_HIP(hipMemcpyAsync(sg.h + o_r, sg.d + o_r, sizeof(tf_align_group_result), hipMemcpyDeviceToHost, v->stream));
-  TF_HIP(hipStreamSynchronize(v->stream));
-  memcpy(result, sg.h + o_r, sizeof(tf_align_group_result));
-  return TF_OK;
+  return stage_out(v, sg, o_r, sizeof(tf_align_group_result), result);
 }
 
 int tf_align_group_log(tf_volume* v, int32_t body, tf_align_iter* out, int64_t cap, int64_t* n) {
-  if (!v || !n || cap < 0 || (cap > 0 && !out)) { set_error("null argument"); return TF_ERR_INVALID; }
+  if (!v) { set_error("null argument"); return TF_ERR_INVALID; }
   if (body < 0 || body >= kGaMax) { set_error("align group: body must be 0..6"); return TF_ERR_INVALID; }
-  *n = 0;
-  TF_DEV_READER(v);
-  if (!v->align_group.block) return TF_OK;
-  const GAlignDev d = galign_carve(v->align_group.block.p, v->align_group.cap_tiles, nullptr);
-  TF_HIP(hipStreamSynchronize(v->stream));
-  GAlignCtl c;  // (a body the last call did not have was cleared by its begin: no records)
-  TF_HIP(hipMemcpy(&c, d.ctl + body, sizeof(c), hipMemcpyDeviceToHost));
-  const int64_t have = c.n_eval < 0 ? 0 : (c.n_eval > TF_ALIGN_MAX_EVALUATIONS ? TF_ALIGN_MAX_EVALUATIONS : c.n_eval);
-  *n = have;
-  const int64_t m = have < cap ? have : cap;
-  if (m > 0)
-    TF_HIP(hipMemcpy(out, d.log + (size_t)body * TF_ALIGN_MAX_EVALUATIONS, (size_t)m * sizeof(tf_align_iter),
-                     hipMemcpyDeviceToHost));
-  return TF_OK;
+  const AlignBlock& s = v->align_group;
+  if (!s.block) return align_log(v, nullptr, nullptr, 0, out, cap, n);
+  const GAlignDev d = galign_carve(s.block.p, s.cap_tiles, nullptr);
+  // (a body the last call did not have was cleared by its begin: no records)
+  return align_log(v, d.ctl + body, d.log + (size_t)body * TF_ALIGN_MAX_EVALUATIONS, sizeof(tf_align_iter), out, cap, n);
 }
 
 int tf_align_unit_group(tf_volume* v, tf_unit_group* group, int rigid, const tf_align_params* params,

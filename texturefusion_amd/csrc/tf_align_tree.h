@@ -1,6 +1,6 @@
-// tf_align_tree.h -- the sums of one 8 x 8 tile of alignment rows, shared by tf_align.hip and tf_align_color.hip: the table
+// tf_align_tree.h -- the sums of one 8 x 8 tile of alignment rows, shared by the four aligners through tf_align_rows.h: the table
 // of operand pairs, one level of the wave tree, and the tree itself.  Device only; including files are built with
-// -ffp-contract=off.  The order of every addition is fixed here (tf_align.hip's header comment states it).
+// -ffp-contract=off.  The order of every addition is fixed here (tf_align_rows.h's header comment states it).
 #pragma once
 
 #include <hip/hip_runtime.h>

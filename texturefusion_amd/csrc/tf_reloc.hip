@@ -20,7 +20,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <type_traits>
 #include <vector>
 
 #include "tf_reloc_score.h"
@@ -159,17 +158,12 @@ __global__ __launch_bounds__(kRlThreads) void k_reloc_score(RelocScoreArgs a) {
 // the index as it lies in RelocState::block (base == null: its size)
 RelocDev reloc_carve(void* base, size_t cap_rows, size_t n, size_t* bytes) {
   RelocDev d{};
-  Layout L;
-  uint8_t* b = static_cast<uint8_t*>(base);
-  const auto take = [&](auto*& p, size_t count) {
-    const size_t at = L.take(count * sizeof(*p));
-    p = b ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(b + at) : nullptr;
-  };
-  take(d.G, (cap_rows + 1) * n);
-  take(d.Z, (cap_rows + 1) * n);
-  take(d.S, cap_rows + 1);
-  take(d.out, 12 * cap_rows + 16);
-  if (bytes) *bytes = L.size;
+  Carver c(base);
+  c.take(d.G, (cap_rows + 1) * n);
+  c.take(d.Z, (cap_rows + 1) * n);
+  c.take(d.S, cap_rows + 1);
+  c.take(d.out, 12 * cap_rows + 16);
+  if (bytes) *bytes = c.L.size;
   return d;
 }
 

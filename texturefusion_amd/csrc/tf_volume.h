@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -94,6 +95,17 @@ struct Layout {
   }
 };
 
+// Typed arrays carved out of a block in Layout's steps (base == null: only the size is wanted, every pointer is null).
+struct Carver {
+  uint8_t* base;
+  Layout L;
+  explicit Carver(void* b) : base(static_cast<uint8_t*>(b)) {}
+  template <typename T> void take(T*& p, size_t count) {
+    const size_t at = L.take(count * sizeof(T));
+    p = base ? reinterpret_cast<T*>(base + at) : nullptr;
+  }
+};
+
 // Host and device base of a staging area in a pool.
 struct Stage {
   uint8_t* h = nullptr;
@@ -105,6 +117,8 @@ struct Stage {
 int stage_begin(tf_volume* v, Scratch& s, size_t dev_bytes, size_t host_bytes, Stage* st);
 // Host bytes in at offset `at` of the staging area, and their upload to the same offset of the device half (enqueued).
 int stage_in(tf_volume* v, const Stage& st, size_t at, const void* src, size_t bytes);
+// `bytes` at offset `at` of the device half back into the host half, one wait, and from there to out (null: left there).
+int stage_out(tf_volume* v, const Stage& st, size_t at, size_t bytes, void* out);
 // stage_begin for `bytes` on both halves, then ids (host, int32[3n]) as an int4 list at offset 0, its upload enqueued.
 int stage_ids(tf_volume* v, Scratch& s, size_t bytes, const int32_t* ids, int64_t n, Stage* st);
 // The first m entries of the int4 list at the start of the pool's device half -> out (int32[3m]); returns after the copy.
@@ -181,27 +195,17 @@ struct CcState {
   DevMem block;
 };
 
-// Frame-to-model alignment (tf_align.hip): partial sums, the f64 pose, control words, the log -- one block sized for the
-// camera at stride 1, null until first use
-struct AlignState {
+// The state block of an aligner (tf_align.hip, tf_align_color.hip, tf_align_group.hip, tf_align_icp.hip): partial sums, the
+// f64 poses, control words, the log -- sized for the camera at stride 1, null until first use.  Each aligner has its own,
+// so that its log outlives the others' calls.
+struct AlignBlock {
   DevMem block;
   size_t cap_tiles = 0;  // 8 x 8 pixel tiles the block has room for
 };
-// The colour-aided alignment's own block (tf_align_color.hip), laid out and owned the same way
-struct AlignColorState {
-  DevMem block;
-  size_t cap_tiles = 0;
-};
-// The group alignment's own block (tf_align_group.hip): the same for seven frames and seven bodies, and a result
-struct AlignGroupState {
-  DevMem block;
-  size_t cap_tiles = 0;
-};
-// The projective ICP's own block (tf_align_icp.hip), laid out and owned as AlignState's, and the six planes of the model's
-// vertex and normal maps of the forms that raycast themselves (null until one of those is used)
+// The projective ICP's block, and the six planes of the model's vertex and normal maps of the forms that raycast
+// themselves (null until one of those is used)
 struct AlignIcpState {
-  DevMem block;
-  size_t cap_tiles = 0;
+  AlignBlock st;
   DevMem maps;
   size_t map_pixels = 0;  // pixels each plane of `maps` has room for
 };
@@ -324,9 +328,7 @@ struct tf_volume {
   tf::TexMapDev tm{};   // TexMap resident on the device: null pointers until the first tf_texmap_* call
   tf::TexMapState tmx;
   tf::CcState cc;
-  tf::AlignState align;
-  tf::AlignColorState align_color;
-  tf::AlignGroupState align_group;
+  tf::AlignBlock align, align_color, align_group;
   tf::AlignIcpState align_icp;
   tf::RelocState reloc;
   tf::ModelState model;
@@ -431,19 +433,36 @@ int patch_stage_device(tf_volume* v, const int4* d_list, uint32_t n, uint32_t* d
 // Chisel::CompensateColor enqueued on the handle's stream, nothing read back (tf_cc.hip); cc_release frees its buffers
 int cc_enqueue(tf_volume* v, uint32_t* d_n_clusters);
 void cc_release(tf_volume* v);
-void align_release(tf_volume* v);  // frees tf_align.hip's state block
-// what tf_align.hip shares with tf_align_color.hip: the readers' camera, and the checks of a call's arguments (with_iters:
-// iters are read too); align_color_release frees tf_align_color.hip's state block
+// The aligners' host side (tf_align.hip; the device side is tf_align_rows.h).  align_cam: the camera of the depth image,
+// the one tf_raycast_camera set (any size), else the handle's.  align_check: what every aligner refuses a call for
+// (with_iters: iters are read too).  track_check (tf_align_icp.hip): what tf_track_frame refuses a call for, for
+// tf_relocalise to refuse it ahead of its first launch.
 struct AlignCam { float fx, fy, cx, cy; int W, H; };
 AlignCam align_cam(const tf_volume* v);
 bool finite_all(const float* p, int n);
 int align_check(tf_volume* v, const float* depth, const float* pose, const tf_align_params* p, bool with_iters);
-void align_color_release(tf_volume* v);
-void align_group_release(tf_volume* v);  // frees tf_align_group.hip's state block
-void align_icp_release(tf_volume* v);    // frees tf_align_icp.hip's state block and its maps
-// what tf_track_frame refuses a call for (tf_align_icp.hip), for tf_relocalise to refuse it ahead of its first launch
 int track_check(tf_volume* v, const float* depth, const float* pose, const tf_align_icp_params* icp_params,
                 const tf_align_params* sdf_params);
+size_t align_pixels(const tf_volume* v);  // of the camera
+size_t align_tiles(const tf_volume* v);   // 8 x 8 tiles of the camera at stride 1
+// First use, or a larger camera since: b.block (re)allocated to bytes_of(align_tiles(v)) after a wait for the stream, its
+// first clear_bytes (the control words) zeroed.
+int align_ensure(tf_volume* v, AlignBlock& b, size_t (*bytes_of)(size_t tiles), size_t clear_bytes);
+// A level's geometry and parameters as the kernels read them (level == n_levels: the closing evaluation, at the last
+// level's stride); sc->n_rows is the rows launch's grid.
+struct AlignRowsCommon;
+struct AlignSolveCommon;
+void align_level(const tf_volume* v, const tf_align_params& p, int level, AlignRowsCommon* rc, AlignSolveCommon* sc);
+// The schedule of a call: evaluate(rc, sc) for iters[l] evaluations of every level l, then once to close.
+void align_walk(const tf_volume* v, const tf_align_params& p,
+                const std::function<void(const AlignRowsCommon&, const AlignSolveCommon&)>& evaluate);
+// tf_*_log: waits for the stream, reads the control words at d_ctl (null: no call yet, no records) and copies
+// min(n_eval, cap) records of rec_bytes from d_log; *n = the records there are.
+int align_log(tf_volume* v, const void* d_ctl, const void* d_log, size_t rec_bytes, void* out, int64_t cap, int64_t* n);
+void align_release(tf_volume* v);        // these free the state block of tf_align.hip,
+void align_color_release(tf_volume* v);  // of tf_align_color.hip,
+void align_group_release(tf_volume* v);  // of tf_align_group.hip,
+void align_icp_release(tf_volume* v);    // and of tf_align_icp.hip with its maps
 void reloc_release(tf_volume* v);        // frees tf_reloc.hip's index and forgets its configuration
 // the resident model stream (tf_model.hip).  model_pack_enqueue: list, rank, scan and write on the handle's stream, nothing
 // read back (the buffers exist and have a capacity); model_stream_sync: the pack, one wait for the control block, the
