@@ -801,10 +801,65 @@ TF_API int tf_align_icp_residuals_device(tf_volume* v, const float* d_depth, con
 /* The coarse-to-fine tracker in one call: tf_align_frame_icp with the model raycast at the start pose; where that ends
  * with status <= TF_ALIGN_MAX_ITERS, tf_align_frame from the ICP's pose.  out->pose is the SDF stage's pose where its
  * status <= TF_ALIGN_MAX_ITERS (stage 2), otherwise the ICP's where the ICP's was (stage 1), otherwise the caller's
- * (stage 0).  It waits twice, once per stage: chaining the stages on the device would need tf_align_frame_device to
- * start from a device pose.  TF_ERR_INVALID (nothing launched, out untouched) for what either stage rejects. */
+ * (stage 0).  It waits twice, once per stage; tf_track_frame_device below chains the stages on the device, from a pose in
+ * device memory, and waits for nothing.  TF_ERR_INVALID (nothing launched, out untouched) for what either stage rejects. */
 TF_API int tf_track_frame(tf_volume* v, const float* depth, const float pose[12], const tf_align_icp_params* icp_params,
                           const tf_align_params* sdf_params, tf_track_result* out);
+
+/* ---- tracking and integrating with the pose kept on the device (tf_devpose.hip) ------------------
+ * KinectFusion's loop on the stream: track frame f against the model, decide whether the result is good enough, integrate
+ * the frame at the tracked pose, track frame f + 1 from it -- everything enqueued up front, nothing read back; the host
+ * looks at the results when it wants to.  The pose travels in a cell in device memory.  The device checks a cell, not the
+ * host: a cell with valid == 0 or a non-finite entry holds no pose, every launch that depends on it does nothing, and the
+ * outputs say so (below).  Cells are 16-byte aligned.
+ * Not here: texturing (tf_stream_frames_textured_device takes pose_inv16 from the host), a multi-rank form (a handle with
+ * a partition or a communicator is refused), a group or colour form of the device tracker. */
+typedef struct tf_device_pose {   /* 64 bytes, 16-byte aligned, device memory */
+  float   pose[12];               /* camera-to-world, row-major 3 x 4, as everywhere else */
+  int32_t valid;                  /* 0: every launch that reads this cell returns at once */
+  int32_t reserved[3];
+} tf_device_pose;
+typedef struct tf_track_accept {      /* tf_relocalise's test of a try */
+  int32_t min_stage;                  /* 1 or 2 */
+  float   min_valid_fraction;         /* of n_valid_last / n_sampled of the stage that gave the pose, in [0, 1] */
+  float   max_rms;                    /* of that stage's rms_last, finite and >= 0 */
+} tf_track_accept;
+TF_API int tf_track_accept_default(tf_track_accept* out);   /* 2, 0.5, 0.01: tf_relocalise's defaults */
+/* tf_track_frame with everything in device memory and no wait: the model raycast at *d_start, the ICP from it, the SDF
+ * stage from the ICP's f32 pose where the ICP held (0 <= status <= TF_ALIGN_MAX_ITERS), *d_out as tf_track_frame fills
+ * it, bit for bit.  The result is accepted where stage >= min_stage, and of the stage that gave the pose n_sampled > 0,
+ * (float)n_valid_last >= min_valid_fraction * (float)n_sampled and rms_last <= max_rms -- tf_relocalise's expressions, by
+ * the same function; accept == NULL: where stage >= 1.  *d_pose_out = {d_out->pose, valid 1} where it is accepted, else
+ * {the start cell's 12 floats, valid 0}.  d_pose_out may be d_start.
+ * A start cell that holds no pose: *d_out = {icp.status -1, sdf.status -1, the rest of both 0, stage 0, pose = the cell's
+ * 12 floats as stored}, d_pose_out->valid = 0.  A stage that did not run has no records of this call: tf_align_icp_log
+ * then returns none, tf_align_log (as after tf_track_frame) those of the last call that ran it; otherwise both return
+ * this call's records.
+ * TF_ERR_INVALID (nothing launched, outputs untouched) for what tf_track_frame rejects from its parameters, a null
+ * pointer, a cell that is not 16-byte aligned, accept fields out of range, a raycast camera whose size is not
+ * tf_set_camera's (tf_relocalise's rule), a handle with a partition or a communicator.  Only the pose checks are made on
+ * the device. */
+TF_API int tf_track_frame_device(tf_volume* v, const float* d_depth, const tf_device_pose* d_start,
+                                 const tf_align_icp_params* icp, const tf_align_params* sdf,
+                                 const tf_track_accept* accept, tf_track_result* d_out, tf_device_pose* d_pose_out);
+/* tf_integrate_frames_device for one frame whose pose is *d_pose; d_rgba may be NULL.  The volume afterwards is that
+ * call's with the same pose, and so is the handle: epoch, selection-set rotation, dirty marks, the bound frame; selections
+ * made ahead by a streaming call are discarded, as for a stream that changed course.  A cell that holds no pose: the
+ * volume is untouched, and the frame counts as one that selected nothing (tf_get_stats: n_selected, n_coarse and the id
+ * range are 0).  TF_ERR_INVALID for a null depth or cell pointer, misaligned images or cell, a partition or a communicator. */
+TF_API int tf_integrate_frame_posed_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba,
+                                           const tf_device_pose* d_pose);
+/* the two above in sequence on the handle's stream, the frame integrated at *d_pose_out only where it was accepted */
+TF_API int tf_track_integrate_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba,
+                                     const tf_device_pose* d_start, const tf_align_icp_params* icp,
+                                     const tf_align_params* sdf, const tf_track_accept* accept,
+                                     tf_track_result* d_out, tf_device_pose* d_pose_out);
+/* diagnostic: the constants block the selection launches read, derived from *d_pose as the device wrote it (waits once).
+ * Words of 4 bytes, in order: res, id_factor, step (i32), diag, diag_step, dtn_coarse, dtn_fine, rot[3][3], tc[3], r0[3],
+ * r1[3], r2[3], coarse[3][8], fine[3][8], pose[12], resDiag, plain (i32) -- tf_host_math.h's SelectConsts -- then the
+ * pose again (12), the gate word (i32, 1: the cell held a pose) and 3 words of padding: 424 bytes; the first `bytes`
+ * (<= 424) are copied. */
+TF_API int tf_pose_consts_download(tf_volume* v, const tf_device_pose* d_pose, void* out, size_t bytes);
 
 /* ---- relocalising a lost camera against the cached keyframes (tf_reloc.hip) -------------------
  * tf_track_frame needs a start within the ICP's capture range (about 12 cm / 8 degrees).  A caller that has none asks the

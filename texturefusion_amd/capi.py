@@ -60,6 +60,8 @@ SYMBOLS = (
     "tf_align_group", "tf_align_group_device", "tf_align_group_log", "tf_align_unit_group",
     "tf_align_icp_default_params", "tf_align_frame_icp", "tf_align_frame_icp_device", "tf_align_icp_log",
     "tf_align_icp_residuals", "tf_align_icp_residuals_device", "tf_track_frame",
+    "tf_track_accept_default", "tf_track_frame_device", "tf_integrate_frame_posed_device", "tf_track_integrate_device",
+    "tf_pose_consts_download",
     "tf_reloc_default_params", "tf_reloc_configure", "tf_reloc_index_add", "tf_reloc_index_remove", "tf_reloc_index_clear",
     "tf_reloc_index_count", "tf_reloc_describe", "tf_reloc_descriptor_download", "tf_reloc_query", "tf_reloc_query_device",
     "tf_relocalise_default_params", "tf_relocalise",
@@ -208,6 +210,40 @@ class AlignIcpParamsC(C.Structure):
 
 class TrackResult(C.Structure):
     _fields_ = [("icp", AlignResult), ("sdf", AlignResult), ("stage", C.c_int32), ("pose", C.c_float * 12)]
+
+
+class DevicePose(C.Structure):
+    """tf_device_pose: a pose cell in device memory (64 bytes, 16-byte aligned)"""
+    _fields_ = [("pose", C.c_float * 12), ("valid", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class TrackAcceptC(C.Structure):
+    _fields_ = [("min_stage", C.c_int32), ("min_valid_fraction", C.c_float), ("max_rms", C.c_float)]
+
+
+class PoseConsts(C.Structure):
+    """What tf_pose_consts_download hands out: tf_host_math.h's SelectConsts, the pose again, the gate word"""
+    _fields_ = [("res", C.c_float), ("id_factor", C.c_float), ("step", C.c_int32), ("diag", C.c_float),
+                ("diag_step", C.c_float), ("dtn_coarse", C.c_float), ("dtn_fine", C.c_float), ("rot", C.c_float * 9),
+                ("tc", C.c_float * 3), ("r0", C.c_float * 3), ("r1", C.c_float * 3), ("r2", C.c_float * 3),
+                ("coarse", C.c_float * 24), ("fine", C.c_float * 24), ("pose", C.c_float * 12), ("resDiag", C.c_float),
+                ("plain", C.c_int32), ("P", C.c_float * 12), ("gate", C.c_int32), ("pad", C.c_int32 * 3)]
+
+
+def TrackAccept(**kw):
+    """tf_track_accept: the library's defaults (tf_track_accept_default) with fields replaced by keyword"""
+    a = TrackAcceptC()
+    rc = lib().tf_track_accept_default(C.byref(a))
+    if rc != TF_OK:
+        raise TFError(rc, lib().tf_last_error().decode())
+    for k, val in kw.items():
+        if k == "min_stage":
+            a.min_stage = int(val)
+        elif k in ("min_valid_fraction", "max_rms"):
+            setattr(a, k, float(val))
+        else:
+            raise TypeError("tf_track_accept has no field %r" % k)
+    return a
 
 
 def AlignIcpParams(**kw):
@@ -476,6 +512,12 @@ def lib():
     L.tf_align_icp_residuals.argtypes = [vp, fp, fp, fp, fp, fp, aip, fp, C.POINTER(C.c_uint32), i32p]
     L.tf_align_icp_residuals_device.argtypes = [vp, vp, fp, vp, vp, fp, aip, vp, vp, vp]
     L.tf_track_frame.argtypes = [vp, fp, fp, aip, app, C.POINTER(TrackResult)]
+    tap = C.POINTER(TrackAcceptC)
+    L.tf_track_accept_default.argtypes = [tap]
+    L.tf_track_frame_device.argtypes = [vp, vp, vp, aip, app, tap, vp, vp]
+    L.tf_integrate_frame_posed_device.argtypes = [vp, vp, vp, vp]
+    L.tf_track_integrate_device.argtypes = [vp, vp, vp, vp, aip, app, tap, vp, vp]
+    L.tf_pose_consts_download.argtypes = [vp, vp, vp, C.c_size_t]
     rlp, u32p, f64p = C.POINTER(RelocParamsC), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
     L.tf_reloc_default_params.argtypes = [rlp]
     L.tf_reloc_configure.argtypes = [vp, rlp]
@@ -1266,6 +1308,33 @@ class Volume:
                                        C.byref(sdf_params), C.byref(res)))
         return dict(icp=self.align_result(res.icp), sdf=self.align_result(res.sdf), stage=res.stage,
                     pose=np.array(res.pose, np.float32).reshape(3, 4))
+
+    # -- tracking and integrating with the pose in device memory (tf_devpose.hip; asynchronous, nothing read back)
+    def track_frame_device(self, d_depth, d_start, icp_params, sdf_params, accept, d_out, d_pose_out):
+        """track_frame from the tf_device_pose at d_start: the tf_track_result to d_out, the accepted pose (or the start,
+        valid 0) to the cell at d_pose_out, which may be d_start.  accept: a TrackAccept, or None for stage >= 1."""
+        self._ck(self.L.tf_track_frame_device(self.h, d_depth or None, d_start or None,
+                                              None if icp_params is None else C.byref(icp_params),
+                                              None if sdf_params is None else C.byref(sdf_params),
+                                              None if accept is None else C.byref(accept), d_out or None, d_pose_out or None))
+
+    def integrate_frame_posed_device(self, d_depth, d_rgba, d_pose):
+        """integrate_frames_device for one frame whose pose is the tf_device_pose at d_pose (valid 0: nothing happens)"""
+        self._ck(self.L.tf_integrate_frame_posed_device(self.h, d_depth or None, d_rgba or None, d_pose or None))
+
+    def track_integrate_device(self, d_depth, d_rgba, d_start, icp_params, sdf_params, accept, d_out, d_pose_out):
+        """track_frame_device, then integrate_frame_posed_device at d_pose_out, in one call"""
+        self._ck(self.L.tf_track_integrate_device(self.h, d_depth or None, d_rgba or None, d_start or None,
+                                                  None if icp_params is None else C.byref(icp_params),
+                                                  None if sdf_params is None else C.byref(sdf_params),
+                                                  None if accept is None else C.byref(accept), d_out or None,
+                                                  d_pose_out or None))
+
+    def pose_consts_download(self, d_pose):
+        """The constants block the device derives from the tf_device_pose at d_pose -> PoseConsts (waits once)"""
+        out = PoseConsts()
+        self._ck(self.L.tf_pose_consts_download(self.h, d_pose or None, C.byref(out), C.sizeof(out)))
+        return out
 
     # -- relocalisation against the cached keyframes (tf_reloc_*, tf_relocalise; read-only)
     def reloc_configure(self, params=None):

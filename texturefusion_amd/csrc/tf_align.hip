@@ -3,6 +3,8 @@
 // has no body for it, so the method and its order of operations are defined here and restated in tests/align_ref.py).
 //
 //   k_align_begin  one lane: the caller's pose into the state block (f64 and f32), the control words cleared
+//   k_stage2_start k_align_begin for a call chained behind another aligner's on the stream: the start is that call's result
+//                  pose, read on the device, where its status holds (the device tracker, tf_devpose.hip)
 //   k_align_rows   one wave per 8 x 8 tile of SAMPLED pixels (lane = 8 y + x, a tile spans 8 * stride image pixels), eight
 //                  waves per workgroup:
 //                  residual, gradient, Jacobian and the wave's share of the normal equations; with map outputs, the
@@ -72,6 +74,20 @@ struct AlignSolveArgs {
 
 __global__ __launch_bounds__(64) void k_align_begin(AlignDev d, AlignPose p, int residuals_only) {
   al_begin(d.ctl, d.pose_d, d.pose_f, d.pose_r, p, residuals_only);
+}
+
+// The begin launch of a call that follows another aligner's on the stream, as the second stage of the device tracker does
+// (tf_devpose.hip): the start is the f32 pose of that call's result, read from device memory.  It runs only where that
+// call's status holds (0 <= *prev_status <= TF_ALIGN_MAX_ITERS).  Otherwise bit 0 of the state word stops every launch of
+// this call: the result is not written and the log stays the last call's.
+__global__ __launch_bounds__(64) void k_stage2_start(AlignDev d, const int32_t* __restrict__ prev_status,
+                                                     const AlignPose* __restrict__ prev_pose) {
+  const int32_t s = *prev_status;
+  if (!(s >= 0 && s <= TF_ALIGN_MAX_ITERS)) {
+    if (threadIdx.x == 0) d.ctl->state |= 1u;
+    return;
+  }
+  al_begin(d.ctl, d.pose_d, d.pose_f, d.pose_r, *prev_pose, 0);
 }
 
 // (six waves per SIMD, no private memory: tests/test_kernel_resources_align.py)
@@ -242,15 +258,21 @@ AlignRowsArgs rows_args(const tf_volume* v, const AlignRowsCommon& rc, const flo
   return a;
 }
 
-// every launch of one alignment: begin, then (rows, solve) per step and once more to close
-int align_enqueue(tf_volume* v, const float* d_depth, const float* pose, const tf_align_params& p, tf_align_result* d_result) {
+// every launch of one alignment: begin, then (rows, solve) per step and once more to close.  d_prev_status != null: the
+// start is the pose at d_prev_pose, read on the device, where that status holds (k_stage2_start; pose is not read).
+int align_enqueue(tf_volume* v, const float* d_depth, const float* pose, const tf_align_params& p, tf_align_result* d_result,
+                  const int32_t* d_prev_status = nullptr, const float* d_prev_pose = nullptr) {
   AlignDev d;
   int rc = align_dev(v, &d);
   if (rc) return rc;
   hipStream_t st = v->stream;
-  AlignPose P;
-  memcpy(P.p, pose, sizeof(P.p));
-  hipLaunchKernelGGL(k_align_begin, dim3(1), dim3(64), 0, st, d, P, 0);
+  if (d_prev_status) {
+    hipLaunchKernelGGL(k_stage2_start, dim3(1), dim3(64), 0, st, d, d_prev_status, reinterpret_cast<const AlignPose*>(d_prev_pose));
+  } else {
+    AlignPose P;
+    memcpy(P.p, pose, sizeof(P.p));
+    hipLaunchKernelGGL(k_align_begin, dim3(1), dim3(64), 0, st, d, P, 0);
+  }
   align_walk(v, p, [&](const AlignRowsCommon& c, const AlignSolveCommon& sc) {
     AlignRowsArgs ra = rows_args(v, c, d_depth);
     ra.pose = d.pose_f; ra.state = &d.ctl->state; ra.part = d.part;
@@ -286,6 +308,13 @@ int residuals_enqueue(tf_volume* v, const float* d_depth, const float* pose, con
 }
 
 }  // namespace
+
+// tf_align_frame_device from the 12 floats at d_prev_pose where *d_prev_status holds, all enqueued (tf_devpose.hip; the
+// caller has checked)
+int track_sdf_posed(tf_volume* v, const float* d_depth, const int32_t* d_prev_status, const float* d_prev_pose,
+                    const tf_align_params& p, tf_align_result* d_result) {
+  return align_enqueue(v, d_depth, nullptr, p, d_result, d_prev_status, d_prev_pose);
+}
 
 }  // namespace tf
 

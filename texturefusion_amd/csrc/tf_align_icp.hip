@@ -6,6 +6,8 @@
 // restates the rows.
 //
 //   k_icp_begin  one lane: the caller's pose (f64 and f32) and the model pose into the state block, the control words cleared
+//   k_track_start  k_icp_begin for a start in device memory: both poses from a tf_device_pose cell, or the call stopped where
+//                the cell holds no pose (the device tracker, tf_devpose.hip)
 //   k_icp_rows   one wave per 8 x 8 tile of SAMPLED pixels (lane = 8 y + x, a tile spans 8 * stride image pixels), eight
 //                waves per workgroup: association, residual, Jacobian and the wave's share of the normal equations; with map
 //                outputs, the maps of tf_align_icp_residuals -- one body
@@ -39,6 +41,7 @@
 #include <string.h>
 
 #include "tf_align_rows.h"
+#include "tf_devpose.h"
 #include "tf_volume.h"
 
 #pragma clang fp contract(off)
@@ -85,6 +88,23 @@ __global__ __launch_bounds__(64) void k_icp_begin(IcpDev d, IcpPoses p, int resi
   if (i == 0) {
     AlignCtl c{};
     c.status = TF_ALIGN_MAX_ITERS;
+    *d.ctl = c;
+  }
+}
+
+// The begin launch of a call whose start is in device memory (tf_devpose.h): the frame's pose and the model's are the
+// cell's.  A cell that holds no pose stops the call before it starts -- bit 0 of the state word, which every rows and
+// solve launch tests -- with status -1 in the control words (what the stage behind this one and the finish read) and no
+// records; the result is not written then.
+__global__ __launch_bounds__(64) void k_track_start(IcpDev d, const tf_device_pose* __restrict__ cell) {
+  const int i = threadIdx.x;
+  const float p = cell->pose[i < 12 ? i : 0];
+  const bool ok = devpose_ok_wave(cell, p);
+  if (ok && i < 12) { d.pose_d[i] = (double)p; d.pose_f[i] = p; d.pose_f[12 + i] = p; }
+  if (i == 0) {
+    AlignCtl c{};
+    c.status = ok ? TF_ALIGN_MAX_ITERS : -1;
+    c.state = ok ? 0u : 1u;
     *d.ctl = c;
   }
 }
@@ -213,17 +233,23 @@ IcpRowsArgs icp_rows_args(const AlignRowsCommon& rc, const tf_align_icp_params& 
   return a;
 }
 
-// every launch of one alignment: begin, then (rows, solve) per step and once more to close
+// every launch of one alignment: begin, then (rows, solve) per step and once more to close.  d_start != null: frame pose
+// and model pose are that cell's, read on the device (pose and model_pose are not read).
 int icp_enqueue(tf_volume* v, const float* d_depth, const float* pose, const float* d_vertex, const float* d_normal,
-                const float* model_pose, const tf_align_icp_params& p, tf_align_result* d_result) {
+                const float* model_pose, const tf_align_icp_params& p, tf_align_result* d_result,
+                const tf_device_pose* d_start = nullptr) {
   IcpDev d;
   int rc = icp_dev(v, &d);
   if (rc) return rc;
   hipStream_t st = v->stream;
-  IcpPoses P;
-  memcpy(P.p, pose, sizeof(P.p));
-  memcpy(P.m, model_pose, sizeof(P.m));
-  hipLaunchKernelGGL(k_icp_begin, dim3(1), dim3(64), 0, st, d, P, 0);
+  if (d_start) {
+    hipLaunchKernelGGL(k_track_start, dim3(1), dim3(64), 0, st, d, d_start);
+  } else {
+    IcpPoses P;
+    memcpy(P.p, pose, sizeof(P.p));
+    memcpy(P.m, model_pose, sizeof(P.m));
+    hipLaunchKernelGGL(k_icp_begin, dim3(1), dim3(64), 0, st, d, P, 0);
+  }
   align_walk(v, p.geo, [&](const AlignRowsCommon& c, const AlignSolveCommon& sc) {
     IcpRowsArgs ra = icp_rows_args(c, p, d_depth, d_vertex, d_normal);
     ra.pose = d.pose_f; ra.state = &d.ctl->state; ra.part = d.part;
@@ -275,6 +301,21 @@ int track_check(tf_volume* v, const float* depth, const float* pose, const tf_al
                 const tf_align_params* sdf_params) {
   const int rc = icp_check(v, depth, pose, nullptr, icp_params, true, true);
   return rc ? rc : align_check(v, depth, pose, sdf_params, true);
+}
+
+// tf_track_frame's first stage with everything in device memory: the model raycast at *d_start into the handle's maps,
+// the alignment from *d_start against them, all enqueued, nothing read back (tf_devpose.hip; the caller has checked).
+// *d_status: the status word of the state block, the call's status once its launches are through (-1: no pose, not run).
+int track_icp_posed(tf_volume* v, const float* d_depth, const tf_device_pose* d_start, const tf_align_icp_params& p,
+                    tf_align_result* d_result, const int32_t** d_status) {
+  float *d_v = nullptr, *d_n = nullptr;
+  int rc = icp_ensure_maps(v, &d_v, &d_n);
+  if (rc || (rc = raycast_posed(v, d_start, p.ray_near, p.ray_far, p.ray_max_steps, d_n, d_v))) return rc;
+  if ((rc = icp_enqueue(v, d_depth, nullptr, d_v, d_n, nullptr, p, d_result, d_start))) return rc;
+  IcpDev d;
+  if ((rc = icp_dev(v, &d))) return rc;
+  *d_status = &d.ctl->status;
+  return TF_OK;
 }
 
 }  // namespace tf

@@ -214,7 +214,7 @@ static int init_device_state(tf_volume* v) {
 // Selections made ahead for frames of a previous streaming call (n_ahead) depend on the camera, the truncation
 // model, the weight (the list records hold weight / (2 truncation), chunk_pre) and the partition: a setter that changes
 // one of these discards them, so that the next call selects again.
-static void discard_primed(tf_volume* v) {
+void discard_primed(tf_volume* v) {
   for (int k = 0; k < v->n_primed; ++k) {
     VolumeDev d = v->dev;
     d.sel = v->selbuf[(v->cur_sel + 1 + k) % tf_volume::kSelSets];
@@ -837,6 +837,7 @@ int tf_volume_reset(tf_volume* v) {
   align_group_release(v);
   align_icp_release(v);
   reloc_release(v);
+  devpose_release(v);
   model_release(v);
   rc = init_device_state(v);
   if (rc) return rc;

@@ -389,6 +389,11 @@ void launch_bbox(const VolumeDev& v, const float* depth, const Cam& cam, const P
                  hipStream_t s);
 void launch_select(const VolumeDev& v, const float* depth, const Cam& cam, const Integ& ig,
                    const Pose& pose, float res, bool emit, hipStream_t s, bool plain = false);
+// K-B and K-C (emit form) of a frame whose pose is in device memory: *pc is what k_pose_consts wrote (tf_devpose.h)
+struct PoseConsts;
+void launch_bbox_posed(const VolumeDev& v, const float* depth, const Cam& cam, const PoseConsts* pc, hipStream_t s);
+void launch_select_posed(const VolumeDev& v, const float* depth, const Cam& cam, const Integ& ig, const PoseConsts* pc,
+                         hipStream_t s);
 void launch_scan(const VolumeDev& v, int step, hipStream_t s);
 void launch_acquire(const VolumeDev& v, hipStream_t s);
 void launch_lookup(const VolumeDev& v, uint32_t n, hipStream_t s);

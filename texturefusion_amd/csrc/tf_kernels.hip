@@ -20,6 +20,7 @@
 #include <atomic>
 #include "tf_device.h"
 #include "tf_devfn.h"
+#include "tf_devpose.h"
 #include "tf_host_math.h"
 #include "tf_patch_body.h"
 #include "tf_voxel_math.h"
@@ -169,6 +170,29 @@ void launch_bbox(const VolumeDev& v, const float* depth, const Cam& cam, const P
   int blocks = (nvec + 255) / 256;
   if (blocks > 128) blocks = 128;  // 6 atomics per block on 6 words: keep the tail short
   hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, s, depth, cam, pose, v.sel.ctl);
+}
+// K-B of a frame whose pose is in device memory: the pose comes from the block k_pose_consts wrote (tf_devpose.h), through
+// a uniform pointer, so it lands in SGPRs as a kernel argument does.  Gate off (the cell held no pose): the set is left as
+// an empty frame's -- no list, no coarse grid, keys armed as they were -- so that k_select_posed has nothing to read and
+// K-A, which follows unchanged, walks nothing.
+__global__ __launch_bounds__(256) void k_bbox_posed(const float* __restrict__ depth, Cam cam,
+                                                    const PoseConsts* __restrict__ pc, FrameCtl* ctl) {
+  if (!pc->gate) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      ctl->n_list = 0; ctl->n_front = 0; ctl->emit_pack = 0ull; ctl->n_coarse = 0;
+      for (int a = 0; a < 3; ++a) ctl->min_id[a] = ctl->max_id[a] = ctl->dims[a] = 0;
+      for (int k = 0; k < 4; ++k) ctl->band_cnt[k] = 0u;
+    }
+    return;
+  }
+  const Pose P = pc->P;
+  bbox_body(depth, cam, P, ctl, blockIdx.x, gridDim.x);
+}
+void launch_bbox_posed(const VolumeDev& v, const float* depth, const Cam& cam, const PoseConsts* pc, hipStream_t s) {
+  int nvec = (cam.W * cam.H) >> 2;
+  int blocks = (nvec + 255) / 256;
+  if (blocks > 128) blocks = 128;  // as launch_bbox
+  hipLaunchKernelGGL(k_bbox_posed, dim3(blocks), dim3(256), 0, s, depth, cam, pc, v.sel.ctl);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -359,6 +383,17 @@ void launch_select(const VolumeDev& v, const float* depth, const Cam& cam, const
   sc.plain = plain ? 1 : 0;
   if (emit) hipLaunchKernelGGL(k_select<true>, dim3(1024), dim3(256), 0, s, depth, cam, ig, sc, v);
   else hipLaunchKernelGGL(k_select<false>, dim3(1024), dim3(256), 0, s, depth, cam, ig, sc, v);
+}
+// K-C (emit form) of a frame whose pose is in device memory: make_select_consts' struct from the block k_pose_consts
+// wrote.  Gate off: nothing is appended to the list k_bbox_posed left empty.
+__global__ __launch_bounds__(256) void k_select_posed(const float* __restrict__ depth, Cam cam, Integ ig,
+                                                      const PoseConsts* __restrict__ pc, VolumeDev v) {
+  if (!pc->gate) return;
+  select_body<true>(depth, cam, ig, pc->sc, v, blockIdx.x, gridDim.x);  // (read in place: a copy would be private memory)
+}
+void launch_select_posed(const VolumeDev& v, const float* depth, const Cam& cam, const Integ& ig, const PoseConsts* pc,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(k_select_posed, dim3(256), dim3(256), 0, s, depth, cam, ig, pc, v);  // the selection role's grid of launch_frame
 }
 
 // ---------------------------------------------------------------------------------------

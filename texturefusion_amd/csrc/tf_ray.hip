@@ -42,6 +42,7 @@
 #include <string.h>
 
 #include "tf_devfn.h"
+#include "tf_devpose.h"
 #include "tf_ray_devfn.h"
 #include "tf_volume.h"
 
@@ -182,7 +183,7 @@ struct RayArgs {
 };
 
 // one wave per 8 x 8 pixel tile (lane = 8 y + x): neighbouring rays march through the same chunks
-__global__ __launch_bounds__(64) void k_raycast(VolumeDev v, RayArgs a) {
+__device__ __forceinline__ void raycast_body(const VolumeDev& v, const RayArgs& a) {
   const int lane = threadIdx.x;
   const int px = (blockIdx.x % a.tiles_x) * 8 + (lane & 7), py = (blockIdx.x / a.tiles_x) * 8 + (lane >> 3);
   if (px >= a.W || py >= a.H) return;
@@ -273,7 +274,19 @@ __global__ __launch_bounds__(64) void k_raycast(VolumeDev v, RayArgs a) {
     reinterpret_cast<uchar4*>(a.rgba)[o] = c;
   }
 }
-
+__global__ __launch_bounds__(64) void k_raycast(VolumeDev v, RayArgs a) { raycast_body(v, a); }
+// the same march from a pose in device memory (tf_devpose.h): R and t come from the cell through a uniform pointer; a
+// cell that holds no pose leaves the maps as they are (whoever reads them is gated by the same cell)
+__global__ __launch_bounds__(64) void k_raycast_posed(VolumeDev v, RayArgs a, const tf_device_pose* __restrict__ cell) {
+  if (!devpose_ok(cell)) return;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a.R[3 * r + c] = cell->pose[4 * r + c];
+    a.t[r] = cell->pose[4 * r + 3];
+  }
+  raycast_body(v, a);
+}
 
 // ---- Chisel::GetDistanceFromSurface / RefineFrameInVoxel (Structure/Chisel.h:251-342, 377-451) ----------------------
 
@@ -439,17 +452,19 @@ int ray_check(tf_volume* v, const float* pose, float near_plane, float far_plane
   return TF_OK;
 }
 
+// d_cell != null: the pose is read from that cell on the device (k_raycast_posed; `pose` is not read)
 int ray_launch(tf_volume* v, const float* pose, float near_plane, float far_plane, int32_t max_steps, const RayCam& cam,
-               float* depth, float* normal, uint8_t* rgba, float* vertex) {
-  RayArgs a;
-  split_pose(pose, a.R, a.t);
+               float* depth, float* normal, uint8_t* rgba, float* vertex, const tf_device_pose* d_cell = nullptr) {
+  RayArgs a{};
+  if (!d_cell) split_pose(pose, a.R, a.t);
   a.fx = cam.fx; a.fy = cam.fy; a.cxs = cam.cx + 0.5f; a.cys = cam.cy + 0.5f;
   a.W = cam.W; a.H = cam.H; a.tiles_x = (cam.W + 7) / 8;
   a.near_p = near_plane; a.far_p = far_plane; a.max_steps = max_steps; a.res = v->res;
   a.plane = (size_t)cam.W * cam.H;
   a.depth = depth; a.normal = normal; a.rgba = rgba; a.vertex = vertex;
   const unsigned tiles = (unsigned)(a.tiles_x * ((cam.H + 7) / 8));
-  hipLaunchKernelGGL(k_raycast, dim3(tiles), dim3(64), 0, v->stream, v->dev, a);
+  if (d_cell) hipLaunchKernelGGL(k_raycast_posed, dim3(tiles), dim3(64), 0, v->stream, v->dev, a, d_cell);
+  else hipLaunchKernelGGL(k_raycast, dim3(tiles), dim3(64), 0, v->stream, v->dev, a);
   TF_HIP(hipGetLastError());
   return TF_OK;
 }
@@ -489,6 +504,15 @@ int refine_launch(tf_volume* v, const float* pose, float* d_depth, float* d_weig
 }
 
 }  // namespace
+
+// tf_raycast_device's launch at the pose in *d_cell (tf_devpose.hip: the device tracker's model maps)
+int tf::raycast_posed(tf_volume* v, const tf_device_pose* d_cell, float near_plane, float far_plane, int32_t max_steps,
+                      float* d_normal, float* d_vertex) {
+  const float eye[12] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+  RayCam cam;
+  const int rc = ray_check(v, eye, near_plane, far_plane, max_steps, &cam);
+  return rc ? rc : ray_launch(v, eye, near_plane, far_plane, max_steps, cam, nullptr, d_normal, nullptr, d_vertex, d_cell);
+}
 
 extern "C" {
 

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "tf_devpose.h"
 #include "tf_reloc_score.h"
 #include "tf_volume.h"
 
@@ -615,9 +616,7 @@ int tf_relocalise(tf_volume* v, const float* depth, const uint8_t* rgb, int32_t 
     tf_reloc_try& t = out.tries[out.n_tried++];
     t.kf_id = k.kf_id; t.overlap = k.overlap; t.score = k.score;
     if ((rc = tf_track_frame(v, depth, pose, &p.icp, &p.sdf, &t.track))) return rc;
-    const tf_align_result& a = t.track.stage == 2 ? t.track.sdf : t.track.icp;
-    if (t.track.stage >= p.min_stage && a.n_sampled > 0 &&
-        (float)a.n_valid_last >= p.min_valid_fraction * (float)a.n_sampled && a.rms_last <= p.max_rms) {
+    if (track_accepted(t.track, p.min_stage, p.min_valid_fraction, p.max_rms)) {  // (tf_devpose.h: the device tracker's test too)
       out.status = TF_RELOC_FOUND;
       out.kf_id = k.kf_id;
       out.rank = rank;

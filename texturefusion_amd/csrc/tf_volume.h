@@ -331,6 +331,7 @@ struct tf_volume {
   tf::AlignBlock align, align_color, align_group;
   tf::AlignIcpState align_icp;
   tf::RelocState reloc;
+  tf::DevMem devpose;  // one PoseConsts (tf_devpose.h): what k_pose_consts derives from a pose cell; null until first use
   tf::ModelState model;
   uint64_t model_gen = 0;  // advanced by every entry point that is not a whitelisted reader (TF_DEV_READER)
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
@@ -464,6 +465,20 @@ void align_color_release(tf_volume* v);  // of tf_align_color.hip,
 void align_group_release(tf_volume* v);  // of tf_align_group.hip,
 void align_icp_release(tf_volume* v);    // and of tf_align_icp.hip with its maps
 void reloc_release(tf_volume* v);        // frees tf_reloc.hip's index and forgets its configuration
+// The pieces of the device tracker outside tf_devpose.hip, each next to the launches it chains; the caller has checked the
+// parameters, nothing is read back.  raycast_posed (tf_ray.hip): tf_raycast_device's launch at the pose in *d_cell.
+// track_icp_posed (tf_align_icp.hip): the model raycast at *d_start into the handle's maps and the projective alignment
+// from *d_start against them; *d_status is the device word that holds the call's status once its launches are through (-1:
+// no pose in the cell).  track_sdf_posed (tf_align.hip): tf_align_frame_device from the 12 floats at d_prev_pose where
+// 0 <= *d_prev_status <= TF_ALIGN_MAX_ITERS.  A stage that does not run writes no result: k_track_finish does.
+int raycast_posed(tf_volume* v, const tf_device_pose* d_cell, float near_plane, float far_plane, int32_t max_steps,
+                  float* d_normal, float* d_vertex);
+int track_icp_posed(tf_volume* v, const float* d_depth, const tf_device_pose* d_start, const tf_align_icp_params& p,
+                    tf_align_result* d_result, const int32_t** d_status);
+int track_sdf_posed(tf_volume* v, const float* d_depth, const int32_t* d_prev_status, const float* d_prev_pose,
+                    const tf_align_params& p, tf_align_result* d_result);
+void discard_primed(tf_volume* v);       // the selections made ahead by a streaming call are dropped (tf_capi.cpp)
+void devpose_release(tf_volume* v);      // frees tf_devpose.hip's block
 // the resident model stream (tf_model.hip).  model_pack_enqueue: list, rank, scan and write on the handle's stream, nothing
 // read back (the buffers exist and have a capacity); model_stream_sync: the pack, one wait for the control block, the
 // buffers grown and the pack repeated on overflow -- ModelState::nv / ni are the counts afterwards; model_release frees all
