@@ -812,8 +812,11 @@ TF_API int tf_track_frame(tf_volume* v, const float* depth, const float pose[12]
  * looks at the results when it wants to.  The pose travels in a cell in device memory.  The device checks a cell, not the
  * host: a cell with valid == 0 or a non-finite entry holds no pose, every launch that depends on it does nothing, and the
  * outputs say so (below).  Cells are 16-byte aligned.
- * Not here: texturing (tf_stream_frames_textured_device takes pose_inv16 from the host), a multi-rank form (a handle with
- * a partition or a communicator is refused), a group or colour form of the device tracker. */
+ * The textured unit runs from a cell too (tf_integrate_frame_textured_posed_device, tf_track_texture_device): the matrix the
+ * patch stage projects with is the cell's rigid inverse, taken on the device.  Not here: that patch stage as a part of the
+ * next frame's launch (it is a launch of its own), a textured form for a handle with untextured marks pending, a multi-rank
+ * form (a handle with a partition or a communicator is refused), a group or colour form of the device tracker, caching the
+ * tracked frame as a keyframe. */
 typedef struct tf_device_pose {   /* 64 bytes, 16-byte aligned, device memory */
   float   pose[12];               /* camera-to-world, row-major 3 x 4, as everywhere else */
   int32_t valid;                  /* 0: every launch that reads this cell returns at once */
@@ -860,6 +863,31 @@ TF_API int tf_track_integrate_device(tf_volume* v, const float* d_depth, const u
  * pose again (12), the gate word (i32, 1: the cell held a pose) and 3 words of padding: 424 bytes; the first `bytes`
  * (<= 424) are copied. */
 TF_API int tf_pose_consts_download(tf_volume* v, const tf_device_pose* d_pose, void* out, size_t bytes);
+/* The textured unit for one frame whose pose is *d_pose.  With pose = the cell's 12 floats and T its rigid inverse
+ * [R^T | -R^T t; 0 0 0 1] -- row-major, T[4r + c] = pose[4c + r], T[4r + 3] = (float)-((p[r] p[3] + p[4 + r] p[7]) +
+ * p[8 + r] p[11]) with the products and the two additions in double -- the volume, meshes, patches, atlas and handle
+ * afterwards are those of tf_stream_frames_textured_device(v, 1, 0, &d_depth, &d_rgba, pose, T, frame_id), bit for bit; the
+ * frame's patch stage is on the stream when the call returns.  Selections made ahead by a streaming call are discarded; a
+ * patch stage such a call left pending is carried as by any frame.  A cell that holds no pose: volume, dirty set, meshes,
+ * patches, atlas texels and the atlas's next location are untouched, tf_get_stats' last-frame figures are 0 as after
+ * tf_integrate_frame_posed_device, and the handle's host-side counters advance.
+ * TF_ERR_INVALID (nothing of this frame launched, outputs untouched, tf_last_error says which) for what
+ * tf_integrate_frame_posed_device refuses, a null d_rgba, a texture stage half done (tf_texture_frame_device_phase), and a
+ * handle on which frames integrated without texturing still wait for a mesher: the host cannot know whether the cell holds
+ * a pose, and if it does not, the backlog would be meshed and its marks cleared without patches.  Texture the backlog
+ * first (tf_texture_frame_device). */
+TF_API int tf_integrate_frame_textured_posed_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba,
+                                                    const tf_device_pose* d_pose, int32_t frame_id);
+/* tf_track_frame_device, then the call above at *d_pose_out: the frame is integrated and textured only where it was
+ * accepted.  Everything either call refuses is refused before anything is launched. */
+TF_API int tf_track_texture_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba,
+                                   const tf_device_pose* d_start, const tf_align_icp_params* icp,
+                                   const tf_align_params* sdf, const tf_track_accept* accept,
+                                   tf_track_result* d_out, tf_device_pose* d_pose_out, int32_t frame_id);
+/* diagnostic: the block the posed patch stage reads, derived from *d_pose as the device wrote it (waits once): T[16] as
+ * above (f32), the gate word (i32, 1: the cell held a pose) and 3 words of padding: 80 bytes; the first `bytes` (<= 80)
+ * are copied.  With the gate off T is the same arithmetic on whatever the cell stores. */
+TF_API int tf_pose_inverse_download(tf_volume* v, const tf_device_pose* d_pose, void* out, size_t bytes);
 
 /* ---- relocalising a lost camera against the cached keyframes (tf_reloc.hip) -------------------
  * tf_track_frame needs a start within the ICP's capture range (about 12 cm / 8 degrees).  A caller that has none asks the

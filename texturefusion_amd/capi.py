@@ -61,7 +61,8 @@ SYMBOLS = (
     "tf_align_icp_default_params", "tf_align_frame_icp", "tf_align_frame_icp_device", "tf_align_icp_log",
     "tf_align_icp_residuals", "tf_align_icp_residuals_device", "tf_track_frame",
     "tf_track_accept_default", "tf_track_frame_device", "tf_integrate_frame_posed_device", "tf_track_integrate_device",
-    "tf_pose_consts_download",
+    "tf_pose_consts_download", "tf_integrate_frame_textured_posed_device", "tf_track_texture_device",
+    "tf_pose_inverse_download",
     "tf_reloc_default_params", "tf_reloc_configure", "tf_reloc_index_add", "tf_reloc_index_remove", "tf_reloc_index_clear",
     "tf_reloc_index_count", "tf_reloc_describe", "tf_reloc_descriptor_download", "tf_reloc_query", "tf_reloc_query_device",
     "tf_relocalise_default_params", "tf_relocalise",
@@ -228,6 +229,11 @@ class PoseConsts(C.Structure):
                 ("tc", C.c_float * 3), ("r0", C.c_float * 3), ("r1", C.c_float * 3), ("r2", C.c_float * 3),
                 ("coarse", C.c_float * 24), ("fine", C.c_float * 24), ("pose", C.c_float * 12), ("resDiag", C.c_float),
                 ("plain", C.c_int32), ("P", C.c_float * 12), ("gate", C.c_int32), ("pad", C.c_int32 * 3)]
+
+
+class PoseInverse(C.Structure):
+    """What tf_pose_inverse_download hands out: the cell's rigid inverse, row-major 4 x 4, and the gate word (80 bytes)"""
+    _fields_ = [("T", C.c_float * 16), ("gate", C.c_int32), ("pad", C.c_int32 * 3)]
 
 
 def TrackAccept(**kw):
@@ -518,6 +524,9 @@ def lib():
     L.tf_integrate_frame_posed_device.argtypes = [vp, vp, vp, vp]
     L.tf_track_integrate_device.argtypes = [vp, vp, vp, vp, aip, app, tap, vp, vp]
     L.tf_pose_consts_download.argtypes = [vp, vp, vp, C.c_size_t]
+    L.tf_integrate_frame_textured_posed_device.argtypes = [vp, vp, vp, vp, C.c_int32]
+    L.tf_track_texture_device.argtypes = [vp, vp, vp, vp, aip, app, tap, vp, vp, C.c_int32]
+    L.tf_pose_inverse_download.argtypes = [vp, vp, vp, C.c_size_t]
     rlp, u32p, f64p = C.POINTER(RelocParamsC), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
     L.tf_reloc_default_params.argtypes = [rlp]
     L.tf_reloc_configure.argtypes = [vp, rlp]
@@ -1334,6 +1343,26 @@ class Volume:
         """The constants block the device derives from the tf_device_pose at d_pose -> PoseConsts (waits once)"""
         out = PoseConsts()
         self._ck(self.L.tf_pose_consts_download(self.h, d_pose or None, C.byref(out), C.sizeof(out)))
+        return out
+
+    def integrate_frame_textured_posed_device(self, d_depth, d_rgba, d_pose, frame_id):
+        """stream_frames_textured_device for one frame whose pose is the tf_device_pose at d_pose and whose pose_inv16 is
+        that pose's rigid inverse, taken on the device (valid 0: nothing happens); nothing stays pending"""
+        self._ck(self.L.tf_integrate_frame_textured_posed_device(self.h, d_depth or None, d_rgba or None, d_pose or None,
+                                                                 int(frame_id)))
+
+    def track_texture_device(self, d_depth, d_rgba, d_start, icp_params, sdf_params, accept, d_out, d_pose_out, frame_id):
+        """track_frame_device, then integrate_frame_textured_posed_device at d_pose_out, in one call"""
+        self._ck(self.L.tf_track_texture_device(self.h, d_depth or None, d_rgba or None, d_start or None,
+                                                None if icp_params is None else C.byref(icp_params),
+                                                None if sdf_params is None else C.byref(sdf_params),
+                                                None if accept is None else C.byref(accept), d_out or None,
+                                                d_pose_out or None, int(frame_id)))
+
+    def pose_inverse_download(self, d_pose):
+        """The block the posed patch stage reads, derived from the tf_device_pose at d_pose -> PoseInverse (waits once)"""
+        out = PoseInverse()
+        self._ck(self.L.tf_pose_inverse_download(self.h, d_pose or None, C.byref(out), C.sizeof(out)))
         return out
 
     # -- relocalisation against the cached keyframes (tf_reloc_*, tf_relocalise; read-only)

@@ -8,6 +8,8 @@
 //   k_patch<P, B, F>   one WAVE per patch: Patch::CalculateTexCoords (Structure/Patch.cpp:40-108, lane =
 //                      vertex, coalesced plane rows, bbox / vote by wave reductions) and / or
 //                      Atlas::UpdateBuffer (Structure/Atlas.cpp:71-91, slot rows written as dwords)
+//   k_patch_posed      k_patch<true, true, true> of a frame whose pose is in device memory: T_g_l from the handle's
+//                      PoseInverse block (tf_devpose.h), nothing done where its gate is off
 //   k_cc_*             Chisel::CompensateColor reductions + transfer (Structure/Chisel.cpp:198-286)
 //   k_draw             Chisel::DrawMeshes vertex / index packing (Structure/Chisel.cpp:288-355)
 //
@@ -21,6 +23,7 @@
 
 #include "tf_cc_solve.h"
 #include "tf_devfn.h"
+#include "tf_devpose.h"
 #include "tf_draw_body.h"
 #include "tf_patch_body.h"
 #include "tf_volume.h"
@@ -162,6 +165,16 @@ __global__ __launch_bounds__(1024) void k_patch_assign(VolumeDev v, uint32_t n) 
 template <bool PROJECT, bool BLIT, bool FUSED>
 __global__ __launch_bounds__(256) void k_patch(VolumeDev v, Cam cam, int par, KfDev kf_fused) {
   patch_body<PROJECT, BLIT, FUSED>(v, cam, par, kf_fused, blockIdx.x, gridDim.x);
+}
+// k_patch<true, true, true> for a frame whose pose is in device memory (tf_devpose.h): T_g_l comes from the block
+// k_pose_consts wrote, through a uniform pointer, into the record the host handed over by value (images, stride, frame id);
+// a block whose gate is off: no patch is touched, no slot handed out
+__global__ __launch_bounds__(256) void k_patch_posed(VolumeDev v, Cam cam, int par, KfDev kf_fused,
+                                                     const PoseInverse* __restrict__ inv) {
+  if (inv->gate == 0) return;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) kf_fused.T[i] = inv->T[i];
+  patch_body<true, true, true>(v, cam, par, kf_fused, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -552,6 +565,11 @@ static int upload_work(tf_volume* v, const int32_t* ids, const int* kfslot, int6
 void launch_patch_fused(tf_volume* v, const VolumeDev& d, int par, const KfDev& kf, hipStream_t s) {
   prof_begin(v, TF_PROF_PATCH_PROJECT, s);
   hipLaunchKernelGGL((k_patch<true, true, true>), dim3(1024), dim3(256), 0, s, d, v->cam, par, kf);
+  prof_end(v, s);
+}
+void launch_patch_posed(tf_volume* v, const VolumeDev& d, int par, const KfDev& kf, const PoseInverse* d_inv, hipStream_t s) {
+  prof_begin(v, TF_PROF_PATCH_PROJECT, s);
+  hipLaunchKernelGGL(k_patch_posed, dim3(1024), dim3(256), 0, s, d, v->cam, par, kf, d_inv);
   prof_end(v, s);
 }
 

@@ -531,12 +531,13 @@ int patch_launched(tf_volume* v) {
   }
   return TF_OK;
 }
-int patch_flush(tf_volume* v) {  // the pending patch stage as a launch of its own
+int patch_flush(tf_volume* v, const PoseInverse* d_inv) {  // the pending patch stage as a launch of its own
   AtlasState& a = v->atlas;
   if (!a.pend_patch.on) return TF_OK;
   {
     AtlasWriteScope aw(v, a.pend_patch.st.kf.kf_id);
-    launch_patch_fused(v, v->dev, a.pend_patch.st.par, a.pend_patch.st.kf, v->stream);
+    if (d_inv) launch_patch_posed(v, v->dev, a.pend_patch.st.par, a.pend_patch.st.kf, d_inv, v->stream);
+    else launch_patch_fused(v, v->dev, a.pend_patch.st.par, a.pend_patch.st.kf, v->stream);
   }
   TF_HIP(hipGetLastError());
   return patch_launched(v);
@@ -622,9 +623,11 @@ int enqueue_frames(tf_volume* v, int64_t n, int64_t n_ahead, const float* const*
     if (carry) { int rc = patch_launched(v); if (rc) return rc; }
     if (hc && tex) {
       // (the next frame's selection role rode on this launch: its band counts can be published behind this frame's exchange)
-      int rc = texture_stage(v, cur.sel, cur.img, cur.epoch, tex->pose_inv16 + 16 * i, tex->first_frame_id + (int32_t)i, claimed,
-                             hn ? nxt.sel.ctl : nullptr, false, /*sized_xchg=*/true);
+      static const float no_matrix[16] = {};  // a frame whose pose is in device memory: the stage is armed without one ...
+      int rc = texture_stage(v, cur.sel, cur.img, cur.epoch, tex->d_inv ? no_matrix : tex->pose_inv16 + 16 * i,
+                             tex->first_frame_id + (int32_t)i, claimed, hn ? nxt.sel.ctl : nullptr, false, /*sized_xchg=*/true);
       if (rc) return rc;
+      if (tex->d_inv && (rc = patch_flush(v, tex->d_inv))) return rc;  // ... and goes out now, with the device's
     }
   }
   for (int64_t k = 0; k < n_ahead; ++k) {

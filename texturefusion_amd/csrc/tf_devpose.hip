@@ -6,7 +6,8 @@
 //   k_pose_consts    one wave: the cell -> the handle's PoseConsts block: the Pose, the pose-dependent fields of
 //                    make_select_consts' struct (tf_host_math.h, operation by operation: f32 multiplies and sequential
 //                    adds, contraction off), the gate word.  The fields that depend on the resolution alone come from
-//                    the host as an argument.
+//                    the host as an argument.  A second lane of the same launch writes the handle's PoseInverse block:
+//                    devpose_inverse16 of the cell (tf_devpose.h) and the gate word again, for the patch stage.
 //   k_track_finish   one lane: tf_track_frame's composition of its result (stage, pose), the acceptance test
 //                    (tf_devpose.h: track_accepted, tf_relocalise's), the output cell
 // and the twins that read a cell or the block, each next to the body it calls:
@@ -14,11 +15,15 @@
 //   k_raycast_posed (tf_ray.hip)                    the model maps at the cell's pose
 //   k_track_start (tf_align_icp.hip)                the projective stage starts from the cell
 //   k_stage2_start (tf_align.hip)                   the SDF stage starts from the projective stage's result where it held
+//   k_patch_posed (tf_atlas.hip)                    the patch stage of a frame projects with the PoseInverse block's matrix
 //
 // tf_track_frame_device:            raycast, projective stage, SDF stage, finish: 2 + 2 launches and 2 per evaluation
 // tf_integrate_frame_posed_device:  consts, K-B, K-C, then the frame launch every integrated frame has (K-A)
-// Not here: texturing from a device pose (tf_stream_frames_textured_device takes pose_inv16 from the host), a multi-rank
-// form, a group or colour form of the device tracker.
+// tf_integrate_frame_textured_posed_device: the same, the frame's mesher behind K-A, then the patch stage as a launch of
+//                                   its own (k_patch_posed): it never rides on k_frame and is never pending across calls
+// Not here: the posed patch stage as a role of k_frame, a textured form for a handle with untextured marks pending (the
+// host cannot know the gate), a multi-rank form, a group or colour form of the device tracker, caching the tracked frame
+// as a keyframe (the keyframe table's mirror lives on the host).
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
@@ -34,11 +39,20 @@ namespace tf {
 namespace {
 
 __global__ __launch_bounds__(64) void k_pose_consts(const tf_device_pose* __restrict__ cell, SelectConsts host,
-                                                    PoseConsts* __restrict__ out) {
+                                                    PoseConsts* __restrict__ out, PoseInverse* __restrict__ inv) {
   const int lane = threadIdx.x;
   float p[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) p[i] = cell->pose[i];
+  if (lane == 32) {  // the patch stage's matrix, next to lane 0's block
+    float T[16];
+    devpose_inverse16(p, T);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) inv->T[i] = T[i];
+    inv->gate = devpose_ok(cell) ? 1 : 0;
+    inv->pad[0] = inv->pad[1] = inv->pad[2] = 0;
+    return;
+  }
   const float res = host.res;
   float rot[3][3];  // cameraPose.linear().transpose()
 #pragma unroll
@@ -119,11 +133,11 @@ __global__ __launch_bounds__(64) void k_track_finish(FinishArgs a) {
   a.pose_out->reserved[0] = a.pose_out->reserved[1] = a.pose_out->reserved[2] = 0;
 }
 
+// both blocks of the handle (first use: allocated)
 int devpose_block(tf_volume* v, PoseConsts** pc) {
-  if (!v->devpose) {
-    const int rc = v->devpose.alloc(sizeof(PoseConsts));
-    if (rc) return rc;
-  }
+  int rc;
+  if (!v->devpose && (rc = v->devpose.alloc(sizeof(PoseConsts)))) return rc;
+  if (!v->devpose_inv && (rc = v->devpose_inv.alloc(sizeof(PoseInverse)))) return rc;
   *pc = v->devpose.as<PoseConsts>();
   return TF_OK;
 }
@@ -131,7 +145,7 @@ int devpose_block(tf_volume* v, PoseConsts** pc) {
 void pose_consts_enqueue(tf_volume* v, const tf_device_pose* d_pose, PoseConsts* pc) {
   const float eye[12] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
   const SelectConsts host = make_select_consts(eye, v->res);  // read for the resolution's fields; the pose's are the kernel's
-  hipLaunchKernelGGL(k_pose_consts, dim3(1), dim3(64), 0, v->stream, d_pose, host, pc);
+  hipLaunchKernelGGL(k_pose_consts, dim3(1), dim3(64), 0, v->stream, d_pose, host, pc, v->devpose_inv.as<PoseInverse>());
 }
 
 bool partitioned(const tf_volume* v) {
@@ -192,7 +206,10 @@ int track_enqueue(tf_volume* v, const float* d_depth, const tf_device_pose* d_st
 // The frame's selection from *d_pose, then the frame launch of tf_integrate_frames_device(v, 1, ..): to enqueue_frames the
 // frame is one whose selection a streaming call made ahead, so it goes on with K-A at once, carries a pending patch stage,
 // stamps the progress word and advances the handle's counters exactly as a host-pose frame does.  K-A reads no pose.
-int integrate_enqueue(tf_volume* v, const float* d_depth, const uint8_t* d_rgba, const tf_device_pose* d_pose) {
+// frame_id != NULL: the textured unit, tf_stream_frames_textured_device(v, 1, 0, ..)'s -- the frame's mesher behind K-A, then
+// its patch stage as a launch of its own with the matrix k_pose_consts left in the handle's PoseInverse block.
+int integrate_enqueue(tf_volume* v, const float* d_depth, const uint8_t* d_rgba, const tf_device_pose* d_pose,
+                      const int32_t* frame_id = nullptr) {
   PoseConsts* pc = nullptr;
   int rc = devpose_block(v, &pc);
   if (rc) return rc;
@@ -207,13 +224,36 @@ int integrate_enqueue(tf_volume* v, const float* d_depth, const uint8_t* d_rgba,
   v->primed[0].depth = d_depth;
   memcpy(v->primed[0].pose, none, sizeof(none));
   v->n_primed = 1;
-  if ((rc = enqueue_frames(v, 1, 0, &d_depth, d_rgba ? &d_rgba : nullptr, none, nullptr))) return rc;
+  const TexturedArgs tex{nullptr, frame_id ? *frame_id : 0, v->devpose_inv.as<PoseInverse>()};
+  if ((rc = enqueue_frames(v, 1, 0, &d_depth, d_rgba ? &d_rgba : nullptr, none, frame_id ? &tex : nullptr))) return rc;
   return bind_frame(v, d_depth, d_rgba);
+}
+
+// what the textured forms refuse on top of integrate_check: from the arguments ...
+int textured_check(const uint8_t* d_rgba) {
+  if (!d_rgba) { set_error("the textured flow needs a colour image per frame"); return TF_ERR_INVALID; }
+  return TF_OK;
+}
+// ... and from the handle's state, once the frames and the patch stage it still owed are on the stream
+int textured_state_check(const tf_volume* v) {
+  if (v->atlas.phase1_on) {
+    set_error("a texture stage is half done: call tf_texture_frame_device_phase(.., 2) first");
+    return TF_ERR_INVALID;
+  }
+  if (v->clear_floor < v->epoch) {
+    set_error("device pose: frames integrated without texturing are still waiting for a mesher, and a cell that holds no "
+              "pose would clear their marks without patches: texture them first (tf_texture_frame_device)");
+    return TF_ERR_INVALID;
+  }
+  return TF_OK;
 }
 
 }  // namespace
 
-void devpose_release(tf_volume* v) { v->devpose = DevMem{}; }
+void devpose_release(tf_volume* v) {
+  v->devpose = DevMem{};
+  v->devpose_inv = DevMem{};
+}
 
 }  // namespace tf
 
@@ -255,6 +295,43 @@ int tf_track_integrate_device(tf_volume* v, const float* d_depth, const uint8_t*
   TF_DEV(v);
   if ((rc = track_enqueue(v, d_depth, d_start, *icp, *sdf, accept, d_out, d_pose_out))) return rc;
   return integrate_enqueue(v, d_depth, d_rgba, d_pose_out);
+}
+
+int tf_integrate_frame_textured_posed_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba,
+                                             const tf_device_pose* d_pose, int32_t frame_id) {
+  int rc = integrate_check(v, d_depth, d_rgba, d_pose);
+  if (rc || (rc = textured_check(d_rgba))) return rc;
+  TF_DEV_STREAM(v);  // (a patch stage an earlier streaming call left pending rides on this frame's launch, as on any frame's)
+  if ((rc = textured_state_check(v))) return rc;
+  return integrate_enqueue(v, d_depth, d_rgba, d_pose, &frame_id);
+}
+
+int tf_track_texture_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba, const tf_device_pose* d_start,
+                            const tf_align_icp_params* icp, const tf_align_params* sdf, const tf_track_accept* accept,
+                            tf_track_result* d_out, tf_device_pose* d_pose_out, int32_t frame_id) {
+  int rc = track_check_device(v, d_depth, d_start, icp, sdf, accept, d_out, d_pose_out);
+  if (rc || (rc = integrate_check(v, d_depth, d_rgba, d_pose_out)) || (rc = textured_check(d_rgba))) return rc;
+  TF_DEV(v);
+  if ((rc = textured_state_check(v))) return rc;
+  if ((rc = track_enqueue(v, d_depth, d_start, *icp, *sdf, accept, d_out, d_pose_out))) return rc;
+  return integrate_enqueue(v, d_depth, d_rgba, d_pose_out, &frame_id);
+}
+
+int tf_pose_inverse_download(tf_volume* v, const tf_device_pose* d_pose, void* out, size_t bytes) {
+  if (!v || !d_pose || !out) { set_error("null argument"); return TF_ERR_INVALID; }
+  if (bytes > sizeof(PoseInverse) || !aligned_to(d_pose, 16)) {
+    set_error("pose inverse: at most 80 bytes, from a 16-byte aligned cell");
+    return TF_ERR_INVALID;
+  }
+  TF_DEV_READER(v);
+  PoseConsts* pc = nullptr;
+  const int rc = devpose_block(v, &pc);
+  if (rc) return rc;
+  pose_consts_enqueue(v, d_pose, pc);
+  TF_HIP(hipGetLastError());
+  TF_HIP(hipMemcpyAsync(out, v->devpose_inv.p, bytes, hipMemcpyDeviceToHost, v->stream));
+  TF_HIP(hipStreamSynchronize(v->stream));
+  return TF_OK;
 }
 
 int tf_pose_consts_download(tf_volume* v, const tf_device_pose* d_pose, void* out, size_t bytes) {

@@ -332,6 +332,7 @@ struct tf_volume {
   tf::AlignIcpState align_icp;
   tf::RelocState reloc;
   tf::DevMem devpose;  // one PoseConsts (tf_devpose.h): what k_pose_consts derives from a pose cell; null until first use
+  tf::DevMem devpose_inv;  // one PoseInverse: the cell's rigid inverse for the patch stage, written by the same launch
   tf::ModelState model;
   uint64_t model_gen = 0;  // advanced by every entry point that is not a whitelisted reader (TF_DEV_READER)
   int64_t comm_cap = 0;  // > 0: the fused textured flow exchanges the ghost band after every voxel update
@@ -390,7 +391,10 @@ uint32_t nbr_next_seq(tf_volume* v);  // neighbour table: the seq of the filter 
 // the dirty set (Chisel::meshesToUpdate) as a device list in scratch.d: [0,16) count word, ids from byte 16 (tf_mesh.hip)
 int dirty_list_enqueue(tf_volume* v);
 void launch_dirty_frame_store(const VolumeDev& v, int par, uint32_t stamp, const KfStoreArgs& a, hipStream_t s);  // tf_mesh.hip
-int patch_flush(tf_volume* v);
+struct PoseInverse;  // tf_devpose.h
+// the pending patch stage as a launch of its own; d_inv: the frame's matrix is the one in that device block, where its gate
+// is set (k_patch_posed), not the one the stage was armed with
+int patch_flush(tf_volume* v, const PoseInverse* d_inv = nullptr);
 // the pending patch stage has been put on the stream (as a role of a frame / filter launch or on its own)
 int patch_launched(tf_volume* v);
 // Software-pipelined enqueue of n frames (+ n_ahead selection-only ones) on the handle's stream, and the textured flow's
@@ -398,6 +402,9 @@ int patch_launched(tf_volume* v);
 struct TexturedArgs {
   const float* pose_inv16;  // per frame: f32(SE3d.inverse().matrix()) of the frame's pose
   int32_t first_frame_id;
+  // one frame whose pose is in device memory (tf_devpose.hip): pose_inv16 is not read, the frame's patch stage goes out
+  // behind its mesher as a launch of its own that takes the matrix from this block, and nothing stays pending
+  const PoseInverse* d_inv = nullptr;
 };
 int enqueue_frames(tf_volume* v, int64_t n, int64_t n_ahead, const float* const* d_depth, const uint8_t* const* d_rgba,
                    const float* poses12, const TexturedArgs* tex);
@@ -478,7 +485,7 @@ int track_icp_posed(tf_volume* v, const float* d_depth, const tf_device_pose* d_
 int track_sdf_posed(tf_volume* v, const float* d_depth, const int32_t* d_prev_status, const float* d_prev_pose,
                     const tf_align_params& p, tf_align_result* d_result);
 void discard_primed(tf_volume* v);       // the selections made ahead by a streaming call are dropped (tf_capi.cpp)
-void devpose_release(tf_volume* v);      // frees tf_devpose.hip's block
+void devpose_release(tf_volume* v);      // frees tf_devpose.hip's blocks
 // the resident model stream (tf_model.hip).  model_pack_enqueue: list, rank, scan and write on the handle's stream, nothing
 // read back (the buffers exist and have a capacity); model_stream_sync: the pack, one wait for the control block, the
 // buffers grown and the pack repeated on overflow -- ModelState::nv / ni are the counts afterwards; model_release frees all
@@ -486,6 +493,8 @@ int model_pack_enqueue(tf_volume* v);
 int model_stream_sync(tf_volume* v);
 void model_release(tf_volume* v);
 void launch_patch_fused(tf_volume* v, const VolumeDev& d, int par, const KfDev& kf, hipStream_t s);
+// the same with KfDev::T taken from *d_inv on the device; a block whose gate is off: the launch does nothing
+void launch_patch_posed(tf_volume* v, const VolumeDev& d, int par, const KfDev& kf, const PoseInverse* d_inv, hipStream_t s);
 inline uint64_t host_pack_id(const int32_t id[3]) {
   return ((uint64_t)((uint32_t)(id[0] + (1 << 20)) & 0x1FFFFFu) << 42) |
          ((uint64_t)((uint32_t)(id[1] + (1 << 20)) & 0x1FFFFFu) << 21) |
