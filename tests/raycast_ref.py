@@ -1,9 +1,11 @@
 """numpy float32 restatement of tf_ray.hip (a helper of the raycast tests, not a test module).
 
 k_query: GetSDF / GetWeight / GetSDFAndGradient / trilinear SDF / trilinear colour, operation for operation in f32 (the
-library is built with -ffp-contract=off, so the device results are reproduced bit for bit).  k_raycast: the march (chunk
-DDA over absent chunks, voxel steps where the sampler is invalid, max(voxel, 0.75 sdf) where it is valid, linear
-refinement at the first + -> - crossing) over the same samples.
+library is built with -ffp-contract=off, so the device results are reproduced bit for bit).  k_raycast, all four maps
+(RefVolume.raycast_maps): the march (chunk DDA over absent chunks, voxel steps where the sampler is invalid,
+max(voxel, 0.75 sdf) where it is valid, linear refinement at the first + -> - crossing) over the same samples, the vertex
+o + thit * d, the normal from six taps of the trilinear SDF (central, or one-sided and doubled, or none), the trilinear
+colour at the hit, and a per-pixel trace of the branches a ray took.  raycast_depth is its depth map.
 
 The volume is a set of chunks: ids [n, 3] int32 with sdf / weight [n, 512] f32 and colour [n, 2048] u16 (R, G, B, count
 per voxel), as Volume.get_chunks (HIP) or oracle.api.Volume.get_chunk return them.
@@ -17,6 +19,15 @@ STEP_K = F(0.75)
 GAP = F(4.0)
 VOX_LIMIT = F(8388607.0)
 CHUNK_LIMIT = F(1048576.0)
+END_HIT, END_BACK, END_FAR, END_STEPS, END_CHUNK = 1, 2, 3, 4, 5  # trace["end"] of raycast_maps
+# One rule of the march or of the normal changed at a time, for tests/test_raycast_cpu.py alone: the hand-built cases of
+# tests/ray_inputs.py must tell every one of these from the kernel's rule.
+#   gap_lt            t - pt < gap instead of <=            hit_lt           s < 0 closes a crossing instead of s <= 0
+#   far_lt            t < far instead of <=                 no_back          no - -> + break
+#   no_eps            the chunk jump lands on the chunk's face, without eps
+#   one_sided_1       the one-sided difference not doubled  one_sided_sign   and with the wrong sign
+#   reset_on_invalid  an invalid sample forgets the last valid one
+_FLIPS = ("gap_lt", "hit_lt", "far_lt", "no_back", "no_eps", "one_sided_1", "one_sided_sign", "reset_on_invalid")
 
 
 def _floor_in(a, lim):
@@ -183,9 +194,24 @@ class RefVolume:
         flags |= np.where(okt, 8, 0).astype(np.uint32) | np.where(okc, 16, 0).astype(np.uint32)
         return {"flags": flags, "sdf": np.where(ok_sdf, sd, F(0)), "weight": w, "grad": grad, "sdf_tri": st, "rgb": rgb}
 
-    # ---- k_raycast: the march, depth and hit mask --------------------------------------------------------------
+    # ---- k_raycast: the march and the four maps -----------------------------------------------------------------
     def raycast_depth(self, pose, fx, fy, cx, cy, W, H, near, far, max_steps):
         """camera-frame depth [H, W] (0 = miss); fx .. cy as given to tf_set_camera (truncated here)"""
+        return self.raycast_maps(pose, fx, fy, cx, cy, W, H, near, far, max_steps)["depth"]
+
+    def raycast_maps(self, pose, fx, fy, cx, cy, W, H, near, far, max_steps, _flip=None):
+        """raycast_body, all four maps: 'depth' [H, W] f32 (0 = miss), 'vertex' [3, H, W] f32, 'normal' [3, H, W] f32,
+        'rgba' [H, W, 4] u8, and 'trace', a dict of small integers per pixel ([H, W] unless noted) that says which way
+        a ray went:
+          end      how the march ended: END_HIT, END_BACK (- -> +), END_FAR (t > far), END_STEPS (the step cap),
+                   END_CHUNK (a chunk coordinate out of range)
+          steps    samples taken (loop iterations entered)
+          jumps    absent-chunk jumps;  invalid  steps over an invalid sample;  gap  valid samples whose pairing the
+                   kRayGap rule refused
+          m        [3, H, W] the normal's validity bits per axis (bit 0: minus tap, bit 1: plus tap), -1 on a miss
+          t_end    f32: t when the march ended (on a hit or a back break, the t of the sample that ended it)
+        fx .. cy as given to tf_raycast_camera (truncated here).  _flip: see _FLIPS."""
+        assert _flip is None or _flip in _FLIPS
         res = self.res
         ir, cs, rc, eps, gap = F(1) / res, F(8) * res, F(1) / (F(8) * res), res * F(0.015625), GAP * res
         fxi, fyi, cxs, cys = F(int(fx)), F(int(fy)), F(int(cx)) + F(0.5), F(int(cy)) + F(0.5)
@@ -202,17 +228,23 @@ class RefVolume:
         pok = np.zeros(n, bool)
         thit = np.full(n, F(-1), np.float32)
         live = np.ones(n, bool)
+        end = np.full(n, END_STEPS, np.int8)
+        steps, jumps, invalid, gaps = (np.zeros(n, np.int32) for _ in range(4))
         for _ in range(int(max_steps)):
-            live &= t <= F(far)
+            in_far = (t < F(far)) if _flip == "far_lt" else (t <= F(far))
+            end[live & ~in_far] = END_FAR
+            live &= in_far
             idx = np.nonzero(live)[0]
             if len(idx) == 0:
                 break
+            steps[idx] += 1
             tt = t[idx]
             dd = [a[idx] for a in d]
             x = [o[a] + tt * dd[a] for a in range(3)]
             cc, okc = zip(*(_floor_in(x[a] * rc, CHUNK_LIMIT) for a in range(3)))
             inr = okc[0] & okc[1] & okc[2]
             live[idx[~inr]] = False
+            end[idx[~inr]] = END_CHUNK
             absent = inr & (self.slot(*cc) < 0)
             with np.errstate(divide="ignore", invalid="ignore"):
                 tx = []
@@ -220,29 +252,77 @@ class RefVolume:
                     hi = ((cc[a] + 1).astype(np.float32) * cs - o[a]) / dd[a]
                     lo = (cc[a].astype(np.float32) * cs - o[a]) / dd[a]
                     tx.append(np.where(dd[a] > 0, hi, np.where(dd[a] < 0, lo, np.float32(np.inf))))
-            tn = np.maximum(np.minimum(np.minimum(tx[0], tx[1]), tx[2]), tt) + eps
+            tn = np.maximum(np.minimum(np.minimum(tx[0], tx[1]), tx[2]), tt)
+            if _flip != "no_eps":
+                tn = tn + eps
             s, oks, _, _ = self.trilinear(np.stack(x, 1), want_rgb=False)
             present = inr & ~absent
             inval = present & ~oks
             val = present & oks
             p_s, p_t = ps[idx], pt[idx]
-            p_ok = pok[idx] & (tt - p_t <= gap)
-            hit = val & p_ok & (p_s > 0) & (s <= 0)
+            near_enough = (tt - p_t < gap) if _flip == "gap_lt" else (tt - p_t <= gap)
+            p_ok = pok[idx] & near_enough
+            hit = val & p_ok & (p_s > 0) & ((s < 0) if _flip == "hit_lt" else (s <= 0))
             back = val & p_ok & (p_s <= 0) & (s > 0) & ~hit
+            if _flip == "no_back":
+                back[:] = False
             with np.errstate(divide="ignore", invalid="ignore"):
                 th = p_t + (tt - p_t) * (p_s / (p_s - s))
             thit[idx[hit]] = th[hit]
             live[idx[hit | back]] = False
+            end[idx[hit]] = END_HIT
+            end[idx[back]] = END_BACK
+            jumps[idx[absent]] += 1
+            invalid[idx[inval]] += 1
+            gaps[idx[val & pok[idx] & ~near_enough]] += 1
             go = val & ~hit & ~back
             newt = tt.copy()
             newt[absent] = tn[absent]
             newt[inval] = tt[inval] + res
             newt[go] = tt[go] + np.maximum(res, STEP_K * s[go])
             t[idx] = newt
-            pok[idx] = np.where(go, True, np.where(absent, False, np.where(inval, pok[idx], p_ok)))
+            keep = np.zeros(len(idx), bool) if _flip == "reset_on_invalid" else pok[idx]
+            pok[idx] = np.where(go, True, np.where(absent, False, np.where(inval, keep, p_ok)))
             pt[idx[go]] = tt[go]
             ps[idx[go]] = s[go]
-        return np.where(thit >= 0, thit, F(0)).reshape(H, W)
+        hit = thit >= 0
+        hidx = np.nonzero(hit)[0]
+        h = [(o[a] + thit * d[a])[hidx] for a in range(3)]
+        vertex = np.zeros((3, n), np.float32)
+        normal = np.zeros((3, n), np.float32)
+        rgba = np.zeros((n, 4), np.uint8)
+        m = np.full((3, n), -1, np.int8)
+        if len(hidx):
+            for a in range(3):
+                vertex[a, hidx] = h[a]
+            # the six taps: one voxel each way through the trilinear SDF (an invalid tap reads 0)
+            g, ok = [], np.ones(len(hidx), bool)
+            for a in range(3):
+                tap = []
+                for sg in (-res, res):
+                    p = [h[b] + (sg if b == a else F(0)) for b in range(3)]
+                    tap.append(self.trilinear(np.stack(p, 1), want_rgb=False)[:2])
+                (sm, okm), (sp, okp) = tap
+                ma = okm.astype(np.int8) + 2 * okp.astype(np.int8)
+                m[a, hidx] = ma
+                k2 = F(1) if _flip == "one_sided_1" else F(2)
+                if _flip == "one_sided_sign":
+                    k2 = -k2
+                g.append(np.where(ma == 3, sp - sm, np.where(ma == 2, k2 * sp, -k2 * sm)).astype(np.float32))
+                ok &= ma != 0
+            ln = np.sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2])
+            ok &= ln > 0
+            with np.errstate(divide="ignore", invalid="ignore"):
+                for a in range(3):
+                    normal[a, hidx] = np.where(ok, g[a] / ln, F(0))
+            _, _, rgb, okc = self.trilinear(np.stack(h, 1))
+            rgba[hidx, :3] = np.where(okc[:, None], rgb, 0)
+            rgba[hidx, 3] = 255
+        img = lambda a: a.reshape(H, W)
+        trace = {"end": img(end), "steps": img(steps), "jumps": img(jumps), "invalid": img(invalid), "gap": img(gaps),
+                 "m": m.reshape(3, H, W), "t_end": img(t.copy())}
+        return {"depth": img(np.where(hit, thit, F(0))), "vertex": vertex.reshape(3, H, W), "normal": normal.reshape(3, H, W),
+                "rgba": rgba.reshape(H, W, 4), "trace": trace}
 
 
 # ---- the S-wall scene of the raycast tests --------------------------------------------------------------------------

@@ -130,7 +130,8 @@ def test_raycast_matches_the_restated_march(wall_pair, room):
             gv.raycast_camera(None)
         exp = ref.raycast_depth(pose, SMALL.fx, SMALL.fy, SMALL.cx, SMALL.cy, SMALL.width, SMALL.height, 0.1, 5.0, 2048)
         assert np.array_equal(r["depth"] > 0, exp > 0), "hit masks differ at %d pixels" % ((r["depth"] > 0) != (exp > 0)).sum()
-        assert np.abs(r["depth"] - exp).max() <= 1e-4
+        diff = r["depth"].view(np.uint32) != exp.view(np.uint32)
+        assert not diff.any(), "depth differs at %d pixels, first (y, x) %s" % (diff.sum(), np.argwhere(diff)[:4].tolist())
         assert (exp > 0).mean() > cover
 
 

@@ -21,7 +21,10 @@
 //   g0 = lerp(e0, e1, fy), g1 = lerp(e2, e3, fy);  result = lerp(g0, g1, fz).
 //   SDF: valid iff all 8 corners exist with weight > 0.  Colour: per corner the mean R / count, G / count, B / count (f32
 //   divisions, ColorVoxel.h:44-55), the same lerps, then u8 = min(255, floor(x + 0.5)); valid iff all 8 counts > 0.
-// The library is built with -ffp-contract=off, so tests/raycast_ref.py restates all of this bit for bit in numpy.
+// The library is built with -ffp-contract=off, so tests/raycast_ref.py restates all of this bit for bit in numpy: k_query in
+// RefVolume.query, and raycast_body's four maps -- the march, vertex = o + thit * d, the normal's six taps with sp - sm /
+// 2 sp / -2 sm per axis, the colour at the hit -- in RefVolume.raycast_maps (tests/test_gpu_ray_edges.py holds the kernel to
+// it on hand-built volumes, tests/test_gpu_raycast.py on integrated scenes).
 //
 // GetDistanceFromSurface, in this order, all f32 (tests/refine_ref.py restates it):
 //   r = (p - res / 2) * (1 / res) per axis (the reciprocal rounded first); d = r - floor(r);
