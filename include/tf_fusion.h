@@ -760,7 +760,8 @@ TF_API int tf_align_unit_group(tf_volume* v, tf_unit_group* group, int rigid, co
  * and restated in tests/align_icp_ref.py.  The maps and the model pose do not change during a call; re-rendering between
  * levels is the caller's choice, through a second call.  A call is 1 + 2 launches per evaluation, all enqueued up front.
  * Read-only; its state and log are its own: tf_align_log, tf_align_color_log and tf_align_group_log keep their meaning.
- * Not here: frame normals and a normal-compatibility gate, a photometric row, a group form, multi-rank. */
+ * A normal-compatibility gate from the frame's own normals is a setting of the handle: the section below tf_track_frame.
+ * Not here: a photometric row, a group form, multi-rank. */
 typedef struct tf_align_icp_params {
   tf_align_params geo;     /* levels, depth range, huber, damping, eps, min_valid; max_residual gates |r| */
   float max_distance;      /* gate on |pw - vm| */
@@ -805,6 +806,45 @@ TF_API int tf_align_icp_residuals_device(tf_volume* v, const float* d_depth, con
  * device memory, and waits for nothing.  TF_ERR_INVALID (nothing launched, out untouched) for what either stage rejects. */
 TF_API int tf_track_frame(tf_volume* v, const float* depth, const float pose[12], const tf_align_icp_params* icp_params,
                           const tf_align_params* sdf_params, tf_track_result* out);
+
+/* ---- the projective ICP gated by frame normals (tf_align_icp_gate.hip) --------------------------
+ * KinectFusion's third rejection test.  Without it a pixel of one wall that projects onto the model's image of another
+ * wall is a valid pair whenever the two points lie within max_distance: at every concave or convex edge.  The gate is a
+ * setting of the handle, off in a new handle and off again after tf_volume_reset.  Every call that runs the projective ICP
+ * reads it: tf_align_frame_icp(_device), tf_align_icp_residuals(_device), tf_track_frame, tf_track_frame_device,
+ * tf_track_integrate_device, tf_track_texture_device, tf_relocalise.
+ * The frame normal of a sampled pixel (x, y) at the level's stride s, depth z0 in range (bit 0), from its neighbours
+ * L = (x - s, y), R = (x + s, y), U = (x, y - s), D = (x, y + s): it exists iff all four lie inside the image, each depth
+ * z_n passes bit 0's test and |z_n - z0| <= max_depth_jump, and with pc(n) = (dcx_n z_n, dcy_n z_n, z_n), a = pc(R) - pc(L),
+ * b = pc(D) - pc(U), n = b x a (towards the camera, as the raycaster's normal on a surface seen from its front; not
+ * normalised), l2 = |n|^2 is finite and > 0.
+ * Flag bit 4 (16): bits 0 to 3 are set and the frame normal exists.  Bit 5 (32): bit 4 is set and, with nw = R n,
+ * d = nw . nm, m2 = |nm|^2: d > 0 and d d >= ((min_normal_cos min_normal_cos) l2) m2.  With the gate on a pixel is valid
+ * iff flags == 63; with it off nothing changes (flags <= 15, valid iff 15).  r, assoc, the Jacobian (still with the model
+ * normal), the Huber weight, the sums and their order, the solve, levels, stops, statuses, results and log records are
+ * untouched.  All f32, the order of operations fixed in tf_align_icp_gate.hip and restated in tests/align_icp_gate_ref.py.
+ * The normal is formed in the rows launch, every evaluation: no normal map, no further launch.
+ * The defaults are KinectFusion's 20 degrees and a round number; neither is tuned on recorded data.
+ * Not here: a per-call form of the gate, a gate for tf_align_frame's SDF stage, a depth pyramid. */
+typedef struct tf_align_icp_gate {
+  float min_normal_cos;   /* in [0, 1] */
+  float max_depth_jump;   /* metres, > 0; +inf allowed: no discontinuity test */
+} tf_align_icp_gate;
+TF_API int tf_align_icp_gate_default(tf_align_icp_gate* out);          /* cosf(20 deg) = 0.9396926f, 0.1f */
+/* gate == NULL: off.  TF_ERR_INVALID, with nothing changed, for a NaN, a cosine outside [0, 1], or a jump that is not > 0.
+ * The setter and the getter launch nothing and wait for nothing; calls already enqueued keep the setting they were
+ * enqueued with.  *on = 0 / 1; *out = the gate that is set, or the defaults where none is. */
+TF_API int tf_align_icp_set_gate(tf_volume* v, const tf_align_icp_gate* gate);
+TF_API int tf_align_icp_get_gate(tf_volume* v, tf_align_icp_gate* out, int32_t* on);
+/* The frame's own normals, a pure function of the image, the camera, params->geo (stride[0], depth range) and *gate
+ * (max_depth_jump; not the handle's setting): n f32 planar [3][H][W], camera frame, NOT normalised, 0 where there is none
+ * or the pixel is not sampled.  It does not look at the model.  Read-only.  _device: asynchronous on the handle's stream;
+ * the host form stages through the scratch pool and waits once.  TF_ERR_INVALID (nothing launched, nothing written) for a
+ * null pointer, parameters tf_align_frame rejects (iters are not read) or a gate tf_align_icp_set_gate rejects. */
+TF_API int tf_align_icp_frame_normals_device(tf_volume* v, const float* d_depth, const tf_align_icp_params* params,
+                                             const tf_align_icp_gate* gate, float* d_normal3);
+TF_API int tf_align_icp_frame_normals(tf_volume* v, const float* depth, const tf_align_icp_params* params,
+                                      const tf_align_icp_gate* gate, float* normal3);
 
 /* ---- tracking and integrating with the pose kept on the device (tf_devpose.hip) ------------------
  * KinectFusion's loop on the stream: track frame f against the model, decide whether the result is good enough, integrate

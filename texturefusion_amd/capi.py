@@ -60,6 +60,8 @@ SYMBOLS = (
     "tf_align_group", "tf_align_group_device", "tf_align_group_log", "tf_align_unit_group",
     "tf_align_icp_default_params", "tf_align_frame_icp", "tf_align_frame_icp_device", "tf_align_icp_log",
     "tf_align_icp_residuals", "tf_align_icp_residuals_device", "tf_track_frame",
+    "tf_align_icp_gate_default", "tf_align_icp_set_gate", "tf_align_icp_get_gate", "tf_align_icp_frame_normals",
+    "tf_align_icp_frame_normals_device",
     "tf_track_accept_default", "tf_track_frame_device", "tf_integrate_frame_posed_device", "tf_track_integrate_device",
     "tf_pose_consts_download", "tf_integrate_frame_textured_posed_device", "tf_track_texture_device",
     "tf_pose_inverse_download",
@@ -209,6 +211,10 @@ class AlignIcpParamsC(C.Structure):
                 ("ray_max_steps", C.c_int32)]
 
 
+class AlignIcpGateC(C.Structure):
+    _fields_ = [("min_normal_cos", C.c_float), ("max_depth_jump", C.c_float)]
+
+
 class TrackResult(C.Structure):
     _fields_ = [("icp", AlignResult), ("sdf", AlignResult), ("stage", C.c_int32), ("pose", C.c_float * 12)]
 
@@ -280,6 +286,19 @@ def AlignIcpParams(**kw):
         else:
             raise TypeError("tf_align_icp_params has no field %r" % k)
     return p
+
+
+def AlignIcpGate(**kw):
+    """tf_align_icp_gate: the library's defaults (tf_align_icp_gate_default) with fields replaced by keyword"""
+    g = AlignIcpGateC()
+    rc = lib().tf_align_icp_gate_default(C.byref(g))
+    if rc != TF_OK:
+        raise TFError(rc, lib().tf_last_error().decode())
+    for k, val in kw.items():
+        if k not in ("min_normal_cos", "max_depth_jump"):
+            raise TypeError("tf_align_icp_gate has no field %r" % k)
+        setattr(g, k, float(val))
+    return g
 
 
 class RelocParamsC(C.Structure):
@@ -518,6 +537,12 @@ def lib():
     L.tf_align_icp_residuals.argtypes = [vp, fp, fp, fp, fp, fp, aip, fp, C.POINTER(C.c_uint32), i32p]
     L.tf_align_icp_residuals_device.argtypes = [vp, vp, fp, vp, vp, fp, aip, vp, vp, vp]
     L.tf_track_frame.argtypes = [vp, fp, fp, aip, app, C.POINTER(TrackResult)]
+    agp = C.POINTER(AlignIcpGateC)
+    L.tf_align_icp_gate_default.argtypes = [agp]
+    L.tf_align_icp_set_gate.argtypes = [vp, agp]
+    L.tf_align_icp_get_gate.argtypes = [vp, agp, i32p]
+    L.tf_align_icp_frame_normals.argtypes = [vp, fp, aip, agp, fp]
+    L.tf_align_icp_frame_normals_device.argtypes = [vp, vp, aip, agp, vp]
     tap = C.POINTER(TrackAcceptC)
     L.tf_track_accept_default.argtypes = [tap]
     L.tf_track_frame_device.argtypes = [vp, vp, vp, aip, app, tap, vp, vp]
@@ -1304,6 +1329,32 @@ class Volume:
         self._ck(self.L.tf_align_icp_residuals_device(self.h, d_depth or None, _p(pose, C.c_float), d_vertex or None,
                                                       d_normal or None, mp, C.byref(params), d_r or None, d_flags or None,
                                                       d_assoc or None))
+
+    # -- the ICP's normal-compatibility gate (tf_align_icp_gate.hip): a setting of the handle, off until set
+    def align_icp_set_gate(self, gate=None):
+        """Gate every projective ICP of this handle by frame normals (an AlignIcpGate); None: off.  With it on a pixel is
+        valid where flags == 63."""
+        self._ck(self.L.tf_align_icp_set_gate(self.h, None if gate is None else C.byref(gate)))
+
+    def align_icp_get_gate(self):
+        """-> (on, AlignIcpGateC: the gate that is set, or the defaults where none is)"""
+        g, on = AlignIcpGateC(), C.c_int32(0)
+        self._ck(self.L.tf_align_icp_get_gate(self.h, C.byref(g), C.byref(on)))
+        return bool(on.value), g
+
+    def align_icp_frame_normals(self, depth, params=None, gate=None):
+        """The frame's own normals at params.geo.stride[0] -> [3, H, W] f32, camera frame, not normalised, 0 where there is
+        none; gate: an AlignIcpGate whose max_depth_jump is read (None: the defaults), not the handle's setting."""
+        d, H, W = self._align_depth(depth)
+        params = params or AlignIcpParams()
+        gate = gate or AlignIcpGate()
+        out = np.zeros((3, H, W), np.float32)
+        self._ck(self.L.tf_align_icp_frame_normals(self.h, _p(d, C.c_float), C.byref(params), C.byref(gate), _p(out, C.c_float)))
+        return out
+
+    def align_icp_frame_normals_device(self, d_depth, params, gate, d_normal3):
+        self._ck(self.L.tf_align_icp_frame_normals_device(self.h, d_depth or None, None if params is None else C.byref(params),
+                                                          None if gate is None else C.byref(gate), d_normal3 or None))
 
     def track_frame(self, depth, pose, icp_params=None, sdf_params=None):
         """The coarse-to-fine tracker: align_frame_icp with the model raycast at pose, then align_frame from its pose ->

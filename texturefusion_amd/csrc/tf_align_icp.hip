@@ -35,11 +35,14 @@
 // No atomics, no counters, no polling: a call is 1 + 2 launches per evaluation, all enqueued up front; a launch first
 // reads the state word (bit 0: stopped, bits 8..: levels that are finished) and returns if it has nothing to do.  The
 // model pose and the maps do not change during a call.
+// With a gate set on the handle (tf_align_icp_set_gate) the rows launch is k_gated_rows of tf_align_icp_gate.hip: the same
+// association (icp_assoc, tf_align_icp_rows.h) and flag bits 4 and 5 from the frame's own normal; everything else is this file's.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <string.h>
 
+#include "tf_align_icp_rows.h"
 #include "tf_align_rows.h"
 #include "tf_devpose.h"
 #include "tf_volume.h"
@@ -59,20 +62,6 @@ struct IcpDev {
 };
 struct IcpPoses { float p[12], m[12]; };
 
-struct IcpRowsArgs {
-  AlignRowsCommon c;
-  const float* depth;
-  const float* vm;        // model vertex map, planar
-  const float* nm;        // model normal map, planar
-  const float* pose;      // 24 floats in the state block: the frame's pose, the model's
-  const uint32_t* state;  // null: always run (tf_align_icp_residuals)
-  float max_dist2;
-  size_t plane;
-  float* r;
-  uint32_t* flags;
-  int32_t* assoc;
-  double* part;  // null: no sums
-};
 struct IcpSolveArgs {
   AlignSolveCommon c;
   tf_align_result* out;
@@ -120,32 +109,9 @@ __global__ __launch_bounds__(kAlWaves * 64) void k_icp_rows(IcpRowsArgs a) {
   if (px.in) {
     const size_t o = (size_t)px.Y * a.c.W + (size_t)px.X;
     if (al_point(a.c, px, a.depth[o], a.pose, &p)) {
-      fl = 1u;
-      const float* M = a.pose + 12;
-      const float dx = p.wx - M[3], dy = p.wy - M[7], dz = p.wz - M[11];
-      const float mx = (M[0] * dx + M[4] * dy) + M[8] * dz;
-      const float my = (M[1] * dx + M[5] * dy) + M[9] * dz;
-      const float mz = (M[2] * dx + M[6] * dy) + M[10] * dz;
-      if (mz > a.c.min_depth) {
-        const float uf = floorf(((a.c.fx * mx) / mz + a.c.cxs) + 0.5f), vf = floorf(((a.c.fy * my) / mz + a.c.cys) + 0.5f);
-        // (compared as floats: a NaN or an infinity of a point near the model camera's plane fails here, ahead of the cast)
-        if (uf >= 0.f && uf < (float)a.c.W && vf >= 0.f && vf < (float)a.c.H) {
-          fl |= 2u;
-          const size_t i = (size_t)(int)vf * (size_t)a.c.W + (size_t)(int)uf;  // < W * H
-          as = (int32_t)i;
-          // the six scattered loads of the pixel, all issued ahead of the first use: one batch in flight
-          const float nx = a.nm[i], ny = a.nm[a.plane + i], nz = a.nm[2 * a.plane + i];
-          const float vx = a.vm[i], vy = a.vm[a.plane + i], vz = a.vm[2 * a.plane + i];
-          // (selects, not a branch on the normal: a branch would let the compiler hold the vertex loads back behind it)
-          const bool hit = (nx * nx + ny * ny) + nz * nz > 0.5f;
-          const float ex = p.wx - vx, ey = p.wy - vy, ez = p.wz - vz;
-          const float rr = (nx * ex + ny * ey) + nz * ez;
-          const bool near = (ex * ex + ey * ey) + ez * ez <= a.max_dist2 && fabsf(rr) <= a.c.max_residual;
-          s = hit ? rr : 0.f;
-          gx = hit ? nx : 0.f; gy = hit ? ny : 0.f; gz = hit ? nz : 0.f;
-          fl |= hit ? (near ? 12u : 4u) : 0u;
-        }
-      }
+      const IcpAssoc m = icp_assoc(a, p);  // bits 1 to 3: tf_align_icp_rows.h, the gated kernel's too
+      fl = m.fl; as = m.as;
+      s = m.s; gx = m.gx; gy = m.gy; gz = m.gz;
     }
     if (a.r) a.r[o] = s;
     if (a.flags) a.flags[o] = fl;
@@ -250,10 +216,12 @@ int icp_enqueue(tf_volume* v, const float* d_depth, const float* pose, const flo
     memcpy(P.m, model_pose, sizeof(P.m));
     hipLaunchKernelGGL(k_icp_begin, dim3(1), dim3(64), 0, st, d, P, 0);
   }
+  const bool gated = icp_gate_on(v);  // tf_align_icp_set_gate: the rows launch is tf_align_icp_gate.hip's
   align_walk(v, p.geo, [&](const AlignRowsCommon& c, const AlignSolveCommon& sc) {
     IcpRowsArgs ra = icp_rows_args(c, p, d_depth, d_vertex, d_normal);
     ra.pose = d.pose_f; ra.state = &d.ctl->state; ra.part = d.part;
-    hipLaunchKernelGGL(k_icp_rows, dim3(sc.n_rows), dim3(kAlWaves * 64), 0, st, ra);
+    if (gated) gated_rows_launch(v, ra, sc.n_rows);
+    else hipLaunchKernelGGL(k_icp_rows, dim3(sc.n_rows), dim3(kAlWaves * 64), 0, st, ra);
     hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(256), 0, st, d, IcpSolveArgs{sc, d_result});
   });
   TF_HIP(hipGetLastError());
@@ -281,7 +249,8 @@ int icp_residuals_enqueue(tf_volume* v, const float* d_depth, const float* pose,
   memcpy(P.p, pose, sizeof(P.p));
   memcpy(P.m, model_pose, sizeof(P.m));
   hipLaunchKernelGGL(k_icp_begin, dim3(1), dim3(64), 0, st, d, P, 1);
-  hipLaunchKernelGGL(k_icp_rows, dim3(sc.n_rows), dim3(kAlWaves * 64), 0, st, ra);
+  if (icp_gate_on(v)) gated_rows_launch(v, ra, sc.n_rows);
+  else hipLaunchKernelGGL(k_icp_rows, dim3(sc.n_rows), dim3(kAlWaves * 64), 0, st, ra);
   TF_HIP(hipGetLastError());
   return TF_OK;
 }

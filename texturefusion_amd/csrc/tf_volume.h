@@ -203,11 +203,14 @@ struct AlignBlock {
   size_t cap_tiles = 0;  // 8 x 8 pixel tiles the block has room for
 };
 // The projective ICP's block, and the six planes of the model's vertex and normal maps of the forms that raycast
-// themselves (null until one of those is used)
+// themselves (null until one of those is used); the normal-compatibility gate of tf_align_icp_set_gate (off in a new state,
+// so off again after tf_volume_reset)
 struct AlignIcpState {
   AlignBlock st;
   DevMem maps;
   size_t map_pixels = 0;  // pixels each plane of `maps` has room for
+  bool gate_on = false;
+  tf_align_icp_gate gate{};
 };
 
 // Relocalisation against the cached keyframes (tf_reloc.hip): the configuration, and the index -- one block holding every

@@ -956,6 +956,18 @@ class Chisel {
     tf_check(tf_track_frame(vol, depthImage, depthExtrinsic.data(), icpParams, sdfParams, result), "TrackFrame");
     return result->stage;
   }
+  // The ICP's normal-compatibility gate (tf_align_icp_set_gate): a pair is kept only where the frame's own normal and the
+  // model's agree.  A setting of this map, read by AlignFrameToModelICP, TrackFrame and Relocalise; off until set and off
+  // again after a reset.  gate == nullptr: the library's defaults (20 degrees, 0.1 m).  It launches nothing.
+  void SetIcpGate(const tf_align_icp_gate* gate = nullptr) {
+    tf_align_icp_gate def;
+    if (!gate) {
+      tf_check(tf_align_icp_gate_default(&def), "SetIcpGate");
+      gate = &def;
+    }
+    tf_check(tf_align_icp_set_gate(vol, gate), "SetIcpGate");
+  }
+  void ClearIcpGate() { tf_check(tf_align_icp_set_gate(vol, nullptr), "ClearIcpGate"); }
   // A lost camera found again (tf_relocalise): the cached keyframes that were put into the index (RelocConfigure, then
   // RelocIndexAdd for keyframes that have been through CacheKeyframe-style tf_keyframe_cache and tf_keyframe_set_pose)
   // are ranked by their small images against this frame's, and TrackFrame runs from the best ones' poses until one holds.

@@ -20,6 +20,11 @@ One JSON line.  Needs the GPU; run it under a time limit:
 --counter-run N times nothing: it issues N one-evaluation ICP calls per stride (1, 2, 4), then N one-evaluation
 tf_align_frame_device calls per stride, and ends, for a run under a profiler (kernel durations of k_icp_rows, k_icp_solve
 and k_align_rows).
+
+--gate measures the normal-compatibility gate (tf_align_icp_set_gate, the library's default gate) beside the ungated
+figures, in the same run: us_per_evaluation["icp_gated"][stride], timed right after the ungated figure of the same stride,
+and "gated": what the default call and tf_track_frame did on this view with the gate set.  With --counter-run the N ICP
+calls per stride are issued gated (k_gated_rows in place of k_icp_rows).
 """
 import argparse
 import ctypes as C
@@ -68,7 +73,7 @@ def _wall(fn, warm, reps):
     return (time.perf_counter() - t0) / reps * 1e6
 
 
-def run(hip, orbit, reps, counter_run=0):
+def run(hip, orbit, reps, counter_run=0, gate=False):
     cam = synth.Camera()
     res = np.float32(0.005)
     pool = 1 << 19
@@ -104,8 +109,15 @@ def run(hip, orbit, reps, counter_run=0):
         def frame_call(params):
             return lambda: vol.align_frame_device(d_depth, near, params, d_res)
 
+        def per_evaluation(stride):
+            lv = dict(eps_t=0.0, eps_r=0.0)
+            return round((timed(hip, stream, icp_call(capi.AlignIcpParams(levels=[(stride, 8)], **lv)), 3, reps) -
+                          timed(hip, stream, icp_call(capi.AlignIcpParams(levels=[(stride, 0)], **lv)), 3, reps)) / 8, 2)
+
         raycast()
         if counter_run:
+            if gate:
+                vol.align_icp_set_gate(capi.AlignIcpGate())
             for stride in (1, 2, 4):
                 one = capi.AlignIcpParams(levels=[(stride, 0)])
                 for _ in range(counter_run):
@@ -117,13 +129,16 @@ def run(hip, orbit, reps, counter_run=0):
             vol.sync()
             for p in bufs:
                 hip.h.hipFree(p)
-            return {"counter_run": counter_run, "n_chunks": n_chunks,
+            return {"counter_run": counter_run, "n_chunks": n_chunks, "gate": bool(gate),
                     "launch_order": "icp at strides 1, 2, 4, then tf_align_frame_device at strides 1, 2, 4; N calls each"}
         per_eval = {"icp": {}, "frame": {}}
         for stride in (1, 2, 4):
             lv = dict(eps_t=0.0, eps_r=0.0)
-            per_eval["icp"][str(stride)] = round((timed(hip, stream, icp_call(capi.AlignIcpParams(levels=[(stride, 8)], **lv)), 3, reps) -
-                                                  timed(hip, stream, icp_call(capi.AlignIcpParams(levels=[(stride, 0)], **lv)), 3, reps)) / 8, 2)
+            per_eval["icp"][str(stride)] = per_evaluation(stride)
+            if gate:
+                vol.align_icp_set_gate(capi.AlignIcpGate())
+                per_eval.setdefault("icp_gated", {})[str(stride)] = per_evaluation(stride)
+                vol.align_icp_set_gate(None)
             per_eval["frame"][str(stride)] = round((timed(hip, stream, frame_call(capi.AlignParams(levels=[(stride, 8)], **lv)), 3, reps) -
                                                     timed(hip, stream, frame_call(capi.AlignParams(levels=[(stride, 0)], **lv)), 3, reps)) / 8, 2)
         us_ray = timed(hip, stream, raycast, 3, reps)
@@ -137,9 +152,24 @@ def run(hip, orbit, reps, counter_run=0):
         us_track = _wall(lambda: vol.track_frame(depth, far), 2, reps)
         trk = vol.track_frame(depth, far)
         alone = vol.align_frame(depth, far)
+        gated = None
+        if gate:
+            vol.align_icp_set_gate(capi.AlignIcpGate())
+            us_g = timed(hip, stream, icp_call(icp_default), 3, reps)
+            vol.sync()
+            hip.download(d_res, raw)
+            g = vol.align_result(raw)
+            g_last = vol.align_icp_log()[-1]
+            g_trk = vol.track_frame(depth, far)
+            vol.align_icp_set_gate(None)
+            gated = {"us_icp_default_device": round(us_g, 1), "icp_status": g["status"], "icp_evaluations": g["evaluations"],
+                     "icp_valid": [g["n_valid_first"], g["n_valid_last"], g["n_sampled"]],
+                     "icp_rms": [float(g["rms_first"]), float(g["rms_last"])], "icp_from_truth_m_rad": _distance(g["pose"], truth),
+                     "icp_cond_A_last": float(np.linalg.cond(g_last["A"])), "track_stage": g_trk["stage"],
+                     "track_from_truth_m_rad": _distance(g_trk["pose"], truth)}
         for p in bufs:
             hip.h.hipFree(p)
-        return {"scene": "room", "image": [cam.width, cam.height], "res_m": float(res), "orbit_frames": orbit, "frame": first,
+        return {"gated": gated, "scene": "room", "image": [cam.width, cam.height], "res_m": float(res), "orbit_frames": orbit, "frame": first,
                 "n_chunks": n_chunks, "start": "80 mm / 5 deg", "us_per_evaluation": per_eval,
                 "us_raycast_vertex_normal": round(us_ray, 1), "us_icp_default_device": round(us_icp, 1),
                 "us_icp_default_host_wall": round(us_host, 1), "us_track_frame_wall": round(us_track, 1),
@@ -163,11 +193,12 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--counter-run", type=int, default=0, metavar="N",
                     help="no timing: N one-evaluation calls per stride of the ICP, then of tf_align_frame_device, for a profiler")
+    ap.add_argument("--gate", action="store_true", help="also measure with the default normal-compatibility gate set")
     args = ap.parse_args()
     hip = Hip()
     if capi.lib().tf_device_count() <= 0:
         sys.exit("no HIP device: this tool measures the MI355X and has no CPU path")
-    print(json.dumps(run(hip, args.orbit, args.reps, args.counter_run)), flush=True)
+    print(json.dumps(run(hip, args.orbit, args.reps, args.counter_run, args.gate)), flush=True)
 
 
 if __name__ == "__main__":
