@@ -761,6 +761,7 @@ TF_API int tf_align_unit_group(tf_volume* v, tf_unit_group* group, int rigid, co
  * levels is the caller's choice, through a second call.  A call is 1 + 2 launches per evaluation, all enqueued up front.
  * Read-only; its state and log are its own: tf_align_log, tf_align_color_log and tf_align_group_log keep their meaning.
  * A normal-compatibility gate from the frame's own normals is a setting of the handle: the section below tf_track_frame.
+ * So is a depth pyramid for the coarse levels (the section after that one); without it a level samples by stride alone.
  * Not here: a photometric row, a group form, multi-rank. */
 typedef struct tf_align_icp_params {
   tf_align_params geo;     /* levels, depth range, huber, damping, eps, min_valid; max_residual gates |r| */
@@ -825,7 +826,7 @@ TF_API int tf_track_frame(tf_volume* v, const float* depth, const float pose[12]
  * untouched.  All f32, the order of operations fixed in tf_align_icp_gate.hip and restated in tests/align_icp_gate_ref.py.
  * The normal is formed in the rows launch, every evaluation: no normal map, no further launch.
  * The defaults are KinectFusion's 20 degrees and a round number; neither is tuned on recorded data.
- * Not here: a per-call form of the gate, a gate for tf_align_frame's SDF stage, a depth pyramid. */
+ * Not here: a per-call form of the gate, a gate for tf_align_frame's SDF stage.  (A depth pyramid: the section below.) */
 typedef struct tf_align_icp_gate {
   float min_normal_cos;   /* in [0, 1] */
   float max_depth_jump;   /* metres, > 0; +inf allowed: no discontinuity test */
@@ -845,6 +846,57 @@ TF_API int tf_align_icp_frame_normals_device(tf_volume* v, const float* d_depth,
                                              const tf_align_icp_gate* gate, float* d_normal3);
 TF_API int tf_align_icp_frame_normals(tf_volume* v, const float* depth, const tf_align_icp_params* params,
                                       const tf_align_icp_gate* gate, float* normal3);
+
+/* ---- the projective ICP on a depth pyramid (tf_align_icp_pyramid.hip) ---------------------------
+ * Without it a level of stride s reads every s-th pixel of the full image against a model map of the full camera: the
+ * coarse levels see the sensor's noise undiminished.  With it a level of stride s = 2^l is an image of its own, W >> l x
+ * H >> l pixels, every pixel the mean of a 2 x 2 block of the level below, with a camera of its own and model maps raycast
+ * for that camera: KinectFusion's form.  A setting of the handle, off in a new handle and off again after
+ * tf_volume_reset.  The calls that run the projective ICP and raycast the model themselves read it: tf_align_frame_icp,
+ * tf_align_icp_residuals where both maps are NULL, tf_track_frame, tf_track_frame_device, tf_track_integrate_device,
+ * tf_track_texture_device, tf_relocalise.  The forms that take the caller's maps do not (those maps are of the full
+ * camera): tf_align_frame_icp_device, tf_align_icp_residuals(_device) with maps.  tf_align_frame keeps its strides.
+ * Level 0 is the caller's image.  Pixel (X, Y) of level l from a = (2X, 2Y), b = (2X + 1, 2Y), c = (2X, 2Y + 1),
+ * d = (2X + 1, 2Y + 1) of level l - 1: valid iff all four are finite and > 0 and max - min of the four <= max_depth_jump
+ * (one f32 subtraction); the value is ((a + b) + (c + d)) * 0.25f, every operation rounded on its own, else 0.  A mean
+ * over whichever readings are valid would move the sample off the block's centre ray, so there is none.
+ * The level camera, from the int-truncated intrinsics (fx, fy, cx, cy) of the image's camera and s = 2^l: fx / s, fy / s,
+ * (cx + 1) / s - 1, (cy + 1) / s - 1 (the centre of the block 2X, 2X + 1 is 2X + 0.5, and pixel x has its centre at x with
+ * the principal point at cx + 0.5); not truncated again.
+ * A call with the setting on: every geo.stride[l], l < n_levels, must be 1, 2, 4 or 8 and divide W and H, otherwise
+ * TF_ERR_INVALID, nothing launched, outputs untouched.  One launch builds every level image the schedule needs; one
+ * raycast launch per distinct stride renders that level's maps (stride 1: the raycast of a call with the setting off);
+ * then 1 + 2 launches per evaluation as ever, all enqueued up front, nothing read back.  A level evaluates every pixel of
+ * its image against its maps with the rows kernel as it is (with tf_align_icp_set_gate on: the gated one, whose
+ * neighbours are then the level image's adjacent pixels).  Flag bits, Huber weight, sums and their order, the solve,
+ * stops, statuses, the closing evaluation, result and log are untouched; n_sampled is the level's pixel count and a
+ * record's stride still names the level.  tf_align_icp_residuals writes level pixel (X, Y) at (sX, sY) of its full-size
+ * maps, s = stride[0]; assoc = v * (W / s) + u in the level's model map; every other pixel gets 0, 0, -1.  With the
+ * setting off every call is what it was, bit for bit.  tests/align_icp_pyramid_ref.py restates it.
+ * The default jump is the gate's, a round number not tuned on recorded data.
+ * Not here: a pyramid for tf_align_frame and tf_align_frame_color, for tf_align_group, for caller-supplied maps; image
+ * sizes that 2^l does not divide; a blurred (Gaussian) pyramid; re-rendering the maps between levels. */
+typedef struct tf_align_icp_pyramid {
+  float max_depth_jump;   /* metres, > 0; +inf allowed: no spread test */
+} tf_align_icp_pyramid;
+TF_API int tf_align_icp_pyramid_default(tf_align_icp_pyramid* out);   /* 0.1f */
+/* p == NULL: off.  TF_ERR_INVALID, with nothing changed, for a NaN or a jump that is not > 0.  The setter and the getter
+ * launch nothing and wait for nothing; calls already enqueued keep the setting they were enqueued with.  *on = 0 / 1;
+ * *out = the setting, or the defaults where there is none. */
+TF_API int tf_align_icp_set_pyramid(tf_volume* v, const tf_align_icp_pyramid* p);
+TF_API int tf_align_icp_get_pyramid(tf_volume* v, tf_align_icp_pyramid* out, int32_t* on);
+/* cam4 = (fx, fy, cx, cy) and the size of level `level` (0..3) of the aligners' camera (tf_raycast_camera's where set, else
+ * tf_set_camera's).  TF_ERR_INVALID for a null pointer, no camera, a level outside 0..3 or one the size does not allow. */
+TF_API int tf_align_icp_pyramid_camera(tf_volume* v, int32_t level, float cam4[4], int32_t* width, int32_t* height);
+/* Levels 1..n_levels (n_levels 1..3) of a depth image by *p (not the handle's setting): d_levels[l - 1] receives
+ * f32[H >> l][W >> l]; entries past n_levels are not read.  One launch, read-only on the handle.  _device: asynchronous
+ * on the handle's stream; the host form stages through the scratch pool and waits once.  TF_ERR_INVALID (nothing
+ * launched, nothing written) for a null pointer, no camera, n_levels outside 1..3, a size 2^n_levels does not divide, or a
+ * setting tf_align_icp_set_pyramid rejects. */
+TF_API int tf_align_icp_pyramid_depth_device(tf_volume* v, const float* d_depth, int32_t n_levels,
+                                             const tf_align_icp_pyramid* p, float* const d_levels[3]);
+TF_API int tf_align_icp_pyramid_depth(tf_volume* v, const float* depth, int32_t n_levels, const tf_align_icp_pyramid* p,
+                                      float* const levels[3]);
 
 /* ---- tracking and integrating with the pose kept on the device (tf_devpose.hip) ------------------
  * KinectFusion's loop on the stream: track frame f against the model, decide whether the result is good enough, integrate

@@ -62,6 +62,8 @@ SYMBOLS = (
     "tf_align_icp_residuals", "tf_align_icp_residuals_device", "tf_track_frame",
     "tf_align_icp_gate_default", "tf_align_icp_set_gate", "tf_align_icp_get_gate", "tf_align_icp_frame_normals",
     "tf_align_icp_frame_normals_device",
+    "tf_align_icp_pyramid_default", "tf_align_icp_set_pyramid", "tf_align_icp_get_pyramid", "tf_align_icp_pyramid_camera",
+    "tf_align_icp_pyramid_depth", "tf_align_icp_pyramid_depth_device",
     "tf_track_accept_default", "tf_track_frame_device", "tf_integrate_frame_posed_device", "tf_track_integrate_device",
     "tf_pose_consts_download", "tf_integrate_frame_textured_posed_device", "tf_track_texture_device",
     "tf_pose_inverse_download",
@@ -215,6 +217,10 @@ class AlignIcpGateC(C.Structure):
     _fields_ = [("min_normal_cos", C.c_float), ("max_depth_jump", C.c_float)]
 
 
+class AlignIcpPyramidC(C.Structure):
+    _fields_ = [("max_depth_jump", C.c_float)]
+
+
 class TrackResult(C.Structure):
     _fields_ = [("icp", AlignResult), ("sdf", AlignResult), ("stage", C.c_int32), ("pose", C.c_float * 12)]
 
@@ -298,6 +304,19 @@ def AlignIcpGate(**kw):
         if k not in ("min_normal_cos", "max_depth_jump"):
             raise TypeError("tf_align_icp_gate has no field %r" % k)
         setattr(g, k, float(val))
+    return g
+
+
+def AlignIcpPyramid(**kw):
+    """tf_align_icp_pyramid: the library's default (tf_align_icp_pyramid_default) with the field replaced by keyword"""
+    g = AlignIcpPyramidC()
+    rc = lib().tf_align_icp_pyramid_default(C.byref(g))
+    if rc != TF_OK:
+        raise TFError(rc, lib().tf_last_error().decode())
+    for k, val in kw.items():
+        if k != "max_depth_jump":
+            raise TypeError("tf_align_icp_pyramid has no field %r" % k)
+        g.max_depth_jump = float(val)
     return g
 
 
@@ -543,6 +562,13 @@ def lib():
     L.tf_align_icp_get_gate.argtypes = [vp, agp, i32p]
     L.tf_align_icp_frame_normals.argtypes = [vp, fp, aip, agp, fp]
     L.tf_align_icp_frame_normals_device.argtypes = [vp, vp, aip, agp, vp]
+    ayp = C.POINTER(AlignIcpPyramidC)
+    L.tf_align_icp_pyramid_default.argtypes = [ayp]
+    L.tf_align_icp_set_pyramid.argtypes = [vp, ayp]
+    L.tf_align_icp_get_pyramid.argtypes = [vp, ayp, i32p]
+    L.tf_align_icp_pyramid_camera.argtypes = [vp, C.c_int32, fp, i32p, i32p]
+    L.tf_align_icp_pyramid_depth.argtypes = [vp, fp, C.c_int32, ayp, C.POINTER(fp)]
+    L.tf_align_icp_pyramid_depth_device.argtypes = [vp, vp, C.c_int32, ayp, C.POINTER(vp)]
     tap = C.POINTER(TrackAcceptC)
     L.tf_track_accept_default.argtypes = [tap]
     L.tf_track_frame_device.argtypes = [vp, vp, vp, aip, app, tap, vp, vp]
@@ -1355,6 +1381,41 @@ class Volume:
     def align_icp_frame_normals_device(self, d_depth, params, gate, d_normal3):
         self._ck(self.L.tf_align_icp_frame_normals_device(self.h, d_depth or None, None if params is None else C.byref(params),
                                                           None if gate is None else C.byref(gate), d_normal3 or None))
+
+    # -- the ICP's depth pyramid (tf_align_icp_pyramid.hip): a setting of the handle, off until set
+    def align_icp_set_pyramid(self, pyramid=None):
+        """Run the coarse levels of every projective ICP of this handle that raycasts the model itself on block-averaged
+        level images with their own cameras and maps (an AlignIcpPyramid); None: off."""
+        self._ck(self.L.tf_align_icp_set_pyramid(self.h, None if pyramid is None else C.byref(pyramid)))
+
+    def align_icp_get_pyramid(self):
+        """-> (on, AlignIcpPyramidC: the setting, or the defaults where there is none)"""
+        g, on = AlignIcpPyramidC(), C.c_int32(0)
+        self._ck(self.L.tf_align_icp_get_pyramid(self.h, C.byref(g), C.byref(on)))
+        return bool(on.value), g
+
+    def align_icp_pyramid_camera(self, level):
+        """-> ((fx, fy, cx, cy) f32, width, height) of pyramid level 0..3 of the aligners' camera"""
+        cam, w, h = np.zeros(4, np.float32), C.c_int32(0), C.c_int32(0)
+        self._ck(self.L.tf_align_icp_pyramid_camera(self.h, int(level), _p(cam, C.c_float), C.byref(w), C.byref(h)))
+        return cam, w.value, h.value
+
+    def align_icp_pyramid_depth(self, depth, n_levels, pyramid=None):
+        """Levels 1..n_levels of the depth image [H, W] -> a list of [H >> l, W >> l] f32; pyramid: an AlignIcpPyramid
+        (None: the defaults), not the handle's setting."""
+        d, H, W = self._align_depth(depth)
+        pyramid = pyramid or AlignIcpPyramid()
+        n = int(n_levels)
+        outs = [np.zeros((H >> l, W >> l), np.float32) for l in range(1, min(max(n, 0), 3) + 1)]
+        ptrs = (C.POINTER(C.c_float) * 3)(*[_p(o, C.c_float) for o in outs])
+        self._ck(self.L.tf_align_icp_pyramid_depth(self.h, _p(d, C.c_float), n, C.byref(pyramid), ptrs))
+        return outs
+
+    def align_icp_pyramid_depth_device(self, d_depth, n_levels, pyramid, d_levels):
+        """Asynchronous on the handle's stream: d_levels = up to three device pointers, level l to d_levels[l - 1]"""
+        ptrs = (C.c_void_p * 3)(*[p or None for p in list(d_levels)[:3]])
+        self._ck(self.L.tf_align_icp_pyramid_depth_device(self.h, d_depth or None, int(n_levels),
+                                                          None if pyramid is None else C.byref(pyramid), ptrs))
 
     def track_frame(self, depth, pose, icp_params=None, sdf_params=None):
         """The coarse-to-fine tracker: align_frame_icp with the model raycast at pose, then align_frame from its pose ->

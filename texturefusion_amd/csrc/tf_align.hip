@@ -193,10 +193,12 @@ int align_ensure(tf_volume* v, AlignBlock& b, size_t (*bytes_of)(size_t tiles), 
   return TF_OK;
 }
 
-void align_level(const tf_volume* v, const tf_align_params& p, int level, AlignRowsCommon* rc, AlignSolveCommon* sc) {
+namespace {
+// a level's blocks: the rows walk an image of camera c at rows_stride, the solve's block names block_stride
+void level_fill(const AlignCam& c, int rows_stride, int block_stride, const tf_align_params& p, int level, AlignRowsCommon* rc,
+                AlignSolveCommon* sc) {
   const bool closing = level == p.n_levels;
-  const int s = p.stride[closing ? p.n_levels - 1 : level];
-  const AlignCam c = align_cam(v);
+  const int s = rows_stride;
   AlignRowsCommon r{};
   r.fx = c.fx; r.fy = c.fy; r.cxs = c.cx + 0.5f; r.cys = c.cy + 0.5f;
   r.W = c.W; r.H = c.H; r.stride = s; r.level = level;
@@ -205,19 +207,32 @@ void align_level(const tf_volume* v, const tf_align_params& p, int level, AlignR
   const uint32_t n_tiles = (uint32_t)r.tiles_x * (uint32_t)((ny + 7) / 8);  // <= the tiles at stride 1
   r.min_depth = p.min_depth; r.max_depth = p.max_depth; r.max_residual = p.max_residual; r.huber = p.huber;
   AlignSolveCommon q{};
-  q.level = level; q.log_level = closing ? p.n_levels - 1 : level; q.stride = s; q.closing = closing;
+  q.level = level; q.log_level = closing ? p.n_levels - 1 : level; q.stride = block_stride; q.closing = closing;
   q.last_level = level == p.n_levels - 1; q.n_rows = (n_tiles + kAlWaves - 1) / kAlWaves;
   q.damping = p.damping; q.eps_t = p.eps_t; q.eps_r = p.eps_r; q.min_valid = p.min_valid;
   *rc = r;
   *sc = q;
 }
+int level_stride(const tf_align_params& p, int level) { return p.stride[level == p.n_levels ? p.n_levels - 1 : level]; }
+}  // namespace
+
+void align_level(const tf_volume* v, const tf_align_params& p, int level, AlignRowsCommon* rc, AlignSolveCommon* sc) {
+  const int s = level_stride(p, level);
+  level_fill(align_cam(v), s, s, p, level, rc, sc);
+}
+
+void align_level_image(const AlignCam& cam, const tf_align_params& p, int level, AlignRowsCommon* rc, AlignSolveCommon* sc) {
+  level_fill(cam, 1, level_stride(p, level), p, level, rc, sc);
+}
 
 void align_walk(const tf_volume* v, const tf_align_params& p,
-                const std::function<void(const AlignRowsCommon&, const AlignSolveCommon&)>& evaluate) {
+                const std::function<void(const AlignRowsCommon&, const AlignSolveCommon&)>& evaluate,
+                const AlignCam* level_cams) {
   for (int l = 0; l <= p.n_levels; ++l) {
     AlignRowsCommon rc;
     AlignSolveCommon sc;
-    align_level(v, p, l, &rc, &sc);
+    if (level_cams) align_level_image(level_cams[__builtin_ctz((unsigned)level_stride(p, l))], p, l, &rc, &sc);
+    else align_level(v, p, l, &rc, &sc);
     const int n = sc.closing ? 1 : p.iters[l];
     for (int it = 0; it < n; ++it) evaluate(rc, sc);
   }

@@ -37,11 +37,15 @@
 // model pose and the maps do not change during a call.
 // With a gate set on the handle (tf_align_icp_set_gate) the rows launch is k_gated_rows of tf_align_icp_gate.hip: the same
 // association (icp_assoc, tf_align_icp_rows.h) and flag bits 4 and 5 from the frame's own normal; everything else is this file's.
+// With a depth pyramid set on the handle (tf_align_icp_set_pyramid) the forms that raycast the model themselves hand the
+// rows launch of a level of stride 2^k the level's image, camera and maps (tf_align_icp_pyramid.hip builds the images, this
+// file raycasts a map pair per level in the schedule), at stride 1; the kernels and the solve are the same.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <string.h>
 
+#include "tf_align_icp_pyramid.h"
 #include "tf_align_icp_rows.h"
 #include "tf_align_rows.h"
 #include "tf_devpose.h"
@@ -186,6 +190,7 @@ int icp_check(tf_volume* v, const float* depth, const float* pose, const float* 
   }
   if (model_pose && !finite_all(model_pose, 12)) { set_error("model pose is not finite"); return TF_ERR_INVALID; }
   if (with_ray && !ray_params_ok(p)) return TF_ERR_INVALID;
+  if (with_ray && icp_pyramid_on(v)) return icp_pyramid_check(v, p->geo, p->geo.n_levels);  // the forms that raycast themselves
   return TF_OK;
 }
 
@@ -200,10 +205,11 @@ IcpRowsArgs icp_rows_args(const AlignRowsCommon& rc, const tf_align_icp_params& 
 }
 
 // every launch of one alignment: begin, then (rows, solve) per step and once more to close.  d_start != null: frame pose
-// and model pose are that cell's, read on the device (pose and model_pose are not read).
+// and model pose are that cell's, read on the device (pose and model_pose are not read).  lv != null: the pyramid is on,
+// and a level of stride 2^k evaluates lv's image, camera and maps of level k (d_depth, d_vertex, d_normal are not read).
 int icp_enqueue(tf_volume* v, const float* d_depth, const float* pose, const float* d_vertex, const float* d_normal,
                 const float* model_pose, const tf_align_icp_params& p, tf_align_result* d_result,
-                const tf_device_pose* d_start = nullptr) {
+                const tf_device_pose* d_start = nullptr, const IcpLevels* lv = nullptr) {
   IcpDev d;
   int rc = icp_dev(v, &d);
   if (rc) return rc;
@@ -218,28 +224,34 @@ int icp_enqueue(tf_volume* v, const float* d_depth, const float* pose, const flo
   }
   const bool gated = icp_gate_on(v);  // tf_align_icp_set_gate: the rows launch is tf_align_icp_gate.hip's
   align_walk(v, p.geo, [&](const AlignRowsCommon& c, const AlignSolveCommon& sc) {
-    IcpRowsArgs ra = icp_rows_args(c, p, d_depth, d_vertex, d_normal);
+    const int k = lv ? __builtin_ctz((unsigned)sc.stride) : 0;
+    IcpRowsArgs ra = lv ? icp_rows_args(c, p, lv->depth[k], lv->vm[k], lv->nm[k]) : icp_rows_args(c, p, d_depth, d_vertex, d_normal);
     ra.pose = d.pose_f; ra.state = &d.ctl->state; ra.part = d.part;
     if (gated) gated_rows_launch(v, ra, sc.n_rows);
     else hipLaunchKernelGGL(k_icp_rows, dim3(sc.n_rows), dim3(kAlWaves * 64), 0, st, ra);
     hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(256), 0, st, d, IcpSolveArgs{sc, d_result});
-  });
+  }, lv ? lv->cam : nullptr);
   TF_HIP(hipGetLastError());
   return TF_OK;
 }
 
 int icp_residuals_enqueue(tf_volume* v, const float* d_depth, const float* pose, const float* d_vertex,
                           const float* d_normal, const float* model_pose, const tf_align_icp_params& p, float* d_r,
-                          uint32_t* d_flags, int32_t* d_assoc) {
+                          uint32_t* d_flags, int32_t* d_assoc, const IcpLevels* lv = nullptr) {
   IcpDev d;
   int rc = icp_dev(v, &d);
   if (rc) return rc;
   hipStream_t st = v->stream;
   AlignRowsCommon c;
   AlignSolveCommon sc;
-  align_level(v, p.geo, 0, &c, &sc);
-  IcpRowsArgs ra = icp_rows_args(c, p, d_depth, d_vertex, d_normal);
+  // lv != null: the pyramid is on, and the evaluation is of level k = log2(stride[0]) -- its image, camera and maps; the
+  // rows launch writes level-sized maps of the handle's, which are spread over the caller's behind it
+  const int k = lv ? __builtin_ctz((unsigned)p.geo.stride[0]) : 0;
+  if (lv) align_level_image(lv->cam[k], p.geo, 0, &c, &sc);
+  else align_level(v, p.geo, 0, &c, &sc);
+  IcpRowsArgs ra = lv ? icp_rows_args(c, p, lv->depth[k], lv->vm[k], lv->nm[k]) : icp_rows_args(c, p, d_depth, d_vertex, d_normal);
   ra.pose = d.pose_r; ra.r = d_r; ra.flags = d_flags; ra.assoc = d_assoc;
+  if (k > 0 && (rc = icp_pyramid_residual_maps(v, k, &ra.r, &ra.flags, &ra.assoc))) return rc;
   if (c.stride > 1) {  // pixels that are not sampled
     if (d_r) TF_HIP(hipMemsetAsync(d_r, 0, 4 * ra.plane, st));
     if (d_flags) TF_HIP(hipMemsetAsync(d_flags, 0, 4 * ra.plane, st));
@@ -252,7 +264,7 @@ int icp_residuals_enqueue(tf_volume* v, const float* d_depth, const float* pose,
   if (icp_gate_on(v)) gated_rows_launch(v, ra, sc.n_rows);
   else hipLaunchKernelGGL(k_icp_rows, dim3(sc.n_rows), dim3(kAlWaves * 64), 0, st, ra);
   TF_HIP(hipGetLastError());
-  return TF_OK;
+  return k > 0 ? icp_pyramid_spread(v, k, d_r, d_flags, d_assoc) : TF_OK;
 }
 
 // the model raycast at model_pose into the state block's own maps: tf_raycast_device's launch
@@ -260,6 +272,22 @@ int icp_raycast(tf_volume* v, const float* model_pose, const tf_align_icp_params
   int rc = icp_ensure_maps(v, d_vertex, d_normal);
   if (rc) return rc;
   return tf_raycast_device(v, model_pose, p.ray_near, p.ray_far, p.ray_max_steps, nullptr, *d_normal, nullptr, *d_vertex);
+}
+
+// What a call that raycasts the model itself evaluates with the pyramid on: the level images of the strides of the first
+// n_levels (one launch), then a raycast per such stride at that level's camera -- at model_pose, or at the pose in
+// *d_cell -- level 0's being the raycast of a call with the pyramid off, into the same maps.
+int icp_model_levels(tf_volume* v, const float* d_depth, const float* model_pose, const tf_device_pose* d_cell,
+                     const tf_align_icp_params& p, int n_levels, IcpLevels* lv) {
+  int rc = icp_pyramid_enqueue(v, d_depth, p.geo, n_levels, d_cell, lv);
+  for (int k = 0; k < 4 && !rc; ++k) {
+    if (!((lv->used >> k) & 1u)) continue;
+    if (k > 0) rc = raycast_level(v, model_pose, d_cell, p.ray_near, p.ray_far, p.ray_max_steps, lv->cam[k], lv->nm[k], lv->vm[k]);
+    else if (!d_cell) rc = icp_raycast(v, model_pose, p, &lv->vm[0], &lv->nm[0]);
+    else if (!(rc = icp_ensure_maps(v, &lv->vm[0], &lv->nm[0])))
+      rc = raycast_posed(v, d_cell, p.ray_near, p.ray_far, p.ray_max_steps, lv->nm[0], lv->vm[0]);
+  }
+  return rc;
 }
 
 }  // namespace
@@ -278,9 +306,16 @@ int track_check(tf_volume* v, const float* depth, const float* pose, const tf_al
 int track_icp_posed(tf_volume* v, const float* d_depth, const tf_device_pose* d_start, const tf_align_icp_params& p,
                     tf_align_result* d_result, const int32_t** d_status) {
   float *d_v = nullptr, *d_n = nullptr;
-  int rc = icp_ensure_maps(v, &d_v, &d_n);
-  if (rc || (rc = raycast_posed(v, d_start, p.ray_near, p.ray_far, p.ray_max_steps, d_n, d_v))) return rc;
-  if ((rc = icp_enqueue(v, d_depth, nullptr, d_v, d_n, nullptr, p, d_result, d_start))) return rc;
+  int rc;
+  if (icp_pyramid_on(v)) {
+    IcpLevels lv;
+    if ((rc = icp_model_levels(v, d_depth, nullptr, d_start, p, p.geo.n_levels, &lv))) return rc;
+    if ((rc = icp_enqueue(v, d_depth, nullptr, nullptr, nullptr, nullptr, p, d_result, d_start, &lv))) return rc;
+  } else {
+    rc = icp_ensure_maps(v, &d_v, &d_n);
+    if (rc || (rc = raycast_posed(v, d_start, p.ray_near, p.ray_far, p.ray_max_steps, d_n, d_v))) return rc;
+    if ((rc = icp_enqueue(v, d_depth, nullptr, d_v, d_n, nullptr, p, d_result, d_start))) return rc;
+  }
   IcpDev d;
   if ((rc = icp_dev(v, &d))) return rc;
   *d_status = &d.ctl->status;
@@ -330,9 +365,16 @@ int tf_align_frame_icp(tf_volume* v, const float* depth, const float pose[12], c
   const size_t o_d = L.take(4 * P), o_r = L.take(sizeof(tf_align_result));
   Stage sg;
   if ((rc = stage_begin(v, v->scratch, L.size, L.size, &sg)) || (rc = stage_in(v, sg, o_d, depth, 4 * P))) return rc;
-  float *d_v = nullptr, *d_n = nullptr;
-  if ((rc = icp_raycast(v, mp, *params, &d_v, &d_n))) return rc;
-  if ((rc = icp_enqueue(v, sg.dp<const float>(o_d), pose, d_v, d_n, mp, *params, sg.dp<tf_align_result>(o_r)))) return rc;
+  if (icp_pyramid_on(v)) {
+    IcpLevels lv;
+    if ((rc = icp_model_levels(v, sg.dp<const float>(o_d), mp, nullptr, *params, params->geo.n_levels, &lv))) return rc;
+    rc = icp_enqueue(v, nullptr, pose, nullptr, nullptr, mp, *params, sg.dp<tf_align_result>(o_r), nullptr, &lv);
+  } else {
+    float *d_v = nullptr, *d_n = nullptr;
+    if ((rc = icp_raycast(v, mp, *params, &d_v, &d_n))) return rc;
+    rc = icp_enqueue(v, sg.dp<const float>(o_d), pose, d_v, d_n, mp, *params, sg.dp<tf_align_result>(o_r));
+  }
+  if (rc) return rc;
   return stage_out(v, sg, o_r, sizeof(tf_align_result), result);
 }
 
@@ -371,14 +413,18 @@ int tf_align_icp_residuals(tf_volume* v, const float* depth, const float pose[12
   Stage sg;
   if ((rc = stage_begin(v, v->scratch, L.size, L.size, &sg)) || (rc = stage_in(v, sg, o_d, depth, 4 * P))) return rc;
   float *d_v = nullptr, *d_n = nullptr;
-  if (own) {
+  IcpLevels lv;
+  const bool pyr = own && icp_pyramid_on(v);
+  if (pyr) {
+    if ((rc = icp_model_levels(v, sg.dp<const float>(o_d), mp, nullptr, *params, 1, &lv))) return rc;
+  } else if (own) {
     if ((rc = icp_raycast(v, mp, *params, &d_v, &d_n))) return rc;
   } else {
     if ((rc = stage_in(v, sg, o_v, model_vertex, 12 * P)) || (rc = stage_in(v, sg, o_n, model_normal, 12 * P))) return rc;
     d_v = sg.dp<float>(o_v); d_n = sg.dp<float>(o_n);
   }
   rc = icp_residuals_enqueue(v, sg.dp<const float>(o_d), pose, d_v, d_n, mp, *params, r ? sg.dp<float>(o_r) : nullptr,
-                             flags ? sg.dp<uint32_t>(o_f) : nullptr, assoc ? sg.dp<int32_t>(o_a) : nullptr);
+                             flags ? sg.dp<uint32_t>(o_f) : nullptr, assoc ? sg.dp<int32_t>(o_a) : nullptr, pyr ? &lv : nullptr);
   if (rc) return rc;
   if ((rc = stage_out(v, sg, o_r, L.size - o_r, nullptr))) return rc;
   if (r) memcpy(r, sg.h + o_r, 4 * P);

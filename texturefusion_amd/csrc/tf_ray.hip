@@ -517,6 +517,15 @@ int tf::raycast_posed(tf_volume* v, const tf_device_pose* d_cell, float near_pla
   return rc ? rc : ray_launch(v, eye, near_plane, far_plane, max_steps, cam, nullptr, d_normal, nullptr, d_vertex, d_cell);
 }
 
+// the vertex and normal maps of a camera that is neither the handle's nor tf_raycast_camera's -- a level of the projective
+// ICP's depth pyramid -- at `pose`, or at the pose in *d_cell where that is given; the caller has checked the parameters
+int tf::raycast_level(tf_volume* v, const float* pose, const tf_device_pose* d_cell, float near_plane, float far_plane,
+                      int32_t max_steps, const AlignCam& cam, float* d_normal, float* d_vertex) {
+  const float eye[12] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+  const RayCam rc{cam.fx, cam.fy, cam.cx, cam.cy, cam.W, cam.H};
+  return ray_launch(v, d_cell ? eye : pose, near_plane, far_plane, max_steps, rc, nullptr, d_normal, nullptr, d_vertex, d_cell);
+}
+
 extern "C" {
 
 int tf_query_points_device(tf_volume* v, const float* d_xyz, int64_t n, uint32_t want_mask, float* d_sdf, float* d_weight,

@@ -204,13 +204,18 @@ struct AlignBlock {
 };
 // The projective ICP's block, and the six planes of the model's vertex and normal maps of the forms that raycast
 // themselves (null until one of those is used); the normal-compatibility gate of tf_align_icp_set_gate (off in a new state,
-// so off again after tf_volume_reset)
+// so off again after tf_volume_reset); the depth pyramid of tf_align_icp_set_pyramid (off in a new state too) with what a
+// call with it on needs beside `maps`: the images of levels 1 to 3, their model maps, and the level-sized maps
+// tf_align_icp_residuals spreads over the full image -- each grown on demand (tf_align_icp_pyramid.hip)
 struct AlignIcpState {
   AlignBlock st;
   DevMem maps;
   size_t map_pixels = 0;  // pixels each plane of `maps` has room for
   bool gate_on = false;
   tf_align_icp_gate gate{};
+  bool pyr_on = false;
+  tf_align_icp_pyramid pyr{};
+  DevMem pyr_img, pyr_maps, pyr_res;  // fitted buffers (tf_mem.h)
 };
 
 // Relocalisation against the cached keyframes (tf_reloc.hip): the configuration, and the index -- one block holding every
@@ -464,9 +469,15 @@ int align_ensure(tf_volume* v, AlignBlock& b, size_t (*bytes_of)(size_t tiles), 
 struct AlignRowsCommon;
 struct AlignSolveCommon;
 void align_level(const tf_volume* v, const tf_align_params& p, int level, AlignRowsCommon* rc, AlignSolveCommon* sc);
-// The schedule of a call: evaluate(rc, sc) for iters[l] evaluations of every level l, then once to close.
+// Its twin for a level that is an image of its own (the projective ICP's depth pyramid): cam is that image's camera, every
+// pixel of it is a row (the rows' stride is 1, the grid is the image's), and the solve's block keeps the level's stride,
+// so that a log record's stride still names the level's block.
+void align_level_image(const AlignCam& cam, const tf_align_params& p, int level, AlignRowsCommon* rc, AlignSolveCommon* sc);
+// The schedule of a call: evaluate(rc, sc) for iters[l] evaluations of every level l, then once to close.  level_cams !=
+// null: a level of stride 2^k is the image of camera level_cams[k] (align_level_image).
 void align_walk(const tf_volume* v, const tf_align_params& p,
-                const std::function<void(const AlignRowsCommon&, const AlignSolveCommon&)>& evaluate);
+                const std::function<void(const AlignRowsCommon&, const AlignSolveCommon&)>& evaluate,
+                const AlignCam* level_cams = nullptr);
 // tf_*_log: waits for the stream, reads the control words at d_ctl (null: no call yet, no records) and copies
 // min(n_eval, cap) records of rec_bytes from d_log; *n = the records there are.
 int align_log(tf_volume* v, const void* d_ctl, const void* d_log, size_t rec_bytes, void* out, int64_t cap, int64_t* n);
@@ -485,6 +496,9 @@ int raycast_posed(tf_volume* v, const tf_device_pose* d_cell, float near_plane, 
                   float* d_normal, float* d_vertex);
 int track_icp_posed(tf_volume* v, const float* d_depth, const tf_device_pose* d_start, const tf_align_icp_params& p,
                     tf_align_result* d_result, const int32_t** d_status);
+// raycast_level (tf_ray.hip): the vertex and normal maps of a pyramid level's camera, at `pose` or at the pose in *d_cell.
+int raycast_level(tf_volume* v, const float* pose, const tf_device_pose* d_cell, float near_plane, float far_plane,
+                  int32_t max_steps, const AlignCam& cam, float* d_normal, float* d_vertex);
 int track_sdf_posed(tf_volume* v, const float* d_depth, const int32_t* d_prev_status, const float* d_prev_pose,
                     const tf_align_params& p, tf_align_result* d_result);
 void discard_primed(tf_volume* v);       // the selections made ahead by a streaming call are dropped (tf_capi.cpp)

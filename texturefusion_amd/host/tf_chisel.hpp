@@ -968,6 +968,34 @@ class Chisel {
     tf_check(tf_align_icp_set_gate(vol, gate), "SetIcpGate");
   }
   void ClearIcpGate() { tf_check(tf_align_icp_set_gate(vol, nullptr), "ClearIcpGate"); }
+  // The ICP's depth pyramid (tf_align_icp_set_pyramid): a level of stride 2^l runs on an image of 2 x 2 block means with its
+  // own camera and its own raycast model maps, so that the coarse levels average the sensor's noise.  A setting of this map,
+  // read by AlignFrameToModelICP, TrackFrame and Relocalise (not by the forms that take the caller's maps); off until set and
+  // off again after a reset.  pyramid == nullptr: the library's default (0.1 m).  Strides must then be 1, 2, 4 or 8 and
+  // divide the image.  It launches nothing.
+  void SetIcpPyramid(const tf_align_icp_pyramid* pyramid = nullptr) {
+    tf_align_icp_pyramid def;
+    if (!pyramid) {
+      tf_check(tf_align_icp_pyramid_default(&def), "SetIcpPyramid");
+      pyramid = &def;
+    }
+    tf_check(tf_align_icp_set_pyramid(vol, pyramid), "SetIcpPyramid");
+  }
+  void ClearIcpPyramid() { tf_check(tf_align_icp_set_pyramid(vol, nullptr), "ClearIcpPyramid"); }
+  // the camera (fx, fy, cx, cy) and the size of pyramid level 0..3, and levels 1..nLevels of a depth image (host arrays)
+  void IcpPyramidCamera(int level, float cam4[4], int* width, int* height) {
+    int32_t w = 0, h = 0;
+    tf_check(tf_align_icp_pyramid_camera(vol, level, cam4, &w, &h), "IcpPyramidCamera");
+    *width = w; *height = h;
+  }
+  void IcpPyramidDepth(const float* depthImage, int nLevels, float* const levels[3], const tf_align_icp_pyramid* pyramid = nullptr) {
+    tf_align_icp_pyramid def;
+    if (!pyramid) {
+      tf_check(tf_align_icp_pyramid_default(&def), "IcpPyramidDepth");
+      pyramid = &def;
+    }
+    tf_check(tf_align_icp_pyramid_depth(vol, depthImage, nLevels, pyramid, levels), "IcpPyramidDepth");
+  }
   // A lost camera found again (tf_relocalise): the cached keyframes that were put into the index (RelocConfigure, then
   // RelocIndexAdd for keyframes that have been through CacheKeyframe-style tf_keyframe_cache and tf_keyframe_set_pose)
   // are ranked by their small images against this frame's, and TrackFrame runs from the best ones' poses until one holds.

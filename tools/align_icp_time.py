@@ -25,6 +25,18 @@ and k_align_rows).
 figures, in the same run: us_per_evaluation["icp_gated"][stride], timed right after the ungated figure of the same stride,
 and "gated": what the default call and tf_track_frame did on this view with the gate set.  With --counter-run the N ICP
 calls per stride are issued gated (k_gated_rows in place of k_icp_rows).
+
+--pyramid measures the depth pyramid (tf_align_icp_set_pyramid, the library's default) beside the other figures, in the same
+run, as "pyramid":
+  us_pyramid_launch                one tf_align_icp_pyramid_depth_device building levels 1 and 2 (what the default schedule needs)
+  us_raycast_level[s]              one raycast of the two maps at the camera of the level of stride s = 2, 4
+  us_per_evaluation[s]             the evaluation a call with the setting on makes at the level of stride s: the level image,
+                                   the level camera and the level maps handed to tf_align_frame_icp_device at stride 1 (the same
+                                   rows launch, the same solve), (a call of 8 steps - a call of none) / 8 -- to be read against
+                                   us_per_evaluation["icp"][s], the strided evaluation
+  us_track_device_off / _on        one tf_track_frame_device call (raycasts, the ICP, the SDF stage, the finish; HIP events)
+  us_icp_default_host_wall_on      one tf_align_frame_icp call with the setting on (us_icp_default_host_wall is the same, off)
+  and what the default call did on this view with the setting on.
 """
 import argparse
 import ctypes as C
@@ -73,7 +85,55 @@ def _wall(fn, warm, reps):
     return (time.perf_counter() - t0) / reps * 1e6
 
 
-def run(hip, orbit, reps, counter_run=0, gate=False):
+def _pyramid(hip, stream, vol, cam, depth, d_depth, far, truth, icp_default, reps, per_evaluation_on):
+    """the --pyramid figures (this file's header); leaves the setting off and the raycast camera unset"""
+    out = {"us_raycast_level": {}, "us_per_evaluation": {}}
+    P = cam.width * cam.height
+    d_l = [hip.malloc(4 * (P >> (2 * l))) for l in (1, 2)]
+    bufs = list(d_l)
+    pyr = capi.AlignIcpPyramid()
+    build = lambda: vol.align_icp_pyramid_depth_device(d_depth, 2, pyr, d_l)
+    out["us_pyramid_launch"] = round(timed(hip, stream, build, 3, reps), 2)
+    build()
+    for l, stride in ((1, 2), (2, 4)):
+        c4, w, h = vol.align_icp_pyramid_camera(l)
+        d_v, d_n = hip.malloc(12 * w * h), hip.malloc(12 * w * h)
+        bufs += [d_v, d_n]
+        vol.raycast_camera(synth.Camera(w, h, float(c4[0]), float(c4[1]), float(c4[2]), float(c4[3])))
+        ray = lambda: vol.raycast_device(far, icp_default.ray_near, icp_default.ray_far, icp_default.ray_max_steps, d_normal=d_n, d_vertex=d_v)
+        out["us_raycast_level"][str(stride)] = round(timed(hip, stream, ray, 3, reps), 2)
+        ray()
+        out["us_per_evaluation"][str(stride)] = per_evaluation_on(d_l[l - 1], d_v, d_n)
+        vol.raycast_camera(None)
+    cell = capi.DevicePose()
+    cell.pose[:] = [float(x) for x in np.asarray(far, np.float32).reshape(12)]
+    cell.valid = 1
+    d_start, d_out, d_pose = hip.malloc(64), hip.malloc(256), hip.malloc(64)
+    bufs += [d_start, d_out, d_pose]
+    hip.upload(d_start, np.frombuffer(bytes(cell), np.uint8))
+    sdf = capi.AlignParams()
+    track = lambda: vol.track_frame_device(d_depth, d_start, icp_default, sdf, None, d_out, d_pose)
+    out["us_track_device_off"] = round(timed(hip, stream, track, 3, reps), 1)
+    vol.align_icp_set_pyramid(pyr)
+    out["us_track_device_on"] = round(timed(hip, stream, track, 3, reps), 1)
+    out["us_icp_default_host_wall_on"] = round(_wall(lambda: vol.align_frame_icp(depth, far, None, icp_default), 2, reps), 1)
+    g = vol.align_frame_icp(depth, far, None, icp_default)
+    log = vol.align_icp_log()
+    trk = vol.track_frame(depth, far)
+    vol.align_icp_set_pyramid(None)
+    out.update({"icp_status": g["status"], "icp_evaluations": g["evaluations"],
+                "icp_valid": [g["n_valid_first"], g["n_valid_last"], g["n_sampled"]],
+                "icp_sampled_per_evaluation": [r["n_sampled"] for r in log],
+                "icp_rms": [float(g["rms_first"]), float(g["rms_last"])], "icp_from_truth_m_rad": _distance(g["pose"], truth),
+                "icp_cond_A_last": float(np.linalg.cond(log[-1]["A"])), "track_stage": trk["stage"],
+                "track_from_truth_m_rad": _distance(trk["pose"], truth)})
+    vol.sync()
+    for p in bufs:
+        hip.h.hipFree(p)
+    return out
+
+
+def run(hip, orbit, reps, counter_run=0, gate=False, pyramid=False):
     cam = synth.Camera()
     res = np.float32(0.005)
     pool = 1 << 19
@@ -167,9 +227,19 @@ def run(hip, orbit, reps, counter_run=0, gate=False):
                      "icp_rms": [float(g["rms_first"]), float(g["rms_last"])], "icp_from_truth_m_rad": _distance(g["pose"], truth),
                      "icp_cond_A_last": float(np.linalg.cond(g_last["A"])), "track_stage": g_trk["stage"],
                      "track_from_truth_m_rad": _distance(g_trk["pose"], truth)}
+        pyr = None
+        if pyramid:
+            lv = dict(eps_t=0.0, eps_r=0.0)
+
+            def per_evaluation_on(d_img, d_lv, d_ln):
+                call = lambda params: (lambda: vol.align_frame_icp_device(d_img, far, d_lv, d_ln, far, params, d_res))
+                return round((timed(hip, stream, call(capi.AlignIcpParams(levels=[(1, 8)], **lv)), 3, reps) -
+                              timed(hip, stream, call(capi.AlignIcpParams(levels=[(1, 0)], **lv)), 3, reps)) / 8, 2)
+
+            pyr = _pyramid(hip, stream, vol, cam, depth, d_depth, far, truth, icp_default, reps, per_evaluation_on)
         for p in bufs:
             hip.h.hipFree(p)
-        return {"gated": gated, "scene": "room", "image": [cam.width, cam.height], "res_m": float(res), "orbit_frames": orbit, "frame": first,
+        return {"gated": gated, "pyramid": pyr, "scene": "room", "image": [cam.width, cam.height], "res_m": float(res), "orbit_frames": orbit, "frame": first,
                 "n_chunks": n_chunks, "start": "80 mm / 5 deg", "us_per_evaluation": per_eval,
                 "us_raycast_vertex_normal": round(us_ray, 1), "us_icp_default_device": round(us_icp, 1),
                 "us_icp_default_host_wall": round(us_host, 1), "us_track_frame_wall": round(us_track, 1),
@@ -194,11 +264,12 @@ def main():
     ap.add_argument("--counter-run", type=int, default=0, metavar="N",
                     help="no timing: N one-evaluation calls per stride of the ICP, then of tf_align_frame_device, for a profiler")
     ap.add_argument("--gate", action="store_true", help="also measure with the default normal-compatibility gate set")
+    ap.add_argument("--pyramid", action="store_true", help="also measure the depth pyramid (tf_align_icp_set_pyramid)")
     args = ap.parse_args()
     hip = Hip()
     if capi.lib().tf_device_count() <= 0:
         sys.exit("no HIP device: this tool measures the MI355X and has no CPU path")
-    print(json.dumps(run(hip, args.orbit, args.reps, args.counter_run, args.gate)), flush=True)
+    print(json.dumps(run(hip, args.orbit, args.reps, args.counter_run, args.gate, args.pyramid)), flush=True)
 
 
 if __name__ == "__main__":
