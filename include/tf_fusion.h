@@ -756,13 +756,14 @@ TF_API int tf_align_unit_group(tf_volume* v, tf_unit_group* group, int rigid, co
  * and |r| <= geo.max_residual).  Each bit is set only where the lower ones are; a pixel is valid when flags == 15.
  * Jacobian [nm, (R pc) x nm]: tf_align_frame's twist about the camera centre.  Huber weight, sums and their order, the
  * solve, the pose update, levels, stops, statuses, the closing evaluation, tf_align_result and tf_align_iter are
- * tf_align_frame's; a plane alone still ends TF_ALIGN_SINGULAR.  The order of operations is fixed in tf_align_icp.hip
+ * tf_align_frame's; a plane alone still ends TF_ALIGN_SINGULAR (tf_align_frame_icp_color below holds it).  The order of operations is fixed in tf_align_icp.hip
  * and restated in tests/align_icp_ref.py.  The maps and the model pose do not change during a call; re-rendering between
  * levels is the caller's choice, through a second call.  A call is 1 + 2 launches per evaluation, all enqueued up front.
  * Read-only; its state and log are its own: tf_align_log, tf_align_color_log and tf_align_group_log keep their meaning.
  * A normal-compatibility gate from the frame's own normals is a setting of the handle: the section below tf_track_frame.
  * So is a depth pyramid for the coarse levels (the section after that one); without it a level samples by stride alone.
- * Not here: a photometric row, a group form, multi-rank. */
+ * A photometric row beside the geometric one is a call of its own: tf_align_frame_icp_color, below the pyramid's section.
+ * Not here: a group form, multi-rank. */
 typedef struct tf_align_icp_params {
   tf_align_params geo;     /* levels, depth range, huber, damping, eps, min_valid; max_residual gates |r| */
   float max_distance;      /* gate on |pw - vm| */
@@ -897,6 +898,79 @@ TF_API int tf_align_icp_pyramid_depth_device(tf_volume* v, const float* d_depth,
                                              const tf_align_icp_pyramid* p, float* const d_levels[3]);
 TF_API int tf_align_icp_pyramid_depth(tf_volume* v, const float* depth, int32_t n_levels, const tf_align_icp_pyramid* p,
                                       float* const levels[3]);
+
+/* ---- the projective ICP held inside a plane: a photometric row from the model (tf_align_icp_color.hip) ----
+ * On a wall, a floor or a table top the point-to-plane rows leave three degrees of freedom open: tf_align_frame_icp ends
+ * TF_ALIGN_SINGULAR, or slides with its start where little relief is in view.  tf_align_frame_color cures that only inside
+ * the truncation band.  These calls put a photometric row beside the ICP's: the model's intensity L at the vertex of each
+ * model pixel (tf_align_frame_color's intensity, sampled from the volume, in [0, 1]; -1 on a miss or where a corner has no
+ * colour), its central image differences Gu, Gv (only across neighbours that have an intensity and lie within
+ * max_depth_jump in model depth), made once per call from the call's vertex and normal maps; per sampled pixel
+ * rc = (L[i] + Gu[i] du + Gv[i] dv) - Lf at the associated model pixel i, (du, dv) the projection's offset from that
+ * pixel's centre, Lf the frame pixel's luma; the gradient carried through the projection into the world frame and
+ * tf_align_frame's twist.  Flag bits 0 to 3 (4, 5 with tf_align_icp_set_gate) are the plain call's; bit 8 (256): valid
+ * geometrically, frame alpha != 0, model pixel usable; bit 9 (512): and |rc| <= max_photo_residual, the pixel is valid
+ * photometrically.  Sums, the joined system M = A_g + w^2 A_c, the solve, stops, tf_align_color_result and
+ * tf_align_color_iter are tf_align_frame_color's; TF_ALIGN_TOO_FEW goes by the geometric count.  With photo_weight == 0 or
+ * on a volume without colour pose, status and every geometric sum are tf_align_frame_icp's, bit for bit, gate off or on.
+ * All f32, the order of operations fixed in tf_align_icp_color.hip and restated in tests/align_icp_color_ref.py.  Readers:
+ * no voxel, mark or model generation changes; state and log are their own, so tf_align_log, tf_align_color_log,
+ * tf_align_icp_log and tf_align_group_log keep their meaning.
+ * Not here: the depth pyramid (tf_align_icp_set_pyramid is not read by these calls; a level samples by stride), a
+ * device-pose form (tf_track_*_device), a tf_relocalise hook, exposure or gain compensation, blurred images, multi-rank. */
+typedef struct tf_align_icp_color_params {
+  tf_align_icp_params icp;
+  float photo_weight, max_photo_residual, huber_photo; /* as tf_align_color_params'; all finite and >= 0 */
+  float max_depth_jump;                                /* model depth across which no gradient is formed; > 0, +inf allowed */
+} tf_align_icp_color_params;
+typedef struct tf_track_color_result {
+  tf_align_color_result icp, sdf;   /* sdf.geo.status == -1 (the rest 0): the second stage was not run */
+  int32_t stage;                    /* 0 none usable, 1 colour icp only, 2 tf_align_frame_color */
+  float pose[12];
+} tf_track_color_result;
+/* tf_align_icp_default_params, then 0.1, 0.25, 0.05 (tf_align_color_default_params') and max_depth_jump 0.1
+ * (tf_align_icp_gate_default's).  None of these is tuned on recorded data. */
+TF_API int tf_align_icp_color_default_params(tf_align_icp_color_params* out);
+/* TF_ERR_INVALID (nothing launched, outputs untouched) for everything tf_align_frame_icp(_device) rejects, a null rgba (the
+ * device form: not 4-byte aligned), non-finite or negative photo parameters, max_depth_jump not > 0.
+ * _device: depth, RGBA8 [H][W][4], the caller's vertex and normal maps in device memory, model_pose on the host (not NULL);
+ * asynchronous on the handle's stream, nothing read back.  tf_align_frame_icp_color: host images staged through the
+ * scratch pool; the model is raycast at model_pose (NULL: at pose) into maps the handle owns; it waits once. */
+TF_API int tf_align_frame_icp_color_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba, const float pose[12],
+                                           const float* d_model_vertex, const float* d_model_normal,
+                                           const float model_pose[12], const tf_align_icp_color_params* params,
+                                           tf_align_color_result* d_result);
+TF_API int tf_align_frame_icp_color(tf_volume* v, const float* depth, const uint8_t* rgba, const float pose[12],
+                                    const float* model_pose, const tf_align_icp_color_params* params,
+                                    tf_align_color_result* result);
+/* the records of the last tf_align_frame_icp_color(_device) or tf_track_frame_color call (waits for it), as tf_align_color_log */
+TF_API int tf_align_icp_color_log(tf_volume* v, tf_align_color_iter* out, int64_t cap, int64_t* n);
+/* The maps of one evaluation at icp.geo.stride[0] (iters are not read): r, flags, assoc as tf_align_icp_residuals', rc
+ * f32[H][W] and the world-frame gradient gradc3 f32[3][H][W] (both 0 without bit 8); any may be NULL; pixels not sampled
+ * get 0, 0, 0, -1, 0.  The host form takes host maps, or raycasts the model where both are NULL. */
+TF_API int tf_align_icp_color_residuals(tf_volume* v, const float* depth, const uint8_t* rgba, const float pose[12],
+                                        const float* model_vertex, const float* model_normal, const float* model_pose,
+                                        const tf_align_icp_color_params* params, float* r, float* rc, uint32_t* flags,
+                                        int32_t* assoc, float* gradc3);
+TF_API int tf_align_icp_color_residuals_device(tf_volume* v, const float* d_depth, const uint8_t* d_rgba, const float pose[12],
+                                               const float* d_model_vertex, const float* d_model_normal,
+                                               const float model_pose[12], const tf_align_icp_color_params* params,
+                                               float* d_r, float* d_rc, uint32_t* d_flags, int32_t* d_assoc, float* d_gradc3);
+/* A diagnostic, as tf_align_icp_frame_normals is: the model maps a call would make of these vertex and normal maps --
+ * L, Gu, Gv, each f32[H][W], any may be NULL; a gradient that does not exist is a quiet NaN.  TF_ERR_INVALID for a null
+ * input, a non-finite model pose, parameters the calls above reject (iters are not read). */
+TF_API int tf_align_icp_color_model_maps(tf_volume* v, const float* model_vertex, const float* model_normal,
+                                         const float model_pose[12], const tf_align_icp_color_params* params, float* L,
+                                         float* Gu, float* Gv);
+TF_API int tf_align_icp_color_model_maps_device(tf_volume* v, const float* d_model_vertex, const float* d_model_normal,
+                                                const float model_pose[12], const tf_align_icp_color_params* params,
+                                                float* d_L, float* d_Gu, float* d_Gv);
+/* tf_track_frame with colour in both stages: tf_align_frame_icp_color with the model raycast at the start pose; where that
+ * ends with status <= TF_ALIGN_MAX_ITERS, tf_align_frame_color from its pose; out->stage and out->pose by tf_track_frame's
+ * rule.  It waits twice.  TF_ERR_INVALID (nothing launched, out untouched) for what either stage rejects. */
+TF_API int tf_track_frame_color(tf_volume* v, const float* depth, const uint8_t* rgba, const float pose[12],
+                                const tf_align_icp_color_params* icp_params, const tf_align_color_params* sdf_params,
+                                tf_track_color_result* out);
 
 /* ---- tracking and integrating with the pose kept on the device (tf_devpose.hip) ------------------
  * KinectFusion's loop on the stream: track frame f against the model, decide whether the result is good enough, integrate

@@ -64,6 +64,9 @@ SYMBOLS = (
     "tf_align_icp_frame_normals_device",
     "tf_align_icp_pyramid_default", "tf_align_icp_set_pyramid", "tf_align_icp_get_pyramid", "tf_align_icp_pyramid_camera",
     "tf_align_icp_pyramid_depth", "tf_align_icp_pyramid_depth_device",
+    "tf_align_icp_color_default_params", "tf_align_frame_icp_color", "tf_align_frame_icp_color_device",
+    "tf_align_icp_color_log", "tf_align_icp_color_residuals", "tf_align_icp_color_residuals_device",
+    "tf_align_icp_color_model_maps", "tf_align_icp_color_model_maps_device", "tf_track_frame_color",
     "tf_track_accept_default", "tf_track_frame_device", "tf_integrate_frame_posed_device", "tf_track_integrate_device",
     "tf_pose_consts_download", "tf_integrate_frame_textured_posed_device", "tf_track_texture_device",
     "tf_pose_inverse_download",
@@ -225,6 +228,15 @@ class TrackResult(C.Structure):
     _fields_ = [("icp", AlignResult), ("sdf", AlignResult), ("stage", C.c_int32), ("pose", C.c_float * 12)]
 
 
+class AlignIcpColorParamsC(C.Structure):
+    _fields_ = [("icp", AlignIcpParamsC), ("photo_weight", C.c_float), ("max_photo_residual", C.c_float),
+                ("huber_photo", C.c_float), ("max_depth_jump", C.c_float)]
+
+
+class TrackColorResult(C.Structure):
+    _fields_ = [("icp", AlignColorResult), ("sdf", AlignColorResult), ("stage", C.c_int32), ("pose", C.c_float * 12)]
+
+
 class DevicePose(C.Structure):
     """tf_device_pose: a pose cell in device memory (64 bytes, 16-byte aligned)"""
     _fields_ = [("pose", C.c_float * 12), ("valid", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -291,6 +303,20 @@ def AlignIcpParams(**kw):
             setattr(p.geo, k, float(val))
         else:
             raise TypeError("tf_align_icp_params has no field %r" % k)
+    return p
+
+
+def AlignIcpColorParams(**kw):
+    """tf_align_icp_color_params: the library's defaults (tf_align_icp_color_default_params) with fields replaced by keyword;
+    photo_weight, max_photo_residual, huber_photo and max_depth_jump are its own, every other keyword is AlignIcpParams'."""
+    p = AlignIcpColorParamsC()
+    rc = lib().tf_align_icp_color_default_params(C.byref(p))
+    if rc != TF_OK:
+        raise TFError(rc, lib().tf_last_error().decode())
+    for k in ("photo_weight", "max_photo_residual", "huber_photo", "max_depth_jump"):
+        if k in kw:
+            setattr(p, k, float(kw.pop(k)))
+    p.icp = AlignIcpParams(**kw)
     return p
 
 
@@ -569,6 +595,16 @@ def lib():
     L.tf_align_icp_pyramid_camera.argtypes = [vp, C.c_int32, fp, i32p, i32p]
     L.tf_align_icp_pyramid_depth.argtypes = [vp, fp, C.c_int32, ayp, C.POINTER(fp)]
     L.tf_align_icp_pyramid_depth_device.argtypes = [vp, vp, C.c_int32, ayp, C.POINTER(vp)]
+    aqp, u8p, u32q = C.POINTER(AlignIcpColorParamsC), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    L.tf_align_icp_color_default_params.argtypes = [aqp]
+    L.tf_align_frame_icp_color.argtypes = [vp, fp, u8p, fp, fp, aqp, C.POINTER(AlignColorResult)]
+    L.tf_align_frame_icp_color_device.argtypes = [vp, vp, vp, fp, vp, vp, fp, aqp, vp]
+    L.tf_align_icp_color_log.argtypes = [vp, C.POINTER(AlignColorIter), C.c_int64, i64p]
+    L.tf_align_icp_color_residuals.argtypes = [vp, fp, u8p, fp, fp, fp, fp, aqp, fp, fp, u32q, i32p, fp]
+    L.tf_align_icp_color_residuals_device.argtypes = [vp, vp, vp, fp, vp, vp, fp, aqp, vp, vp, vp, vp, vp]
+    L.tf_align_icp_color_model_maps.argtypes = [vp, fp, fp, fp, aqp, fp, fp, fp]
+    L.tf_align_icp_color_model_maps_device.argtypes = [vp, vp, vp, fp, aqp, vp, vp, vp]
+    L.tf_track_frame_color.argtypes = [vp, fp, u8p, fp, aqp, acp, C.POINTER(TrackColorResult)]
     tap = C.POINTER(TrackAcceptC)
     L.tf_track_accept_default.argtypes = [tap]
     L.tf_track_frame_device.argtypes = [vp, vp, vp, aip, app, tap, vp, vp]
@@ -1191,6 +1227,10 @@ class Volume:
         n = C.c_int64(0)
         buf = (AlignColorIter * TF_ALIGN_MAX_EVALUATIONS)()
         self._ck(self.L.tf_align_color_log(self.h, buf, TF_ALIGN_MAX_EVALUATIONS, C.byref(n)))
+        return self._align_color_iters(buf, n.value)
+
+    @staticmethod
+    def _align_color_iters(buf, n):
         out = []
         iu = np.triu_indices(6)
 
@@ -1199,7 +1239,7 @@ class Volume:
             A[iu] = a21
             return A + np.triu(A, 1).T
 
-        for k in range(min(n.value, TF_ALIGN_MAX_EVALUATIONS)):
+        for k in range(min(n, TF_ALIGN_MAX_EVALUATIONS)):
             it = buf[k]
             g = it.geo
             A21, Ac21 = np.array(g.A, np.float64), np.array(it.Ac, np.float64)
@@ -1428,6 +1468,110 @@ class Volume:
         self._ck(self.L.tf_track_frame(self.h, _p(d, C.c_float), _p(pose, C.c_float), C.byref(icp_params),
                                        C.byref(sdf_params), C.byref(res)))
         return dict(icp=self.align_result(res.icp), sdf=self.align_result(res.sdf), stage=res.stage,
+                    pose=np.array(res.pose, np.float32).reshape(3, 4))
+
+    # -- the projective ICP with a photometric row from the model (tf_align_icp_color.hip; read-only)
+    def align_frame_icp_color(self, depth, rgba, pose, model_pose=None, params=None):
+        """align_frame_icp with a photometric row: depth [H, W] f32 and rgba [H, W, 4] u8 (alpha = colour valid) against the
+        model raycast at model_pose (None: at pose) -> align_frame_color's dict."""
+        d, H, W = self._align_depth(depth)
+        c = self._align_rgba(rgba, H, W)
+        pose = _f32(pose).reshape(12)
+        mp = None if model_pose is None else _p(_f32(model_pose).reshape(12), C.c_float)
+        params = params or AlignIcpColorParams()
+        res = AlignColorResult()
+        self._ck(self.L.tf_align_frame_icp_color(self.h, _p(d, C.c_float), _p(c, C.c_uint8), _p(pose, C.c_float), mp,
+                                                 C.byref(params), C.byref(res)))
+        return self.align_color_result(res)
+
+    def align_frame_icp_color_device(self, d_depth, d_rgba, pose, d_vertex, d_normal, model_pose, params, d_result):
+        """Asynchronous on the handle's stream: device images and device model maps (planar [3][H][W], rendered from
+        model_pose), the tf_align_color_result written to d_result"""
+        pose = _f32(pose).reshape(12)
+        mp = None if model_pose is None else _p(_f32(model_pose).reshape(12), C.c_float)
+        self._ck(self.L.tf_align_frame_icp_color_device(self.h, d_depth or None, d_rgba or None, _p(pose, C.c_float),
+                                                        d_vertex or None, d_normal or None, mp, C.byref(params),
+                                                        d_result or None))
+
+    def align_icp_color_log(self):
+        """The records of the last align_frame_icp_color(_device) or track_frame_color: align_color_log's dicts"""
+        n = C.c_int64(0)
+        buf = (AlignColorIter * TF_ALIGN_MAX_EVALUATIONS)()
+        self._ck(self.L.tf_align_icp_color_log(self.h, buf, TF_ALIGN_MAX_EVALUATIONS, C.byref(n)))
+        return self._align_color_iters(buf, n.value)
+
+    def _model_maps(self, vertex, normal, H, W):
+        maps = []
+        for m in (vertex, normal):
+            if m is not None:
+                m = _f32(m)
+                if m.size != 3 * W * H:
+                    raise TFError(TF_ERR_INVALID, "a model map needs 3x%dx%d values" % (H, W))
+            maps.append(m)
+        return maps
+
+    def align_icp_color_residuals(self, depth, rgba, pose, model_pose=None, params=None, vertex=None, normal=None):
+        """The maps of one evaluation at params.icp.geo.stride[0] -> dict(r, rc [H, W] f32, flags [H, W] u32, assoc [H, W]
+        i32, gradc [3, H, W] f32; photometrically valid where flags & 512).  vertex, normal: host model maps [3, H, W] f32
+        rendered from model_pose; both None: the model is raycast at model_pose (None: at pose)."""
+        d, H, W = self._align_depth(depth)
+        c = self._align_rgba(rgba, H, W)
+        pose = _f32(pose).reshape(12)
+        mp = None if model_pose is None else _p(_f32(model_pose).reshape(12), C.c_float)
+        maps = self._model_maps(vertex, normal, H, W)
+        params = params or AlignIcpColorParams()
+        out = {"r": np.zeros((H, W), np.float32), "rc": np.zeros((H, W), np.float32), "flags": np.zeros((H, W), np.uint32),
+               "assoc": np.zeros((H, W), np.int32), "gradc": np.zeros((3, H, W), np.float32)}
+        self._ck(self.L.tf_align_icp_color_residuals(self.h, _p(d, C.c_float), _p(c, C.c_uint8), _p(pose, C.c_float),
+                                                     None if maps[0] is None else _p(maps[0], C.c_float),
+                                                     None if maps[1] is None else _p(maps[1], C.c_float), mp, C.byref(params),
+                                                     _p(out["r"], C.c_float), _p(out["rc"], C.c_float),
+                                                     _p(out["flags"], C.c_uint32), _p(out["assoc"], C.c_int32),
+                                                     _p(out["gradc"], C.c_float)))
+        return out
+
+    def align_icp_color_residuals_device(self, d_depth, d_rgba, pose, d_vertex, d_normal, model_pose, params, d_r=0, d_rc=0,
+                                         d_flags=0, d_assoc=0, d_gradc=0):
+        pose = _f32(pose).reshape(12)
+        mp = None if model_pose is None else _p(_f32(model_pose).reshape(12), C.c_float)
+        self._ck(self.L.tf_align_icp_color_residuals_device(self.h, d_depth or None, d_rgba or None, _p(pose, C.c_float),
+                                                            d_vertex or None, d_normal or None, mp, C.byref(params),
+                                                            d_r or None, d_rc or None, d_flags or None, d_assoc or None,
+                                                            d_gradc or None))
+
+    def align_icp_color_model_maps(self, vertex, normal, model_pose, params=None):
+        """The model maps a colour ICP call makes of these host model maps [3, H, W] f32 -> dict(L, Gu, Gv [H, W] f32; L = -1
+        where there is no intensity, a gradient that does not exist is a NaN)"""
+        v = _f32(vertex)
+        H, W = v.shape[-2], v.shape[-1]
+        maps = self._model_maps(v, normal, H, W)
+        mp = _p(_f32(model_pose).reshape(12), C.c_float)
+        params = params or AlignIcpColorParams()
+        out = {k: np.zeros((H, W), np.float32) for k in ("L", "Gu", "Gv")}
+        self._ck(self.L.tf_align_icp_color_model_maps(self.h, _p(maps[0], C.c_float), _p(maps[1], C.c_float), mp,
+                                                      C.byref(params), _p(out["L"], C.c_float), _p(out["Gu"], C.c_float),
+                                                      _p(out["Gv"], C.c_float)))
+        return out
+
+    def align_icp_color_model_maps_device(self, d_vertex, d_normal, model_pose, params, d_L=0, d_Gu=0, d_Gv=0):
+        mp = None if model_pose is None else _p(_f32(model_pose).reshape(12), C.c_float)
+        self._ck(self.L.tf_align_icp_color_model_maps_device(self.h, d_vertex or None, d_normal or None, mp,
+                                                             None if params is None else C.byref(params), d_L or None,
+                                                             d_Gu or None, d_Gv or None))
+
+    def track_frame_color(self, depth, rgba, pose, icp_params=None, sdf_params=None):
+        """track_frame with colour in both stages: align_frame_icp_color with the model raycast at pose, then
+        align_frame_color from its pose -> dict(icp, sdf: align_frame_color's dicts (sdf["status"] == -1: not run), stage
+        0 / 1 / 2, pose [3, 4] f32)."""
+        d, H, W = self._align_depth(depth)
+        c = self._align_rgba(rgba, H, W)
+        pose = _f32(pose).reshape(12)
+        icp_params = icp_params or AlignIcpColorParams()
+        sdf_params = sdf_params or AlignColorParams()
+        res = TrackColorResult()
+        self._ck(self.L.tf_track_frame_color(self.h, _p(d, C.c_float), _p(c, C.c_uint8), _p(pose, C.c_float),
+                                             C.byref(icp_params), C.byref(sdf_params), C.byref(res)))
+        return dict(icp=self.align_color_result(res.icp), sdf=self.align_color_result(res.sdf), stage=res.stage,
                     pose=np.array(res.pose, np.float32).reshape(3, 4))
 
     # -- tracking and integrating with the pose in device memory (tf_devpose.hip; asynchronous, nothing read back)

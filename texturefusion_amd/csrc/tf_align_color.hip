@@ -7,7 +7,8 @@
 //                   the photometric row of each pixel and the wave's share of both sets of sums; with map outputs, the maps
 //                   of tf_align_color_residuals -- one body
 //   k_calign_solve  one workgroup: the partials combined in tile order, the two systems joined, the 6 x 6 solve and the pose
-//                   update by one lane (tf_align_solve.h), a log record, the result
+//                   update by one lane (tf_align_solve.h), a log record, the result: al_solve_color of tf_align_rows.h,
+//                   which the projective aligner with a photometric row runs too
 //
 // Per sampled pixel (x, y), all f32, every operation rounded on its own (-ffp-contract=off).  The geometric row is
 // k_align_rows' row unchanged: z, pc, q, pw = t + q, the seven sample points pw and pw -+ res e_a, flag bits 0 to 3, r = s,
@@ -41,8 +42,6 @@
 
 namespace tf {
 namespace {
-
-constexpr int kCaRow = 2 * kAlRow;   // doubles of a workgroup's partial sums: the geometric row, then the photometric one
 
 struct CAlignDev {
   AlignCtl* ctl;
@@ -119,47 +118,7 @@ __global__ __launch_bounds__(kAlWaves * 64) void k_calign_rows(VolumeDev v, CAli
 }
 
 __global__ __launch_bounds__(256) void k_calign_solve(CAlignDev d, CAlignSolveArgs a) {
-  if (al_idle(&d.ctl->state, a.c.level)) return;
-  // both rows of every workgroup through k_align_solve's additions; the photometric sums go to the record, the joined
-  // system stays in registers
-  __shared__ double red[8][kCaRow];
-  al_add_rows(d.part, a.c.n_rows, red);
-  if (threadIdx.x != 0) return;
-  AlignCtl c = *d.ctl;
-  tf_align_color_iter* rec = al_record(d.log, c);
-  double pose[12], M[21], bb[6], xi[6];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) pose[i] = d.pose_d[i];
-  const AlEval ev = al_fill_iter(&rec->geo, a.c, [&](int i) { return al_total(red, i); }, pose, M, bb);
-#pragma unroll
-  for (int i = 0; i < 21; ++i) {
-    const double tc = al_total(red, kAlRow + kAlA + i);
-    rec->Ac[i] = tc;
-    M[i] = M[i] + a.l2 * tc;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const double tc = al_total(red, kAlRow + kAlB + i);
-    rec->bc[i] = tc;
-    bb[i] = bb[i] + a.l2 * tc;
-  }
-  const double sum_rc2 = al_total(red, kAlRow + kAlR2);
-  const int n_photo = (int)al_total(red, kAlRow + kAlNv);
-  const float rms_c = n_photo > 0 ? (float)sqrt(sum_rc2 / (double)n_photo) : 0.f;
-  rec->n_photo = n_photo; rec->pad = 0;
-  rec->sum_rc2 = sum_rc2; rec->sum_wrc2 = al_total(red, kAlRow + kAlWr2);
-  if (c.n_eval == 0) { c.n_photo_first = n_photo; c.rms_photo_first = rms_c; }
-  al_count(c, ev);
-  if (al_decide(c, a.c, ev.n_valid, M, bb, &rec->geo, xi)) {
-    align_update(pose, xi);
-    al_keep_pose(d.pose_d, d.pose_f, pose);
-  }
-  *d.ctl = c;
-  tf_align_color_result* out = a.out;
-  al_fill_result(&out->geo, c, ev);
-  al_put_pose(out->geo.pose, pose);
-  out->n_photo_first = c.n_photo_first; out->n_photo_last = n_photo;
-  out->rms_photo_first = c.rms_photo_first; out->rms_photo_last = rms_c;
+  al_solve_color(d.ctl, d.log, d.pose_d, d.pose_f, d.part, a.c, a.l2, a.out);
 }
 
 // the state block as it lies in tf_volume::align_color (base == null: its size)

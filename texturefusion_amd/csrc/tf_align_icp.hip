@@ -294,6 +294,11 @@ int icp_model_levels(tf_volume* v, const float* d_depth, const float* model_pose
 
 void align_icp_release(tf_volume* v) { v->align_icp = AlignIcpState{}; }
 
+int align_icp_check(tf_volume* v, const float* depth, const float* pose, const float* model_pose, const tf_align_icp_params* p,
+                    bool with_iters, bool with_ray) {
+  return icp_check(v, depth, pose, model_pose, p, with_iters, with_ray);
+}
+
 int track_check(tf_volume* v, const float* depth, const float* pose, const tf_align_icp_params* icp_params,
                 const tf_align_params* sdf_params) {
   const int rc = icp_check(v, depth, pose, nullptr, icp_params, true, true);

@@ -22,12 +22,15 @@
 //   m2 = (nm.x^2 + nm.y^2) + nm.z^2, the hit test's value;  c2 = min_normal_cos * min_normal_cos, formed on the host
 //   d > 0 and d * d >= (c2 * l2) * m2: no square root, no division                                              (bit 5)
 //   bit 4 only where bits 0 to 3 are set, bit 5 only where bit 4 is; the pixel is valid iff flags == 63.
-// r, assoc, J (with the model normal), the Huber weight, the sums and the solve are k_icp_rows'.
+// r, assoc, J (with the model normal), the Huber weight, the sums and the solve are k_icp_rows'.  The frame normal and the
+// two bits are functions of tf_align_icp_normal.h (FnTaps, fn_taps, fn_in_range, frame_normal, fn_gate_bits), which the
+// colour ICP's gated rows kernel includes too.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <string.h>
 
+#include "tf_align_icp_normal.h"
 #include "tf_align_icp_rows.h"
 #include "tf_volume.h"
 
@@ -35,51 +38,6 @@
 
 namespace tf {
 namespace {
-
-// The five depths of a sampled pixel inside the image, loaded as one batch.  Where a neighbour lies outside the image all
-// four addresses are the pixel's own (in4 == false: the values are not looked at): selects, not branches, around the loads,
-// so that none of them waits for a comparison.
-struct FnTaps {
-  float z0, zl, zr, zu, zd;
-  bool in4;
-};
-__device__ __forceinline__ FnTaps fn_taps(const AlignRowsCommon& c, const AlPixel& px, const float* __restrict__ depth, size_t o) {
-  const long long s = c.stride;
-  FnTaps t;
-  t.in4 = px.X >= s && px.X + s < c.W && px.Y >= s && px.Y + s < c.H;
-  const size_t dx = t.in4 ? (size_t)s : 0, dy = t.in4 ? (size_t)s * (size_t)c.W : 0;  // o -+ dx, o -+ dy: inside [0, W * H)
-  t.z0 = depth[o];
-  t.zl = depth[o - dx]; t.zr = depth[o + dx];
-  t.zu = depth[o - dy]; t.zd = depth[o + dy];
-  return t;
-}
-__device__ __forceinline__ bool fn_in_range(const AlignRowsCommon& c, float z) {  // bit 0's test (al_point)
-  return isfinite(z) && z >= c.min_depth && z <= c.max_depth;
-}
-// the frame normal of a pixel whose own depth is in range (this file's header)
-struct FrameNormal {
-  float x, y, z, l2;
-  bool ok;
-};
-__device__ __forceinline__ FrameNormal frame_normal(const AlignRowsCommon& c, const AlPixel& px, const FnTaps& t, float max_jump) {
-  const int X = (int)px.X, Y = (int)px.Y, s = c.stride;
-  bool ok = t.in4 && fn_in_range(c, t.zl) && fn_in_range(c, t.zr) && fn_in_range(c, t.zu) && fn_in_range(c, t.zd);
-  ok = ok && fabsf(t.zl - t.z0) <= max_jump && fabsf(t.zr - t.z0) <= max_jump && fabsf(t.zu - t.z0) <= max_jump &&
-       fabsf(t.zd - t.z0) <= max_jump;
-  // (X - s, Y - s: not formed as ints where they could overflow -- in4 is false there and the value is not used)
-  const float xl = t.in4 ? (float)(X - s) : 0.f, xr = t.in4 ? (float)(X + s) : 0.f;
-  const float yu = t.in4 ? (float)(Y - s) : 0.f, yd = t.in4 ? (float)(Y + s) : 0.f;
-  const float dcx = ((float)X - c.cxs) / c.fx, dcy = ((float)Y - c.cys) / c.fy;
-  const float dcxl = (xl - c.cxs) / c.fx, dcxr = (xr - c.cxs) / c.fx;
-  const float dcyu = (yu - c.cys) / c.fy, dcyd = (yd - c.cys) / c.fy;
-  const float ax = dcxr * t.zr - dcxl * t.zl, ay = dcy * t.zr - dcy * t.zl, az = t.zr - t.zl;
-  const float bx = dcx * t.zd - dcx * t.zu, by = dcyd * t.zd - dcyu * t.zu, bz = t.zd - t.zu;
-  FrameNormal n;
-  n.x = by * az - bz * ay; n.y = bz * ax - bx * az; n.z = bx * ay - by * ax;
-  n.l2 = (n.x * n.x + n.y * n.y) + n.z * n.z;
-  n.ok = ok && isfinite(n.l2) && n.l2 > 0.f;
-  return n;
-}
 
 // (resources: tests/test_kernel_resources_align_icp_gate.py -- k_icp_rows' budget)
 __global__ __launch_bounds__(kAlWaves * 64) void k_gated_rows(IcpRowsArgs a, float c2, float max_jump) {
@@ -97,14 +55,7 @@ __global__ __launch_bounds__(kAlWaves * 64) void k_gated_rows(IcpRowsArgs a, flo
       fl = m.fl; as = m.as;
       s = m.s; gx = m.gx; gy = m.gy; gz = m.gz;
       const FrameNormal n = frame_normal(a.c, px, t, max_jump);
-      const float* P = a.pose;
-      const float wx = (P[0] * n.x + P[1] * n.y) + P[2] * n.z;
-      const float wy = (P[4] * n.x + P[5] * n.y) + P[6] * n.z;
-      const float wz = (P[8] * n.x + P[9] * n.y) + P[10] * n.z;
-      const float d = (wx * gx + wy * gy) + wz * gz;  // (g is the model normal wherever bit 2 is set)
-      const bool has = fl == 15u && n.ok;
-      const bool agree = d > 0.f && d * d >= (c2 * n.l2) * m.m2;
-      fl |= has ? (agree ? 48u : 16u) : 0u;
+      fl |= fn_gate_bits(fl, n, a.pose, gx, gy, gz, m.m2, c2);  // (g is the model normal wherever bit 2 is set)
     }
     if (a.r) a.r[o] = s;
     if (a.flags) a.flags[o] = fl;

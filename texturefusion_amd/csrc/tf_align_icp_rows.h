@@ -1,5 +1,5 @@
-// tf_align_icp_rows.h -- what the two rows kernels of the projective ICP share: k_icp_rows (tf_align_icp.hip) and the gated
-// kernel k_gated_rows (tf_align_icp_gate.hip).  The argument block of a rows launch, the association of a pixel's point
+// tf_align_icp_rows.h -- what the rows kernels of the projective ICP share: k_icp_rows (tf_align_icp.hip), the gated
+// kernel k_gated_rows (tf_align_icp_gate.hip) and the colour ICP's k_cicp_rows (tf_align_icp_color.hip).  The argument block of a rows launch, the association of a pixel's point
 // with the model maps (flag bits 1 to 3: one text for both kernels), and the host functions by which tf_align_icp.hip hands
 // a launch to the gated file.  Device functions are forced inline and every operation is rounded on its own.
 #pragma once
@@ -39,15 +39,26 @@ struct IcpAssoc {
   int32_t as;
   float s, gx, gy, gz, m2;
 };
-__device__ __forceinline__ IcpAssoc icp_assoc(const IcpRowsArgs& a, const AlPoint& p) {
+// What the colour ICP's photometric row takes from the association (tf_align_icp_color.hip's header): in, the three planes
+// of the call's model maps; out, where bit 1 is set, the point in the model camera, its projection (uc, vc), the nearest
+// pixel (uf, vf) and that pixel's three map values, loaded with the six of the geometric row.  Without bit 1: zeros, l = -1.
+struct IcpPhoto {
+  const float* L;
+  const float* Gu;
+  const float* Gv;
+  float mx, my, mz, uc, vc, uf, vf, l, gu, gv;
+};
+__device__ __forceinline__ IcpAssoc icp_assoc(const IcpRowsArgs& a, const AlPoint& p, IcpPhoto* ph = nullptr) {
   IcpAssoc r{1u, -1, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (ph) { ph->mx = ph->my = ph->mz = ph->uc = ph->vc = ph->uf = ph->vf = ph->gu = ph->gv = 0.f; ph->l = -1.f; }
   const float* M = a.pose + 12;
   const float dx = p.wx - M[3], dy = p.wy - M[7], dz = p.wz - M[11];
   const float mx = (M[0] * dx + M[4] * dy) + M[8] * dz;
   const float my = (M[1] * dx + M[5] * dy) + M[9] * dz;
   const float mz = (M[2] * dx + M[6] * dy) + M[10] * dz;
   if (mz > a.c.min_depth) {
-    const float uf = floorf(((a.c.fx * mx) / mz + a.c.cxs) + 0.5f), vf = floorf(((a.c.fy * my) / mz + a.c.cys) + 0.5f);
+    const float uc = (a.c.fx * mx) / mz + a.c.cxs, vc = (a.c.fy * my) / mz + a.c.cys;
+    const float uf = floorf(uc + 0.5f), vf = floorf(vc + 0.5f);
     // (compared as floats: a NaN or an infinity of a point near the model camera's plane fails here, ahead of the cast)
     if (uf >= 0.f && uf < (float)a.c.W && vf >= 0.f && vf < (float)a.c.H) {
       r.fl |= 2u;
@@ -56,6 +67,10 @@ __device__ __forceinline__ IcpAssoc icp_assoc(const IcpRowsArgs& a, const AlPoin
       // the six scattered loads of the pixel, all issued ahead of the first use: one batch in flight
       const float nx = a.nm[i], ny = a.nm[a.plane + i], nz = a.nm[2 * a.plane + i];
       const float vx = a.vm[i], vy = a.vm[a.plane + i], vz = a.vm[2 * a.plane + i];
+      if (ph) {  // (a constant after inlining) the photometric row's three, in the same batch
+        ph->l = ph->L[i]; ph->gu = ph->Gu[i]; ph->gv = ph->Gv[i];
+        ph->mx = mx; ph->my = my; ph->mz = mz; ph->uc = uc; ph->vc = vc; ph->uf = uf; ph->vf = vf;
+      }
       // (selects, not a branch on the normal: a branch would let the compiler hold the vertex loads back behind it)
       r.m2 = (nx * nx + ny * ny) + nz * nz;
       const bool hit = r.m2 > 0.5f;

@@ -1,5 +1,5 @@
 // tf_align_rows.h -- the Gauss-Newton machinery the four aligners share (tf_align.hip, tf_align_color.hip,
-// tf_align_group.hip, tf_align_icp.hip), beside the tile's tree (tf_align_tree.h) and the 6 x 6 step (tf_align_solve.h).
+// tf_align_group.hip, tf_align_icp.hip) and the colour ICP (tf_align_icp_color.hip), beside the tile's tree (tf_align_tree.h) and the 6 x 6 step (tf_align_solve.h).
 // Device only; every function is forced inline into the kernel that calls it and every operation is rounded on its own.
 // An aligner keeps what is its own: the row of a pixel, the lever of the twist, how a step is applied.  This file is the
 // one place for the rest, and with tf_align_tree.h it fixes the order of every addition:
@@ -322,6 +322,54 @@ __device__ __forceinline__ void al_solve_pose(AlignCtl* ctl, tf_align_iter* log,
   *ctl = c;
   al_fill_result(out, c, ev);
   al_put_pose(out->pose, pose);
+}
+
+// A whole solve launch of an aligner with one pose and two rows of sums, a geometric and a photometric one, joined as
+// M = A_g + l2 A_c, b = b_g + l2 b_c (k_calign_solve, k_cicp_solve): one workgroup of 256 threads.
+constexpr int kCaRow = 2 * kAlRow;   // doubles of a workgroup's partial sums: the geometric row, then the photometric one
+__device__ __forceinline__ void al_solve_color(AlignCtl* ctl, tf_align_color_iter* log, double* pose_d, float* pose_f,
+                                               const double* part, const AlignSolveCommon& a, double l2,
+                                               tf_align_color_result* out) {
+  if (al_idle(&ctl->state, a.level)) return;
+  // both rows of every workgroup through k_align_solve's additions; the photometric sums go to the record, the joined
+  // system stays in registers
+  __shared__ double red[8][kCaRow];
+  al_add_rows(part, a.n_rows, red);
+  if (threadIdx.x != 0) return;
+  AlignCtl c = *ctl;
+  tf_align_color_iter* rec = al_record(log, c);
+  double pose[12], M[21], bb[6], xi[6];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) pose[i] = pose_d[i];
+  const AlEval ev = al_fill_iter(&rec->geo, a, [&](int i) { return al_total(red, i); }, pose, M, bb);
+#pragma unroll
+  for (int i = 0; i < 21; ++i) {
+    const double tc = al_total(red, kAlRow + kAlA + i);
+    rec->Ac[i] = tc;
+    M[i] = M[i] + l2 * tc;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const double tc = al_total(red, kAlRow + kAlB + i);
+    rec->bc[i] = tc;
+    bb[i] = bb[i] + l2 * tc;
+  }
+  const double sum_rc2 = al_total(red, kAlRow + kAlR2);
+  const int n_photo = (int)al_total(red, kAlRow + kAlNv);
+  const float rms_c = n_photo > 0 ? (float)sqrt(sum_rc2 / (double)n_photo) : 0.f;
+  rec->n_photo = n_photo; rec->pad = 0;
+  rec->sum_rc2 = sum_rc2; rec->sum_wrc2 = al_total(red, kAlRow + kAlWr2);
+  if (c.n_eval == 0) { c.n_photo_first = n_photo; c.rms_photo_first = rms_c; }
+  al_count(c, ev);
+  if (al_decide(c, a, ev.n_valid, M, bb, &rec->geo, xi)) {
+    align_update(pose, xi);
+    al_keep_pose(pose_d, pose_f, pose);
+  }
+  *ctl = c;
+  al_fill_result(&out->geo, c, ev);
+  al_put_pose(out->geo.pose, pose);
+  out->n_photo_first = c.n_photo_first; out->n_photo_last = n_photo;
+  out->rms_photo_first = c.rms_photo_first; out->rms_photo_last = rms_c;
 }
 
 }  // namespace tf

@@ -218,6 +218,14 @@ struct AlignIcpState {
   DevMem pyr_img, pyr_maps, pyr_res;  // fitted buffers (tf_mem.h)
 };
 
+// The colour ICP's block (tf_align_icp_color.hip), and ten planes of f32 beside it: the model's vertex and normal maps of
+// the form that raycasts itself (six), then the model maps L, Gu, Gv and Z of a call (four) -- null until first use
+struct AlignIcpColorState {
+  AlignBlock st;
+  DevMem maps;
+  size_t map_pixels = 0;  // pixels each plane of `maps` has room for
+};
+
 // Relocalisation against the cached keyframes (tf_reloc.hip): the configuration, and the index -- one block holding every
 // row's descriptor, the query's and the scores; the host keeps which keyframe a row belongs to.  Empty until configured.
 struct RelocState {
@@ -338,6 +346,7 @@ struct tf_volume {
   tf::CcState cc;
   tf::AlignBlock align, align_color, align_group;
   tf::AlignIcpState align_icp;
+  tf::AlignIcpColorState align_icp_color;
   tf::RelocState reloc;
   tf::DevMem devpose;  // one PoseConsts (tf_devpose.h): what k_pose_consts derives from a pose cell; null until first use
   tf::DevMem devpose_inv;  // one PoseInverse: the cell's rigid inverse for the patch stage, written by the same launch
@@ -484,7 +493,12 @@ int align_log(tf_volume* v, const void* d_ctl, const void* d_log, size_t rec_byt
 void align_release(tf_volume* v);        // these free the state block of tf_align.hip,
 void align_color_release(tf_volume* v);  // of tf_align_color.hip,
 void align_group_release(tf_volume* v);  // of tf_align_group.hip,
-void align_icp_release(tf_volume* v);    // and of tf_align_icp.hip with its maps
+void align_icp_release(tf_volume* v);    // of tf_align_icp.hip with its maps,
+void align_icp_color_release(tf_volume* v);  // and of tf_align_icp_color.hip with its maps
+// what tf_align_frame_icp refuses a call for, but null map and result pointers (tf_align_icp.hip; with_ray: the form
+// raycasts the model itself), for the colour ICP to refuse the same
+int align_icp_check(tf_volume* v, const float* depth, const float* pose, const float* model_pose, const tf_align_icp_params* p,
+                    bool with_iters, bool with_ray);
 void reloc_release(tf_volume* v);        // frees tf_reloc.hip's index and forgets its configuration
 // The pieces of the device tracker outside tf_devpose.hip, each next to the launches it chains; the caller has checked the
 // parameters, nothing is read back.  raycast_posed (tf_ray.hip): tf_raycast_device's launch at the pose in *d_cell.

@@ -37,6 +37,14 @@ run, as "pyramid":
   us_track_device_off / _on        one tf_track_frame_device call (raycasts, the ICP, the SDF stage, the finish; HIP events)
   us_icp_default_host_wall_on      one tf_align_frame_icp call with the setting on (us_icp_default_host_wall is the same, off)
   and what the default call did on this view with the setting on.
+
+--color measures the colour ICP (tf_align_frame_icp_color_device, tf_align_icp_color.hip) beside the other figures, in the
+same run, as "color" and us_per_evaluation["icp_color"][stride] (timed right after the plain figure of the same stride; the
+two map launches of a call cancel in the difference):
+  us_model_maps                    one tf_align_icp_color_model_maps_device (k_cicp_lum, k_cicp_grad and three copies)
+  us_icp_color_default_device      one tf_align_frame_icp_color_device call, default parameters, maps given
+  us_icp_color_default_host_wall   one tf_align_frame_icp_color call: uploads, raycast, the maps, the ICP, one wait
+  and what the default call did on this view.  With --gate the gated colour evaluation is timed too ("icp_color_gated").
 """
 import argparse
 import ctypes as C
@@ -133,7 +141,7 @@ def _pyramid(hip, stream, vol, cam, depth, d_depth, far, truth, icp_default, rep
     return out
 
 
-def run(hip, orbit, reps, counter_run=0, gate=False, pyramid=False):
+def run(hip, orbit, reps, counter_run=0, gate=False, pyramid=False, color=False):
     cam = synth.Camera()
     res = np.float32(0.005)
     pool = 1 << 19
@@ -146,12 +154,12 @@ def run(hip, orbit, reps, counter_run=0, gate=False, pyramid=False):
             d, rgba, _, pose = synth.room_frame(k, cam, with_quality=False)
             vol.integrate_frame_host(d, rgba, pose.reshape(12), None, k)
             if k == first:
-                frame = (d, pose)
+                frame = (d, pose, rgba)
         vol.update_meshes()  # the neighbour table: the sampler reads it
         vol.sync()
         n_chunks = int(vol.stats().n_chunks)
         P = cam.width * cam.height
-        depth, truth = frame
+        depth, truth, rgba = frame
         far = _far(truth, 0.080, 5.0)
         near = _perturb(truth, np.random.default_rng(0))
         d_depth, d_v, d_n = hip.malloc(4 * P), hip.malloc(12 * P), hip.malloc(12 * P)
@@ -174,6 +182,20 @@ def run(hip, orbit, reps, counter_run=0, gate=False, pyramid=False):
             return round((timed(hip, stream, icp_call(capi.AlignIcpParams(levels=[(stride, 8)], **lv)), 3, reps) -
                           timed(hip, stream, icp_call(capi.AlignIcpParams(levels=[(stride, 0)], **lv)), 3, reps)) / 8, 2)
 
+        d_rgba = d_cres = None
+        if color:
+            d_rgba, d_cres = hip.malloc(4 * P), hip.malloc(C.sizeof(capi.AlignColorResult))
+            hip.upload(d_rgba, np.ascontiguousarray(rgba, np.uint8))
+            bufs += [d_rgba, d_cres]
+
+        def color_call(params):
+            return lambda: vol.align_frame_icp_color_device(d_depth, d_rgba, far, d_v, d_n, far, params, d_cres)
+
+        def per_evaluation_color(stride):
+            lv = dict(eps_t=0.0, eps_r=0.0)
+            return round((timed(hip, stream, color_call(capi.AlignIcpColorParams(levels=[(stride, 8)], **lv)), 3, reps) -
+                          timed(hip, stream, color_call(capi.AlignIcpColorParams(levels=[(stride, 0)], **lv)), 3, reps)) / 8, 2)
+
         raycast()
         if counter_run:
             if gate:
@@ -195,9 +217,13 @@ def run(hip, orbit, reps, counter_run=0, gate=False, pyramid=False):
         for stride in (1, 2, 4):
             lv = dict(eps_t=0.0, eps_r=0.0)
             per_eval["icp"][str(stride)] = per_evaluation(stride)
+            if color:
+                per_eval.setdefault("icp_color", {})[str(stride)] = per_evaluation_color(stride)
             if gate:
                 vol.align_icp_set_gate(capi.AlignIcpGate())
                 per_eval.setdefault("icp_gated", {})[str(stride)] = per_evaluation(stride)
+                if color:
+                    per_eval.setdefault("icp_color_gated", {})[str(stride)] = per_evaluation_color(stride)
                 vol.align_icp_set_gate(None)
             per_eval["frame"][str(stride)] = round((timed(hip, stream, frame_call(capi.AlignParams(levels=[(stride, 8)], **lv)), 3, reps) -
                                                     timed(hip, stream, frame_call(capi.AlignParams(levels=[(stride, 0)], **lv)), 3, reps)) / 8, 2)
@@ -227,6 +253,26 @@ def run(hip, orbit, reps, counter_run=0, gate=False, pyramid=False):
                      "icp_rms": [float(g["rms_first"]), float(g["rms_last"])], "icp_from_truth_m_rad": _distance(g["pose"], truth),
                      "icp_cond_A_last": float(np.linalg.cond(g_last["A"])), "track_stage": g_trk["stage"],
                      "track_from_truth_m_rad": _distance(g_trk["pose"], truth)}
+        col = None
+        if color:
+            cdef = capi.AlignIcpColorParams()
+            d_m = [hip.malloc(4 * P) for _ in range(3)]
+            bufs += d_m
+            us_maps = timed(hip, stream, lambda: vol.align_icp_color_model_maps_device(d_v, d_n, far, cdef, *d_m), 3, reps)
+            us_c = timed(hip, stream, color_call(cdef), 3, reps)
+            vol.sync()
+            craw = np.empty(C.sizeof(capi.AlignColorResult), np.uint8)
+            hip.download(d_cres, craw)
+            g = vol.align_color_result(craw)
+            c_last = vol.align_icp_color_log()[-1]
+            us_ch = _wall(lambda: vol.align_frame_icp_color(depth, rgba, far, None, cdef), 2, reps)
+            col = {"us_model_maps": round(us_maps, 1), "us_icp_color_default_device": round(us_c, 1),
+                   "us_icp_color_default_host_wall": round(us_ch, 1), "icp_status": g["status"],
+                   "icp_evaluations": g["evaluations"], "icp_valid": [g["n_valid_first"], g["n_valid_last"], g["n_sampled"]],
+                   "icp_photo": [g["n_photo_first"], g["n_photo_last"]],
+                   "icp_rms_photo": [float(g["rms_photo_first"]), float(g["rms_photo_last"])],
+                   "icp_from_truth_m_rad": _distance(g["pose"], truth),
+                   "icp_cond_M_last": float(np.linalg.cond(c_last["A"] + float(np.float32(cdef.photo_weight)) ** 2 * c_last["Ac"]))}
         pyr = None
         if pyramid:
             lv = dict(eps_t=0.0, eps_r=0.0)
@@ -239,7 +285,7 @@ def run(hip, orbit, reps, counter_run=0, gate=False, pyramid=False):
             pyr = _pyramid(hip, stream, vol, cam, depth, d_depth, far, truth, icp_default, reps, per_evaluation_on)
         for p in bufs:
             hip.h.hipFree(p)
-        return {"gated": gated, "pyramid": pyr, "scene": "room", "image": [cam.width, cam.height], "res_m": float(res), "orbit_frames": orbit, "frame": first,
+        return {"gated": gated, "pyramid": pyr, "color": col, "scene": "room", "image": [cam.width, cam.height], "res_m": float(res), "orbit_frames": orbit, "frame": first,
                 "n_chunks": n_chunks, "start": "80 mm / 5 deg", "us_per_evaluation": per_eval,
                 "us_raycast_vertex_normal": round(us_ray, 1), "us_icp_default_device": round(us_icp, 1),
                 "us_icp_default_host_wall": round(us_host, 1), "us_track_frame_wall": round(us_track, 1),
@@ -265,11 +311,12 @@ def main():
                     help="no timing: N one-evaluation calls per stride of the ICP, then of tf_align_frame_device, for a profiler")
     ap.add_argument("--gate", action="store_true", help="also measure with the default normal-compatibility gate set")
     ap.add_argument("--pyramid", action="store_true", help="also measure the depth pyramid (tf_align_icp_set_pyramid)")
+    ap.add_argument("--color", action="store_true", help="also measure the colour ICP (tf_align_frame_icp_color_device)")
     args = ap.parse_args()
     hip = Hip()
     if capi.lib().tf_device_count() <= 0:
         sys.exit("no HIP device: this tool measures the MI355X and has no CPU path")
-    print(json.dumps(run(hip, args.orbit, args.reps, args.counter_run, args.gate, args.pyramid)), flush=True)
+    print(json.dumps(run(hip, args.orbit, args.reps, args.counter_run, args.gate, args.pyramid, args.color)), flush=True)
 
 
 if __name__ == "__main__":
