@@ -669,7 +669,7 @@ TF_API int tf_align_residuals_device(tf_volume* v, const float* d_depth, const f
  * A step solves (A + photo_weight^2 A_c + damping diag) xi = -(b + photo_weight^2 b_c); everything else -- levels, stops
  * (TF_ALIGN_TOO_FEW goes by the geometric n_valid), the closing evaluation, the status -- is tf_align_frame's.  With
  * photo_weight == 0 or on a volume without colour the pose, the status and the geometric sums are tf_align_frame's bit
- * for bit.  No image gradients, no blurred pyramids, no exposure compensation.  Read-only; its state and log are its own:
+ * for bit.  No image gradients, no blurred pyramids (exposure: tf_align_set_exposure).  Read-only; its state and log are its own:
  * tf_align_log keeps meaning the last tf_align_frame call. */
 typedef struct tf_align_color_params {
   tf_align_params geo;
@@ -917,7 +917,7 @@ TF_API int tf_align_icp_pyramid_depth(tf_volume* v, const float* depth, int32_t 
  * no voxel, mark or model generation changes; state and log are their own, so tf_align_log, tf_align_color_log,
  * tf_align_icp_log and tf_align_group_log keep their meaning.
  * Not here: the depth pyramid (tf_align_icp_set_pyramid is not read by these calls; a level samples by stride), a
- * device-pose form (tf_track_*_device), a tf_relocalise hook, exposure or gain compensation, blurred images, multi-rank. */
+ * device-pose form (tf_track_*_device), a tf_relocalise hook, blurred images, multi-rank (exposure: tf_align_set_exposure). */
 typedef struct tf_align_icp_color_params {
   tf_align_icp_params icp;
   float photo_weight, max_photo_residual, huber_photo; /* as tf_align_color_params'; all finite and >= 0 */
@@ -971,6 +971,55 @@ TF_API int tf_align_icp_color_model_maps_device(tf_volume* v, const float* d_mod
 TF_API int tf_track_frame_color(tf_volume* v, const float* depth, const uint8_t* rgba, const float pose[12],
                                 const tf_align_icp_color_params* icp_params, const tf_align_color_params* sdf_params,
                                 tf_track_color_result* out);
+
+/* ---- exposure compensation in the photometric aligners (tf_align_exposure.hip) -------------------
+ * A camera with auto-exposure shows the model brighter or darker than the volume's running mean holds it.  With this
+ * setting the frame's luma is compensated before it is compared, in f32, every operation rounded on its own:
+ *   Lfe = gain_f * Lf + offset_f;   rc = L(pw) - Lfe  (tf_align_frame_color),
+ *   rc = (L[i] + (Gu[i] du + Gv[i] dv)) - Lfe  (tf_align_frame_icp_color)
+ * with Lf formed as before and (gain_f, offset_f) the f32 roundings of a pair carried in f64 beside the pose.  Every flag
+ * bit keeps its definition; bit 6 (bit 9 of the ICP form) and the Huber weight use the compensated rc.  With gain 1 and
+ * offset 0, Lfe is Lf bit for bit.  The pair is estimated with the pose: a third row of 17 sums beside the geometric and
+ * the photometric one (P_i = sum wJc_i, Q_i = sum wJc_i Lf, S_w = sum wc, S_l = sum wc Lf, S_ll = sum wl Lf, S_r = sum wc rc,
+ * S_lr = sum wl rc with wl = wc * Lf, each term the f64 product of two f32 operands, over the photometrically valid
+ * pixels), the pair eliminated from the photometric system ahead of the joined 6 x 6 solve and stepped after it
+ * (tf_align_exposure_solve.h states every operation; tests/align_exposure_ref.py restates it).  Stops, TF_ALIGN_TOO_FEW by
+ * the geometric count, the convergence test on the twist alone and the closing evaluation are unchanged; with
+ * photo_weight == 0 or on a volume without colour pose, status and geometric sums stay the plain call's bit for bit.
+ * A setting of the handle, as tf_align_icp_set_gate: off in a new state and off again after tf_volume_reset.  It is read by
+ * tf_align_frame_color(_device), tf_align_frame_icp_color(_device), both residual-map calls (their rc uses the cell's
+ * current pair) and tf_track_frame_color.  The start pair lives in a cell in device memory the handle owns: the setter
+ * writes (gain0, offset0) into it on the handle's stream, a call's begin launch reads its start from it, and with carry on
+ * the closing solve launch of a call that ends with status <= TF_ALIGN_MAX_ITERS writes its estimate there (a call stopped
+ * TF_ALIGN_TOO_FEW or TF_ALIGN_SINGULAR leaves the cell as it was): the _device forms stay asynchronous, nothing is read
+ * back.  tf_track_frame_color's second stage starts from its first stage's estimate whenever it runs, whatever carry says;
+ * after the call the cell holds the last stage's estimate with carry on and (gain0, offset0) with carry off.  With the
+ * setting off every call enqueues exactly the launches it enqueued before.
+ * Not here: per-channel gains, vignetting, response curves, the group aligner, use of the estimate by the integrator. */
+typedef struct tf_align_exposure {
+  int32_t unknowns;         /* 0: apply the start pair, estimate nothing; 1: the offset; 2: gain and offset */
+  int32_t carry;            /* != 0: a call that ends with status <= TF_ALIGN_MAX_ITERS leaves its estimate as the next call's start */
+  float gain0, offset0;     /* the start pair */
+  float min_gain, max_gain; /* the gain is clamped into this after every update */
+} tf_align_exposure;
+typedef struct tf_align_exposure_iter {   /* one per evaluation, parallel to the tf_align_color_iter of the same index */
+  double gain, offset;                    /* the pair at which the sums were taken */
+  int32_t rank, n_photo;                  /* unknowns eliminated in this evaluation (0..2); photometrically valid pixels */
+  double P[6], Q[6], S_w, S_l, S_ll, S_r, S_lr;
+  double d_offset, d_gain;                /* the step taken on the pair, 0 where none was taken */
+} tf_align_exposure_iter;
+/* unknowns 2, carry 0, gain0 1, offset0 0, min_gain 0.25, max_gain 4.  None of these is tuned on recorded data. */
+TF_API int tf_align_exposure_default(tf_align_exposure* out);
+/* e == NULL: off.  TF_ERR_INVALID (setting unchanged, nothing launched) for unknowns outside 0..2, a non-finite field,
+ * min_gain <= 0, min_gain > max_gain, gain0 outside [min_gain, max_gain]. */
+TF_API int tf_align_set_exposure(tf_volume* v, const tf_align_exposure* e);
+TF_API int tf_align_get_exposure(tf_volume* v, tf_align_exposure* out, int32_t* on);
+/* which: 0 the last tf_align_frame_color(_device) call, 1 the last tf_align_frame_icp_color(_device) or
+ * tf_track_frame_color call; TF_ERR_INVALID outside 0..1.  Both wait for the call, as the other logs.  The log holds the
+ * records of that call where it ran with the setting on (*n = 0 otherwise).  The estimate is the pair that call ended at,
+ * *valid != 0 where it ran with the setting on and ended with status <= TF_ALIGN_MAX_ITERS. */
+TF_API int tf_align_exposure_log(tf_volume* v, int32_t which, tf_align_exposure_iter* out, int64_t cap, int64_t* n);
+TF_API int tf_align_exposure_estimate(tf_volume* v, int32_t which, double gain_offset[2], int32_t* valid);
 
 /* ---- tracking and integrating with the pose kept on the device (tf_devpose.hip) ------------------
  * KinectFusion's loop on the stream: track frame f against the model, decide whether the result is good enough, integrate

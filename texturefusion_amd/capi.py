@@ -67,6 +67,8 @@ SYMBOLS = (
     "tf_align_icp_color_default_params", "tf_align_frame_icp_color", "tf_align_frame_icp_color_device",
     "tf_align_icp_color_log", "tf_align_icp_color_residuals", "tf_align_icp_color_residuals_device",
     "tf_align_icp_color_model_maps", "tf_align_icp_color_model_maps_device", "tf_track_frame_color",
+    "tf_align_exposure_default", "tf_align_set_exposure", "tf_align_get_exposure", "tf_align_exposure_log",
+    "tf_align_exposure_estimate",
     "tf_track_accept_default", "tf_track_frame_device", "tf_integrate_frame_posed_device", "tf_track_integrate_device",
     "tf_pose_consts_download", "tf_integrate_frame_textured_posed_device", "tf_track_texture_device",
     "tf_pose_inverse_download",
@@ -233,6 +235,25 @@ class AlignIcpColorParamsC(C.Structure):
                 ("huber_photo", C.c_float), ("max_depth_jump", C.c_float)]
 
 
+class AlignExposureC(C.Structure):
+    _fields_ = [("unknowns", C.c_int32), ("carry", C.c_int32), ("gain0", C.c_float), ("offset0", C.c_float),
+                ("min_gain", C.c_float), ("max_gain", C.c_float)]
+
+
+class AlignExposureIter(C.Structure):
+    _fields_ = [("gain", C.c_double), ("offset", C.c_double), ("rank", C.c_int32), ("n_photo", C.c_int32),
+                ("P", C.c_double * 6), ("Q", C.c_double * 6), ("S_w", C.c_double), ("S_l", C.c_double),
+                ("S_ll", C.c_double), ("S_r", C.c_double), ("S_lr", C.c_double), ("d_offset", C.c_double),
+                ("d_gain", C.c_double)]
+
+
+# tf_align_exposure_iter as a numpy record
+ALIGN_EXPOSURE_ITER_DTYPE = np.dtype([("gain", "<f8"), ("offset", "<f8"), ("rank", "<i4"), ("n_photo", "<i4"),
+                                      ("P", "<f8", 6), ("Q", "<f8", 6), ("S_w", "<f8"), ("S_l", "<f8"), ("S_ll", "<f8"),
+                                      ("S_r", "<f8"), ("S_lr", "<f8"), ("d_offset", "<f8"), ("d_gain", "<f8")])
+assert ALIGN_EXPOSURE_ITER_DTYPE.itemsize == C.sizeof(AlignExposureIter)
+
+
 class TrackColorResult(C.Structure):
     _fields_ = [("icp", AlignColorResult), ("sdf", AlignColorResult), ("stage", C.c_int32), ("pose", C.c_float * 12)]
 
@@ -331,6 +352,22 @@ def AlignIcpGate(**kw):
             raise TypeError("tf_align_icp_gate has no field %r" % k)
         setattr(g, k, float(val))
     return g
+
+
+def AlignExposure(**kw):
+    """tf_align_exposure: the library's defaults (tf_align_exposure_default) with fields replaced by keyword"""
+    e = AlignExposureC()
+    rc = lib().tf_align_exposure_default(C.byref(e))
+    if rc != TF_OK:
+        raise TFError(rc, lib().tf_last_error().decode())
+    for k, val in kw.items():
+        if k in ("unknowns", "carry"):
+            setattr(e, k, int(val))
+        elif k in ("gain0", "offset0", "min_gain", "max_gain"):
+            setattr(e, k, float(val))
+        else:
+            raise TypeError("tf_align_exposure has no field %r" % k)
+    return e
 
 
 def AlignIcpPyramid(**kw):
@@ -600,6 +637,12 @@ def lib():
     L.tf_align_frame_icp_color.argtypes = [vp, fp, u8p, fp, fp, aqp, C.POINTER(AlignColorResult)]
     L.tf_align_frame_icp_color_device.argtypes = [vp, vp, vp, fp, vp, vp, fp, aqp, vp]
     L.tf_align_icp_color_log.argtypes = [vp, C.POINTER(AlignColorIter), C.c_int64, i64p]
+    aep = C.POINTER(AlignExposureC)
+    L.tf_align_exposure_default.argtypes = [aep]
+    L.tf_align_set_exposure.argtypes = [vp, aep]
+    L.tf_align_get_exposure.argtypes = [vp, aep, i32p]
+    L.tf_align_exposure_log.argtypes = [vp, C.c_int32, C.POINTER(AlignExposureIter), C.c_int64, i64p]
+    L.tf_align_exposure_estimate.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), i32p]
     L.tf_align_icp_color_residuals.argtypes = [vp, fp, u8p, fp, fp, fp, fp, aqp, fp, fp, u32q, i32p, fp]
     L.tf_align_icp_color_residuals_device.argtypes = [vp, vp, vp, fp, vp, vp, fp, aqp, vp, vp, vp, vp, vp]
     L.tf_align_icp_color_model_maps.argtypes = [vp, fp, fp, fp, aqp, fp, fp, fp]
@@ -1395,6 +1438,34 @@ class Volume:
         self._ck(self.L.tf_align_icp_residuals_device(self.h, d_depth or None, _p(pose, C.c_float), d_vertex or None,
                                                       d_normal or None, mp, C.byref(params), d_r or None, d_flags or None,
                                                       d_assoc or None))
+
+    # -- exposure compensation in the photometric aligners (tf_align_exposure.hip): a setting of the handle, off until set
+    def align_set_exposure(self, exposure=None):
+        """Compensate the frame's luma by a gain and an offset in align_frame_color, align_frame_icp_color, their residual maps
+        and track_frame_color (an AlignExposure); None: off."""
+        self._ck(self.L.tf_align_set_exposure(self.h, None if exposure is None else C.byref(exposure)))
+
+    def align_get_exposure(self):
+        """-> (on, AlignExposureC: the setting, zeros where none is set)"""
+        e, on = AlignExposureC(), C.c_int32(0)
+        self._ck(self.L.tf_align_get_exposure(self.h, C.byref(e), C.byref(on)))
+        return bool(on.value), e
+
+    def align_exposure_log(self, which):
+        """The exposure records of the last align_frame_color (which 0) or align_frame_icp_color / track_frame_color (which 1)
+        call -> a numpy record array (ALIGN_EXPOSURE_ITER_DTYPE), one per evaluation, parallel to the colour log; empty
+        where that call ran with the setting off."""
+        n = C.c_int64(0)
+        buf = (AlignExposureIter * TF_ALIGN_MAX_EVALUATIONS)()
+        self._ck(self.L.tf_align_exposure_log(self.h, int(which), buf, TF_ALIGN_MAX_EVALUATIONS, C.byref(n)))
+        k = min(n.value, TF_ALIGN_MAX_EVALUATIONS)
+        return np.frombuffer(buf, ALIGN_EXPOSURE_ITER_DTYPE, count=TF_ALIGN_MAX_EVALUATIONS)[:k].copy()
+
+    def align_exposure_estimate(self, which):
+        """-> (gain, offset, valid): the pair the last call of aligner `which` ended at"""
+        go, valid = (C.c_double * 2)(), C.c_int32(0)
+        self._ck(self.L.tf_align_exposure_estimate(self.h, int(which), go, C.byref(valid)))
+        return float(go[0]), float(go[1]), bool(valid.value)
 
     # -- the ICP's normal-compatibility gate (tf_align_icp_gate.hip): a setting of the handle, off until set
     def align_icp_set_gate(self, gate=None):

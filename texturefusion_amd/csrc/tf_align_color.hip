@@ -29,12 +29,15 @@
 // then tf_align_frame's damping, solve, update and stop rules (al_decide).  TF_ALIGN_TOO_FEW goes by the geometric n_valid.
 // With photo_weight == 0 or on a volume without colour the second term is an exact zero: pose, status and every geometric
 // sum are tf_align_frame's bit for bit.
+// With tf_align_set_exposure on, Lf is compensated by a gain and an offset that are estimated with the pose: the launches of
+// a call are tf_align_exposure.hip's then (its header states them), this file's state block and log stay the call's.
 // No atomics, no counters, no polling; every launch of a call is enqueued up front and reads one state word at its start.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <string.h>
 
+#include "tf_align_exposure.h"
 #include "tf_align_rows.h"
 #include "tf_volume.h"
 
@@ -52,21 +55,6 @@ struct CAlignDev {
   tf_align_color_iter* log;   // [TF_ALIGN_MAX_EVALUATIONS]
 };
 
-struct CAlignRowsArgs {
-  AlignRowsCommon c;
-  const float* depth;
-  const uint32_t* rgba;   // RGBA8, one word per pixel (r in the low byte)
-  const float* pose;      // 12 floats in the state block
-  const uint32_t* state;  // null: always run (tf_align_color_residuals)
-  float res, max_photo_residual, huber_photo;
-  size_t plane;
-  float* r;
-  float* grad;
-  float* rc;
-  float* gradc;
-  uint32_t* flags;
-  double* part;  // null: no sums
-};
 struct CAlignSolveArgs {
   AlignSolveCommon c;
   double l2;  // photo_weight squared
@@ -93,8 +81,7 @@ __global__ __launch_bounds__(kAlWaves * 64) void k_calign_rows(VolumeDev v, CAli
     fl = row.fl;
     if (fl == 15u && (c8 >> 24) != 0u && lum.okl) {
       fl |= 16u;
-      const float r8 = (float)(c8 & 255u), g8 = (float)((c8 >> 8) & 255u), b8 = (float)((c8 >> 16) & 255u);
-      const float lf = ((0.299f * r8 + 0.587f * g8) + 0.114f * b8) * (1.0f / 255.0f);
+      const float lf = al_luma(c8);
       rc = lum.lc - lf;
       if (lum.okt) {
         fl |= 32u;
@@ -175,8 +162,12 @@ int calign_enqueue(tf_volume* v, const float* d_depth, const uint8_t* d_rgba, co
   hipStream_t st = v->stream;
   AlignPose P;
   memcpy(P.p, pose, sizeof(P.p));
-  hipLaunchKernelGGL(k_calign_begin, dim3(1), dim3(64), 0, st, d, P, 0);
   const double l2 = (double)cp.photo_weight * (double)cp.photo_weight;
+  if (exposure_on(v))  // tf_align_set_exposure: the launches are tf_align_exposure.hip's, state and log stay this file's
+    return exposure_sdf_enqueue(v, ExposureOwn{d.ctl, d.pose_d, d.pose_f, d.pose_r, d.log}, P,
+                                crows_args(v, AlignRowsCommon{}, cp, d_depth, d_rgba), cp.geo, l2, d_result);
+  exposure_not_run(v, 0);
+  hipLaunchKernelGGL(k_calign_begin, dim3(1), dim3(64), 0, st, d, P, 0);
   align_walk(v, cp.geo, [&](const AlignRowsCommon& c, const AlignSolveCommon& sc) {
     CAlignRowsArgs ra = crows_args(v, c, cp, d_depth, d_rgba);
     ra.pose = d.pose_f; ra.state = &d.ctl->state; ra.part = d.part;
@@ -208,6 +199,8 @@ int cresiduals_enqueue(tf_volume* v, const float* d_depth, const uint8_t* d_rgba
   }
   AlignPose P;
   memcpy(P.p, pose, sizeof(P.p));
+  if (exposure_on(v))
+    return exposure_sdf_residuals(v, ExposureOwn{d.ctl, d.pose_d, d.pose_f, d.pose_r, d.log}, P, ra, sc.n_rows);
   hipLaunchKernelGGL(k_calign_begin, dim3(1), dim3(64), 0, st, d, P, 1);
   hipLaunchKernelGGL(k_calign_rows, dim3(sc.n_rows), dim3(kAlWaves * 64), 0, st, v->dev, ra);
   TF_HIP(hipGetLastError());

@@ -44,14 +44,17 @@
 // LDS: the rows kernel's 8 x 64 doubles (4096 B), the solve's 8 x 64; the map kernels none.  No atomics, no counters, no
 // polling; every launch of a call is enqueued up front, the map launches once per call ahead of the first rows launch.
 //
+// With tf_align_set_exposure on, Lf is compensated by a gain and an offset that are estimated with the pose: begin, rows
+// and solve of a call are tf_align_exposure.hip's then, the map kernels and this file's state block and log stay the call's.
+//
 // Not here: the depth pyramid (tf_align_icp_set_pyramid is not read by these calls; a level samples by stride); a
-// device-pose form (tf_track_*_device); a tf_relocalise hook; exposure or gain compensation; blurred images; a multi-rank
-// form.
+// device-pose form (tf_track_*_device); a tf_relocalise hook; blurred images; a multi-rank form.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <string.h>
 
+#include "tf_align_exposure.h"
 #include "tf_align_icp_normal.h"
 #include "tf_align_icp_rows.h"
 #include "tf_align_rows.h"
@@ -86,17 +89,6 @@ struct CicpMapArgs {
   float* Gv;
 };
 
-struct CicpRowsArgs {
-  IcpRowsArgs icp;
-  const uint32_t* rgba;  // RGBA8, one word per pixel (r in the low byte)
-  const float* L;
-  const float* Gu;
-  const float* Gv;
-  float max_photo_residual, huber_photo;
-  float c2, max_jump;    // the gate's (read by the gated variant only)
-  float* rc;
-  float* gradc;
-};
 struct CicpSolveArgs {
   AlignSolveCommon c;
   double l2;  // photo_weight squared
@@ -181,8 +173,7 @@ __global__ __launch_bounds__(kAlWaves * 64) void k_cicp_rows(CicpRowsArgs a) {
       const bool usable = ph.l >= 0.f && ph.gu == ph.gu && ph.gv == ph.gv;
       if (fl == (kGate ? 63u : 15u) && (c8 >> 24) != 0u && usable) {
         fl |= 256u;
-        const float r8 = (float)(c8 & 255u), g8 = (float)((c8 >> 8) & 255u), b8 = (float)((c8 >> 16) & 255u);
-        const float lf = ((0.299f * r8 + 0.587f * g8) + 0.114f * b8) * (1.0f / 255.0f);
+        const float lf = al_luma(c8);
         const float du = ph.uc - ph.uf, dv = ph.vc - ph.vf;
         rc = (ph.l + (ph.gu * du + ph.gv * dv)) - lf;
         const float ja = (g.c.fx * ph.gu) / ph.mz, jb = (g.c.fy * ph.gv) / ph.mz;
@@ -324,9 +315,16 @@ int cicp_enqueue(tf_volume* v, const float* d_depth, const uint8_t* d_rgba, cons
   CicpPoses P;
   memcpy(P.p, pose, sizeof(P.p));
   memcpy(P.m, model_pose, sizeof(P.m));
+  const double l2 = (double)p.photo_weight * (double)p.photo_weight;
+  if (exposure_on(v)) {  // tf_align_set_exposure: begin, rows and solve are tf_align_exposure.hip's, state and log stay this file's
+    cicp_maps_enqueue(v, d_vertex, d_normal, model_pose, p.max_depth_jump, m.L, m.Gu, m.Gv, m.Z);
+    return exposure_proj_enqueue(v, ExposureOwn{d.ctl, d.pose_d, d.pose_f, d.pose_r, d.log}, P.p, P.m,
+                                 cicp_rows_args(v, AlignRowsCommon{}, p, d_depth, d_rgba, d_vertex, d_normal, m), p.icp.geo, l2,
+                                 d_result);
+  }
+  exposure_not_run(v, 1);
   hipLaunchKernelGGL(k_cicp_begin, dim3(1), dim3(64), 0, st, d, P, 0);
   cicp_maps_enqueue(v, d_vertex, d_normal, model_pose, p.max_depth_jump, m.L, m.Gu, m.Gv, m.Z);
-  const double l2 = (double)p.photo_weight * (double)p.photo_weight;
   align_walk(v, p.icp.geo, [&](const AlignRowsCommon& c, const AlignSolveCommon& sc) {
     CicpRowsArgs ra = cicp_rows_args(v, c, p, d_depth, d_rgba, d_vertex, d_normal, m);
     ra.icp.pose = d.pose_f; ra.icp.state = &d.ctl->state; ra.icp.part = d.part;
@@ -360,6 +358,10 @@ int cicp_residuals_enqueue(tf_volume* v, const float* d_depth, const uint8_t* d_
   CicpPoses P;
   memcpy(P.p, pose, sizeof(P.p));
   memcpy(P.m, model_pose, sizeof(P.m));
+  if (exposure_on(v)) {
+    cicp_maps_enqueue(v, d_vertex, d_normal, model_pose, p.max_depth_jump, m.L, m.Gu, m.Gv, m.Z);
+    return exposure_proj_residuals(v, ExposureOwn{d.ctl, d.pose_d, d.pose_f, d.pose_r, d.log}, P.p, P.m, ra, sc.n_rows);
+  }
   hipLaunchKernelGGL(k_cicp_begin, dim3(1), dim3(64), 0, st, d, P, 1);
   cicp_maps_enqueue(v, d_vertex, d_normal, model_pose, p.max_depth_jump, m.L, m.Gu, m.Gv, m.Z);
   cicp_rows_launch(v, ra, sc.n_rows);
@@ -560,11 +562,17 @@ int tf_track_frame_color(tf_volume* v, const float* depth, const uint8_t* rgba, 
   tf_track_color_result t{};
   t.sdf.geo.status = -1;  // not run
   memcpy(t.pose, pose, sizeof(t.pose));
-  if ((rc = tf_align_frame_icp_color(v, depth, rgba, pose, nullptr, icp_params, &t.icp))) return rc;
+  // (tf_align_set_exposure: the second stage starts at the first stage's estimate, whatever carry says)
+  exposure_track_stage(v, 1);
+  rc = tf_align_frame_icp_color(v, depth, rgba, pose, nullptr, icp_params, &t.icp);
+  exposure_track_stage(v, 0);
+  if (rc) return rc;
   if (t.icp.geo.status <= TF_ALIGN_MAX_ITERS) {
     t.stage = 1;
     memcpy(t.pose, t.icp.geo.pose, sizeof(t.pose));
-    if ((rc = tf_align_frame_color(v, depth, rgba, t.icp.geo.pose, sdf_params, &t.sdf))) return rc;
+    rc = tf_align_frame_color(v, depth, rgba, t.icp.geo.pose, sdf_params, &t.sdf);
+    const int rx = exposure_track_stage(v, 2);
+    if (rc || (rc = rx)) return rc;
     if (t.sdf.geo.status <= TF_ALIGN_MAX_ITERS) {
       t.stage = 2;
       memcpy(t.pose, t.sdf.geo.pose, sizeof(t.pose));

@@ -31,6 +31,19 @@ struct IcpRowsArgs {
   double* part;  // null: no sums
 };
 
+// The argument block of the colour ICP's rows launch (k_cicp_rows, and k_ealign_proj_rows of tf_align_exposure.hip)
+struct CicpRowsArgs {
+  IcpRowsArgs icp;
+  const uint32_t* rgba;  // RGBA8, one word per pixel (r in the low byte)
+  const float* L;
+  const float* Gu;
+  const float* Gv;
+  float max_photo_residual, huber_photo;
+  float c2, max_jump;    // the gate's (read by the gated variant only)
+  float* rc;
+  float* gradc;
+};
+
 // Bits 1 to 3 of a pixel whose depth is in range (bit 0; p is its point, tf_align_icp.hip's header has the arithmetic):
 // fl with bit 0 and whichever of bits 1 to 3 hold, the associated model pixel (-1 without bit 1), the residual s and the
 // model normal g (0 without bit 2), m2 = |nm|^2 as the hit test formed it (0 without bit 1).

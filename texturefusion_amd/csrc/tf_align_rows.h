@@ -15,6 +15,8 @@
 //   stop rules    n_valid < min_valid: TF_ALIGN_TOO_FEW, the call stops.  Else, unless this is the closing evaluation, the
 //                 damped solve: a failed pivot is TF_ALIGN_SINGULAR and the call stops; a step with |v| < eps_t and
 //                 |w| < eps_r finishes the level, and on the last level the status is TF_ALIGN_CONVERGED.
+//   exposure      with tf_align_set_exposure on, the photometric aligners add a third row of sums (al_exposure_row_sums) and
+//                 their solve launch is al_solve_color_exposure: the pair eliminated ahead of the join, stepped after al_decide.
 //   state word    bit 0: stopped, bits 8..: levels that are finished.  Every launch of a call is enqueued up front and
 //                 reads this word first (al_idle); there are no atomics, no counters and no polling.
 #pragma once
@@ -23,6 +25,7 @@
 
 #include <math.h>
 
+#include "tf_align_exposure_solve.h"
 #include "tf_align_solve.h"
 #include "tf_align_tree.h"
 #include "../../include/tf_fusion.h"
@@ -169,6 +172,31 @@ __device__ __forceinline__ AlSdfRow al_sdf_row(const VolumeDev& v, const AlignRo
   return r;
 }
 
+// The luma Lf of a frame pixel's RGBA8 word (r in the low byte), in [0, 1]: the photometric rows' (tf_align_color.hip's
+// header), and what the exposure pair of tf_align_set_exposure compensates: Lfe = gain * Lf + offset.
+__device__ __forceinline__ float al_luma(uint32_t c8) {
+  const float r8 = (float)(c8 & 255u), g8 = (float)((c8 >> 8) & 255u), b8 = (float)((c8 >> 16) & 255u);
+  return ((0.299f * r8 + 0.587f * g8) + 0.114f * b8) * (1.0f / 255.0f);
+}
+__device__ __forceinline__ float al_luma_exposed(float lf, const float* pair) { return pair[0] * lf + pair[1]; }
+
+// The argument block of the rows launch of tf_align_frame_color (k_calign_rows, and k_ealign_rows of tf_align_exposure.hip)
+struct CAlignRowsArgs {
+  AlignRowsCommon c;
+  const float* depth;
+  const uint32_t* rgba;   // RGBA8, one word per pixel (r in the low byte)
+  const float* pose;      // 12 floats in the state block
+  const uint32_t* state;  // null: always run (tf_align_color_residuals)
+  float res, max_photo_residual, huber_photo;
+  size_t plane;
+  float* r;
+  float* grad;
+  float* rc;
+  float* gradc;
+  uint32_t* flags;
+  double* part;  // null: no sums
+};
+
 // A row's share of the sums: J = [g, l x g] with gradient g and lever l, the Huber weight of the residual r, an exact zero
 // in every term where the pixel is not valid, the tile's sums through the wave tree (lane l ends up with entry
 // al_entry(l)) into the wave's line of `wsum`, `at` doubles in.  al_store_rows follows, once for all rows of the pixel.
@@ -185,6 +213,28 @@ __device__ __forceinline__ void al_row_sums(double (&wsum)[kAlWaves][kRow], int 
     for (int i = 0; i < 6; ++i) J[i] = 0.f;
   }
   const double total = al_tile_sum(J, w, r, valid ? 1.0f : 0.0f, in ? 1.0f : 0.0f, px.lane);
+  if (!(px.lane & 1)) wsum[px.wave][at + al_entry(px.lane)] = total;
+}
+// The exposure row's share (tf_align_set_exposure): the photometric row's own operands wJc_i = wc * Jc_i, wc, rc and the
+// frame's uncompensated luma lf, an exact zero in every term where the pixel is not photometrically valid, through the
+// same tree with the second pair table (tf_align_tree.h states the 17 sums and their order) into `at` of the wave's line.
+template <int kRow>
+__device__ __forceinline__ void al_exposure_row_sums(double (&wsum)[kAlWaves][kRow], int at, const AlPixel& px, float gx,
+                                                     float gy, float gz, float lx, float ly, float lz, float rc, float lf,
+                                                     float huber, bool valid) {
+  // (J, w and the zeroing are al_row_sums' own lines: the compiler forms them once for both rows)
+  float J[6] = {gx, gy, gz, ly * gz - lz * gy, lz * gx - lx * gz, lx * gy - ly * gx};
+  const float ar = fabsf(rc);
+  float w = (huber == 0.f || ar <= huber) ? 1.0f : huber / ar;
+  if (!valid) {
+    w = 0.f; rc = 0.f; lf = 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) J[i] = 0.f;
+  }
+  float wJ[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) wJ[i] = w * J[i];
+  const double total = al_exposure_tile_sum(wJ, w, lf, rc, valid ? 1.0f : 0.0f, px.lane);
   if (!(px.lane & 1)) wsum[px.wave][at + al_entry(px.lane)] = total;
 }
 // the workgroup's eight tiles in wave order, one plain-stored row of kRow doubles per workgroup
@@ -327,6 +377,30 @@ __device__ __forceinline__ void al_solve_pose(AlignCtl* ctl, tf_align_iter* log,
 // A whole solve launch of an aligner with one pose and two rows of sums, a geometric and a photometric one, joined as
 // M = A_g + l2 A_c, b = b_g + l2 b_c (k_calign_solve, k_cicp_solve): one workgroup of 256 threads.
 constexpr int kCaRow = 2 * kAlRow;   // doubles of a workgroup's partial sums: the geometric row, then the photometric one
+// the photometric row's counts of an evaluation into its record (the first evaluation's are kept for the result), and the
+// result of a call with a photometric row
+struct AlPhotoEval {
+  int n_photo;
+  float rms;
+};
+template <int kRow>
+__device__ __forceinline__ AlPhotoEval al_fill_photo(tf_align_color_iter* rec, const double (&red)[8][kRow], AlignCtl& c) {
+  const double sum_rc2 = al_total(red, kAlRow + kAlR2);
+  AlPhotoEval ph;
+  ph.n_photo = (int)al_total(red, kAlRow + kAlNv);
+  ph.rms = ph.n_photo > 0 ? (float)sqrt(sum_rc2 / (double)ph.n_photo) : 0.f;
+  rec->n_photo = ph.n_photo; rec->pad = 0;
+  rec->sum_rc2 = sum_rc2; rec->sum_wrc2 = al_total(red, kAlRow + kAlWr2);
+  if (c.n_eval == 0) { c.n_photo_first = ph.n_photo; c.rms_photo_first = ph.rms; }
+  return ph;
+}
+__device__ __forceinline__ void al_fill_color_result(tf_align_color_result* out, const AlignCtl& c, const AlEval& ev,
+                                                     const AlPhotoEval& ph, const double (&pose)[12]) {
+  al_fill_result(&out->geo, c, ev);
+  al_put_pose(out->geo.pose, pose);
+  out->n_photo_first = c.n_photo_first; out->n_photo_last = ph.n_photo;
+  out->rms_photo_first = c.rms_photo_first; out->rms_photo_last = ph.rms;
+}
 __device__ __forceinline__ void al_solve_color(AlignCtl* ctl, tf_align_color_iter* log, double* pose_d, float* pose_f,
                                                const double* part, const AlignSolveCommon& a, double l2,
                                                tf_align_color_result* out) {
@@ -354,22 +428,81 @@ __device__ __forceinline__ void al_solve_color(AlignCtl* ctl, tf_align_color_ite
     rec->bc[i] = tc;
     bb[i] = bb[i] + l2 * tc;
   }
-  const double sum_rc2 = al_total(red, kAlRow + kAlR2);
-  const int n_photo = (int)al_total(red, kAlRow + kAlNv);
-  const float rms_c = n_photo > 0 ? (float)sqrt(sum_rc2 / (double)n_photo) : 0.f;
-  rec->n_photo = n_photo; rec->pad = 0;
-  rec->sum_rc2 = sum_rc2; rec->sum_wrc2 = al_total(red, kAlRow + kAlWr2);
-  if (c.n_eval == 0) { c.n_photo_first = n_photo; c.rms_photo_first = rms_c; }
+  const AlPhotoEval ph = al_fill_photo(rec, red, c);
   al_count(c, ev);
   if (al_decide(c, a, ev.n_valid, M, bb, &rec->geo, xi)) {
     align_update(pose, xi);
     al_keep_pose(pose_d, pose_f, pose);
   }
   *ctl = c;
-  al_fill_result(&out->geo, c, ev);
-  al_put_pose(out->geo.pose, pose);
-  out->n_photo_first = c.n_photo_first; out->n_photo_last = n_photo;
-  out->rms_photo_first = c.rms_photo_first; out->rms_photo_last = rms_c;
+  al_fill_color_result(out, c, ev, ph, pose);
+}
+
+// The same launch with the exposure pair (tf_align_set_exposure): three rows of sums per workgroup, the pair eliminated
+// from the photometric system ahead of the join and stepped after al_decide (tf_align_exposure_solve.h states every
+// operation).  k_ealign_solve of tf_align_exposure.hip, for both photometric aligners.
+constexpr int kCeRow = 3 * kAlRow;  // the geometric row, the photometric one, the exposure row (tf_align_tree.h: kAlExp*)
+struct AlExposureCtl {   // the pair of a call, in the exposure state block
+  double pair_d[2];      // (gain, offset) between iterations
+  float pair_f[2];       // the same rounded: what the rows kernels compensate with
+  float pair_r[2];       // the residual maps' pair (the last alignment's state stays as it is)
+  int32_t valid, n_eval; // the last call ended with status <= TF_ALIGN_MAX_ITERS; its evaluations
+};
+struct AlExposureArgs {
+  AlExposureCtl* x;
+  tf_align_exposure_iter* log;
+  double* cell;          // the handle's start pair
+  int unknowns, carry;
+  double min_gain, max_gain;
+};
+__device__ __forceinline__ void al_solve_color_exposure(AlignCtl* ctl, tf_align_color_iter* log, double* pose_d, float* pose_f,
+                                                        const double* part, const AlignSolveCommon& a, double l2,
+                                                        tf_align_color_result* out, const AlExposureArgs& e) {
+  if (al_idle(&ctl->state, a.level)) return;
+  __shared__ double red[8][kCeRow];
+  al_add_rows(part, a.n_rows, red);
+  if (threadIdx.x != 0) return;
+  AlignCtl c = *ctl;
+  tf_align_color_iter* rec = al_record(log, c);
+  tf_align_exposure_iter* xrec = al_record(e.log, c);
+  double pose[12], M[21], bb[6], xi[6], Ac[21], bc[6], S[kExpSums], pair[2], de[2];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) pose[i] = pose_d[i];
+  pair[0] = e.x->pair_d[0]; pair[1] = e.x->pair_d[1];
+  const AlEval ev = al_fill_iter(&rec->geo, a, [&](int i) { return al_total(red, i); }, pose, M, bb);
+#pragma unroll
+  for (int i = 0; i < 21; ++i) { Ac[i] = al_total(red, kAlRow + kAlA + i); rec->Ac[i] = Ac[i]; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { bc[i] = al_total(red, kAlRow + kAlB + i); rec->bc[i] = bc[i]; }
+#pragma unroll
+  for (int i = 0; i < kExpSums; ++i) S[i] = al_total(red, 2 * kAlRow + i);
+  const AlPhotoEval ph = al_fill_photo(rec, red, c);
+  ExposureElim el;
+  exposure_eliminate(S, e.unknowns, Ac, bc, &el);
+#pragma unroll
+  for (int i = 0; i < 21; ++i) M[i] = M[i] + l2 * Ac[i];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) bb[i] = bb[i] + l2 * bc[i];
+  xrec->gain = pair[0]; xrec->offset = pair[1]; xrec->rank = el.rank; xrec->n_photo = ph.n_photo;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { xrec->P[i] = S[kExpP + i]; xrec->Q[i] = S[kExpQ + i]; }
+  xrec->S_w = S[kExpSw]; xrec->S_l = S[kExpSl]; xrec->S_ll = S[kExpSll]; xrec->S_r = S[kExpSr]; xrec->S_lr = S[kExpSlr];
+  xrec->d_offset = 0.0; xrec->d_gain = 0.0;
+  al_count(c, ev);
+  if (al_decide(c, a, ev.n_valid, M, bb, &rec->geo, xi)) {
+    align_update(pose, xi);
+    al_keep_pose(pose_d, pose_f, pose);
+    exposure_step(S, el, xi, de);
+    exposure_apply(pair, el.rank, de, e.min_gain, e.max_gain);
+    xrec->d_offset = de[0]; xrec->d_gain = de[1];
+    e.x->pair_d[0] = pair[0]; e.x->pair_d[1] = pair[1];
+    e.x->pair_f[0] = (float)pair[0]; e.x->pair_f[1] = (float)pair[1];
+  }
+  *ctl = c;
+  const bool held = c.status <= TF_ALIGN_MAX_ITERS;
+  e.x->valid = held ? 1 : 0; e.x->n_eval = c.n_eval;
+  if (a.closing && e.carry && held) { e.cell[0] = pair[0]; e.cell[1] = pair[1]; }
+  al_fill_color_result(out, c, ev, ph, pose);
 }
 
 }  // namespace tf

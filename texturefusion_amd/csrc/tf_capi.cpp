@@ -840,6 +840,7 @@ int tf_volume_reset(tf_volume* v) {
   align_group_release(v);
   align_icp_release(v);
   align_icp_color_release(v);
+  align_exposure_release(v);
   reloc_release(v);
   devpose_release(v);
   model_release(v);

@@ -226,6 +226,19 @@ struct AlignIcpColorState {
   size_t map_pixels = 0;  // pixels each plane of `maps` has room for
 };
 
+// Exposure compensation of the photometric aligners (tf_align_exposure.hip): the setting of tf_align_set_exposure (off in a
+// new state, so off again after tf_volume_reset), the cell that holds the start pair (two f64: gain, offset), and one state
+// block per aligner (0: tf_align_color.hip's calls, 1: tf_align_icp_color.hip's) with the pair between iterations, the log
+// and three rows of partial sums per workgroup.  ran[w]: the aligner's last call ran with the setting on.
+struct AlignExposureState {
+  bool on = false;
+  tf_align_exposure e{};
+  DevMem cell;
+  AlignBlock st[2];
+  bool ran[2] = {false, false};
+  bool hold_carry = false;  // tf_track_frame_color's first stage: the estimate goes to the cell whatever carry says
+};
+
 // Relocalisation against the cached keyframes (tf_reloc.hip): the configuration, and the index -- one block holding every
 // row's descriptor, the query's and the scores; the host keeps which keyframe a row belongs to.  Empty until configured.
 struct RelocState {
@@ -347,6 +360,7 @@ struct tf_volume {
   tf::AlignBlock align, align_color, align_group;
   tf::AlignIcpState align_icp;
   tf::AlignIcpColorState align_icp_color;
+  tf::AlignExposureState align_exposure;
   tf::RelocState reloc;
   tf::DevMem devpose;  // one PoseConsts (tf_devpose.h): what k_pose_consts derives from a pose cell; null until first use
   tf::DevMem devpose_inv;  // one PoseInverse: the cell's rigid inverse for the patch stage, written by the same launch
@@ -494,7 +508,8 @@ void align_release(tf_volume* v);        // these free the state block of tf_ali
 void align_color_release(tf_volume* v);  // of tf_align_color.hip,
 void align_group_release(tf_volume* v);  // of tf_align_group.hip,
 void align_icp_release(tf_volume* v);    // of tf_align_icp.hip with its maps,
-void align_icp_color_release(tf_volume* v);  // and of tf_align_icp_color.hip with its maps
+void align_icp_color_release(tf_volume* v);  // of tf_align_icp_color.hip with its maps,
+void align_exposure_release(tf_volume* v);   // and of tf_align_exposure.hip with its cell: the setting is off again
 // what tf_align_frame_icp refuses a call for, but null map and result pointers (tf_align_icp.hip; with_ray: the form
 // raycasts the model itself), for the colour ICP to refuse the same
 int align_icp_check(tf_volume* v, const float* depth, const float* pose, const float* model_pose, const tf_align_icp_params* p,

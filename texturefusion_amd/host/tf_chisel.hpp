@@ -884,6 +884,41 @@ class Chisel {
     log.resize((size_t)n);
     return log;
   }
+  // Exposure compensation of the photometric aligners (tf_align_set_exposure): the frame's luma is compensated by a gain
+  // and an offset that are estimated with the pose, so that a camera with auto-exposure does not pull the pose.  A setting of
+  // this map, read by AlignFrameToModelColor and the colour ICP; off until set and off again after a reset.
+  // exposure == nullptr: the library's defaults (gain and offset estimated from (1, 0), no carry).
+  void SetAlignExposure(const tf_align_exposure* exposure = nullptr) {
+    tf_align_exposure def;
+    if (!exposure) {
+      tf_check(tf_align_exposure_default(&def), "SetAlignExposure");
+      exposure = &def;
+    }
+    tf_check(tf_align_set_exposure(vol, exposure), "SetAlignExposure");
+  }
+  void ClearAlignExposure() { tf_check(tf_align_set_exposure(vol, nullptr), "ClearAlignExposure"); }
+  // the setting (zeros where none is set); returns whether it is on
+  bool GetAlignExposure(tf_align_exposure* out) {
+    int32_t on = 0;
+    tf_check(tf_align_get_exposure(vol, out, &on), "GetAlignExposure");
+    return on != 0;
+  }
+  // (gain, offset) the last AlignFrameToModelColor (which 0) or colour ICP (which 1) ended at; false where that call did not
+  // run with the setting on or did not end with status <= TF_ALIGN_MAX_ITERS
+  bool AlignExposureEstimate(int32_t which, double* gain, double* offset) {
+    double go[2];
+    int32_t valid = 0;
+    tf_check(tf_align_exposure_estimate(vol, which, go, &valid), "AlignExposureEstimate");
+    *gain = go[0]; *offset = go[1];
+    return valid != 0;
+  }
+  std::vector<tf_align_exposure_iter> AlignExposureLog(int32_t which) {
+    std::vector<tf_align_exposure_iter> log(TF_ALIGN_MAX_EVALUATIONS);
+    int64_t n = 0;
+    tf_check(tf_align_exposure_log(vol, which, log.data(), (int64_t)log.size(), &n), "AlignExposureLog");
+    log.resize((size_t)n);
+    return log;
+  }
   // AlignFrameToModel for a keyframe group in one call (tf_align_group): up to seven host depth images of the readers'
   // camera with their approximate poses; body[k] names the rigid body frame k belongs to (empty: all frames are one body;
   // bodies are numbered by first appearance, a body's anchor is its first frame).  A body moves as one: a frame that
